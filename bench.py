@@ -21,13 +21,20 @@ Steps are issued through the library's asynchronous C-ABI (rafft_fold_submit / r
 in flight - continuous batching: queued batches with identical parameters are folded as ONE wave by the library's
 scheduler (fewer, fuller kernel launches), and the nearly empty last folding steps of step k (only the longest sequences still fold)
 run beside the busy first steps of step k+1.  Every step is waited for, and its result freed, inside the timed
-region.  `ms_per_call_sequential` is the latency of one synchronous rafft_fold_batch call for comparison.
+region (with --dump-outputs the last step's result is freed once the clock has stopped).  `ms_per_call_sequential` is the
+latency of one synchronous rafft_fold_batch call for comparison.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (expand_kernel<64>): algorithmic bytes
 (per region 3n + 16*min(K,2n-1), per structure 3L) per launch / mean launch duration measured with HIP
 events on the library's stream; `issue_frac` is its instruction-issue roofline from the SQ counters of profiles/.
 `cpu_baseline` times the CPU oracle (oracle/rafft_oracle.c, a port of the reference algorithm) with one process per
 core on the same workload.
+
+A plain run sets up, warms up, times the steps and prints the line; the figures that take runs of their own come with
+`--full`: the CPU baseline and the parity of the beams against it, steady state, call latencies, the Python API, per-stage
+kernel times, the share of guessed table entries, the 4x larger batch, strong scaling and sharded parity (N > 1) and
+BASELINE configs[3] (N > 1, or BENCH_CFG4=1).  `--no-cpu-baseline` and `--no-extras` drop parts of a `--full` run.
+`--dump-outputs DIR` writes the final beams of the last timed step as .npy files (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -116,12 +123,13 @@ class Folder:
         self.lib.rafft_free_result(res)
         assert ok
 
-    def run(self, steps, depth=PIPELINE_DEPTH):
-        """`steps` passes, `depth` in flight; every pass waited for and freed before this returns"""
+    def run(self, steps, depth=PIPELINE_DEPTH, keep_last=False):
+        """`steps` passes, `depth` in flight; every pass waited for and freed before this returns, but for the last one when
+        `keep_last`: its result is returned and the caller frees it"""
         if self.n == 0:
-            return
+            return None
         if depth == 1:          # one call at a time: the synchronous entry point (rafft_fold_batch), as a blocking caller would use it
-            for _ in range(steps):
+            for step in range(steps):
                 res = C.POINTER(self.N.Result)()
                 self.N.check(self.lib.rafft_fold_batch(C.byref(self.p), self.n, self.arr, self.lens, self.device, C.byref(res)))
                 st = self.N.Stats()
@@ -129,16 +137,22 @@ class Folder:
                 for k, v in st.as_dict().items():
                     self.agg[k] = self.agg.get(k, 0) + v
                 ok = res.contents.n_failed == 0
+                if keep_last and step == steps - 1:
+                    return res
                 self.lib.rafft_free_result(res)
                 assert ok
-            return
+            return None
         q = []
         for _ in range(steps):
             q.append(self.submit())
             if len(q) >= depth:
                 self.wait(q.pop(0))
         while q:
-            self.wait(q.pop(0))
+            job = q.pop(0)
+            if keep_last and not q:
+                return self.wait(job, keep=True)
+            self.wait(job)
+        return None
 
     def beams(self, res):
         out = []
@@ -230,6 +244,55 @@ def csrc_digest():
     return h.hexdigest()[:16]
 
 
+DUMP_SAMPLE_BYTES = 40 << 20    # the dot-brackets of a seeded sample of sequences, at most (worst case: every beam full)
+
+
+def beam_records(res, n):
+    """what a caller of the C-ABI receives, per sequence of a result: (status, dcal of the final beam as int32, its
+    dot-brackets as an (n_structs, length) uint8 array)"""
+    import numpy as np
+    out = []
+    for i in range(n):
+        sr = res.contents.seq[i]
+        L, k = sr.length, sr.n_structs
+        if k:
+            dcal = np.ctypeslib.as_array(sr.dcal, (k,)).copy()
+            db = np.frombuffer(C.string_at(sr.db, k * (L + 1)), np.uint8).reshape(k, L + 1)[:, :L]
+        else:
+            dcal, db = np.zeros(0, np.int32), np.zeros((0, max(L, 0)), np.uint8)
+        out.append((int(sr.status), dcal, db))
+    return out
+
+
+def dump_outputs(path, recs, lengths, max_stack):
+    """the final beams of the last timed step, one record per sequence of the step (beam_records), as .npy files:
+    status and n_structs per sequence, dcal (integer energies, decacalories per mol) and n_pairs per final structure in
+    beam order, and the dot-brackets ('.' 0, '(' 1, ')' 2) of every final structure of a fixed, seeded sample of the
+    sequences (structures_sample_seq: their indices) - drawn from the lengths only, so every build dumps the same sample"""
+    import numpy as np
+    order = np.random.default_rng(2296).permutation(len(lengths))
+    budget, pick = DUMP_SAMPLE_BYTES // 4, []
+    for i in order:
+        if lengths[i] * max_stack > budget:
+            break
+        budget -= lengths[i] * max_stack
+        pick.append(int(i))
+    pick.sort()
+    code = np.full(256, -1, np.float32)
+    code[ord(".")], code[ord("(")], code[ord(")")] = 0, 1, 2
+    arrays = {"status": np.array([r[0] for r in recs], np.float64),
+              "n_structs": np.array([len(r[1]) for r in recs], np.float64),
+              "dcal": np.concatenate([r[1] for r in recs]).astype(np.float64),
+              "n_pairs": np.concatenate([(r[2] == ord("(")).sum(axis=1) for r in recs]).astype(np.float32),
+              "structures_sample": np.concatenate([code[recs[i][2]].ravel() for i in pick] or [np.zeros(0, np.float32)]),
+              "structures_sample_seq": np.array(pick, np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64e6, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -238,9 +301,15 @@ def main():
     ap.add_argument("--nb-mode", type=int, default=100)
     ap.add_argument("--max-stack", type=int, default=50)
     ap.add_argument("--max-branch", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also every figure that takes runs of its own (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline and the parity against it")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: without the other extras (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the final beams of the last timed step to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    cpu_leg = args.full and not args.no_cpu_baseline
+    extras_leg = args.full and not args.no_extras
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -260,13 +329,14 @@ def main():
     # (fork-based pool; the timed GPU region below is unaffected)
     seqs = load_bench_sequences()
     cpu, cpu_finals = None, {}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and cpu_leg:
         cpu, cpu_finals = cpu_baseline(seqs, args.nb_mode, args.max_stack, args.max_branch)
 
-    import torch
-    import torch.distributed as dist
     backend, gloo = None, None
     if world > 1:
+        # (torch only for the process group: one GPU needs none of it, and its first import can take a while)
+        import torch
+        import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local_rank)
         # RCCL ("nccl") carries only the barrier and the max-reduction of the elapsed time: the fold itself
@@ -277,7 +347,6 @@ def main():
             gloo = dist.new_group(backend="gloo")       # host-side gather of result records (outside the timed region)
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
-    torch.cuda.set_device(local_rank)
 
     from rafft_amd import _native as N
     from rafft_amd import sharding
@@ -300,7 +369,9 @@ def main():
     def barrier():
         if world > 1:
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
+        else:
+            assert lib.hipDeviceSynchronize() == 0        # (the HIP runtime the library is bound to)
 
     def allmax(x):
         if world > 1:
@@ -313,7 +384,7 @@ def main():
     # the WHOLE final beam (every structure, in order, with its exact dcal) identical; energy MAE in kcal/mol over
     # all beam rows (the metric's second half)
     parity = None
-    if cpu_finals:
+    if cpu_finals:      # (--full only)
         res = full.wait(full.submit(), keep=True, stats=False)
         beams = full.beams(res)
         lib.rafft_free_result(res)
@@ -337,9 +408,14 @@ def main():
     # (weak scaling), so every rank's scheduler sees the N = 1 stream of batches.
     DEPTH_RUN = PIPELINE_DEPTH
     # (a fresh box hands over a GPU in its low-power state: half a second of the same work, untimed, before the W warm-up
-    #  steps, so that the clocks have ramped whatever W is)
+    #  steps, so that the clocks have ramped whatever W is.  That half second starts after a first pass: the first device
+    #  allocations of a process have been seen to take 2.5 s on a box where another process had just exited, and a pre-warm
+    #  that spent its half second waiting for them would do one pass of work)
+    prewarm_s = float(os.environ.get("BENCH_PREWARM_S", "0.5"))
+    if prewarm_s > 0:
+        mine.run(DEPTH_RUN, depth=DEPTH_RUN)
     t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < float(os.environ.get("BENCH_PREWARM_S", "0.5")):
+    while time.perf_counter() - t_pre < prewarm_s:
         mine.run(DEPTH_RUN, depth=DEPTH_RUN)
     mine.run(args.warmup, depth=DEPTH_RUN)
     agg_untimed = dict(mine.agg)        # (pre-warm and warmup launches: with the timed ones they are what rocprofv3 averages over)
@@ -354,7 +430,7 @@ def main():
 
     a0 = alloc_counters()
     t0 = time.perf_counter()
-    mine.run(args.steps, depth=DEPTH_RUN)
+    last = mine.run(args.steps, depth=DEPTH_RUN, keep_last=bool(args.dump_outputs))
     el_own = time.perf_counter() - t0          # this rank's own steps done (before the barrier)
     barrier()
     el = allmax(time.perf_counter() - t0)
@@ -383,8 +459,28 @@ def main():
         print(f"[bench] timed region ends t={time.monotonic():.3f}", file=sys.stderr, flush=True)
     agg = dict(mine.agg)
 
+    # --dump-outputs: the result of the last timed step (kept instead of freed inside the timed region), gathered in the order of
+    # the step's global batch
+    if args.dump_outputs:
+        recs = []
+        if last is not None:
+            ok = last.contents.n_failed == 0
+            recs = beam_records(last, mine.n)
+            lib.rafft_free_result(last)
+            assert ok
+        if world > 1:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object((shard_idx, recs), parts, dst=0, group=gloo)
+            if rank == 0:
+                recs = [None] * (n * world)
+                for idx, part in parts:
+                    for i, r in zip(idx, part):
+                        recs[i] = r
+        if rank == 0:
+            dump_outputs(args.dump_outputs, recs, [len(seqs[i % n]) for i in range(n * world)], args.max_stack)
+
     extras = {}
-    if not args.no_extras:
+    if extras_leg:
         # steady state (outside `value`): at least two seconds of the same sharded steps, so that a short timed region - whose
         # start-up and drain are a visible part at N >= 4, where every rank folds one or two merged waves - has a figure beside it
         # that is neither
@@ -472,7 +568,7 @@ def main():
     # per-stage kernel times: one extra call, outside the timed region, with every stage bracketed by HIP events
     # (the timed steps carry events only around the dominant kernel - a pair around every kernel costs ~1.3 ms)
     stage_ms = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras_leg:
         os.environ["RAFFT_SPANS"] = "2"
         full.agg = {}
         full.wait(full.submit())
@@ -481,7 +577,7 @@ def main():
     # the drop-in Python API on the same workload (outside the timed region): rafft_amd.fold_batch returns lazily
     # materialised rows, so it costs what the C call costs
     py_api = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras_leg:
         rafft_amd.fold_batch(seqs, args.nb_mode, args.max_stack, args.max_branch)
         t1 = time.perf_counter()
         for _ in range(5):
@@ -504,7 +600,7 @@ def main():
     # such an entry is right in ~9 of 10 cases; no reference-held energy row pins it) - per workload, in the record and not only in the
     # design notes.  configs[2] (this set), configs[1] (1000 random sequences of 200 nt, ms=50), a sample of configs[3] (ms=200)
     guessed = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras_leg:
         import numpy as np
 
         def guessed_share(seq_list, ms, every=1):
@@ -536,7 +632,7 @@ def main():
     # informational, outside the timed region: the same call on a 4x larger batch (the set replicated 4 times in
     # ONE rafft_fold_batch call).  Never part of `value`.
     scaling_info = None
-    if world == 1 and not args.no_cpu_baseline and not args.no_extras:
+    if world == 1 and cpu_leg and extras_leg:
         R = 4
         big = Folder(lib, N, p, seqs * R, local_rank)
         best = None

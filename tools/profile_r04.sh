@@ -5,7 +5,7 @@
 #      2.-6. PMC passes, each in its own run, synchronous calls (4 batches): FETCH_SIZE | WRITE_SIZE | SQ issue | SQ mix | lanes + LDS conflicts
 #   B. BASELINE configs[3], one GPU's LPT shard (2048 sequences, L 100..3000, ms=200; tools/ab_cfg4.py, 3 calls)
 #      7. kernel trace + stats   8.-9. FETCH_SIZE | WRITE_SIZE   10. SQ issue  11. lanes
-#   C. BASELINE configs[3] whole on one GPU (BENCH_CFG4=1 python bench.py): its bench line
+#   C. BASELINE configs[3] whole on one GPU (BENCH_CFG4=1 python bench.py --full): its bench line
 # The digest of rafft_amd/csrc of the tree that RAN goes beside the raw files; tools/pmc_summary.py (run in the build container, where
 # git knows the commit) turns gpurun_out/r04_prof into profiles/r04_*.  (Under rocprofv3 the program itself follows `--`.)
 set -e
@@ -45,6 +45,6 @@ echo "cfg4 sq done" >> $OUT/progress.log
 # the kernel traces of the PMC passes are not needed beside the counter files, and the raw trace of the cfg3 loop is big
 rm -f $OUT/pmc_*/p_kernel_trace.csv $C4/pmc_*/p_kernel_trace.csv
 # ---- C. configs[3] whole on one GPU
-cd $R && BENCH_CFG4=1 timeout -k 10 500 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_cfg4_n1.json 2> $OUT/bench_cfg4_n1.err || echo "cfg4 whole failed" >> $OUT/progress.log
+cd $R && BENCH_CFG4=1 timeout -k 10 500 python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $OUT/bench_cfg4_n1.json 2> $OUT/bench_cfg4_n1.err || echo "cfg4 whole failed" >> $OUT/progress.log
 echo "all done" >> $OUT/progress.log
 du -sh $OUT

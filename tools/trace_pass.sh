@@ -8,4 +8,4 @@ python3 -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.csrc
 cd /tmp && export TMPDIR=/tmp
 BENCH_PREWARM_S=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python3 $R/bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 > $OUT/trace_bench.json 2> $OUT/trace.err
 python3 $R/tools/cu_share.py $OUT/trace/t_kernel_trace.csv > $OUT/cu_share.json || true
-cd $R && python3 bench.py --gpus 1 --steps 20 --warmup 5 > $R/gpurun_out/r04_bench_n1.json 2> $R/gpurun_out/r04_bench_n1.err
+cd $R && python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > ${OUT%/*}/r04_bench_n1.json 2> ${OUT%/*}/r04_bench_n1.err
