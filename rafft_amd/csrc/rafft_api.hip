@@ -61,8 +61,8 @@ struct Workspace {
     hipStream_t stream = nullptr;
     hipStream_t cls_stream[NCLS] = {};
     hipStream_t copy_stream = nullptr;   // result rows of sequences that finish early leave while the others still fold
-    hipEvent_t ev_fork = nullptr, ev_join[NCLS] = {}, ev_hot[2] = {}, ev_copy = nullptr;
-    void *hot = nullptr;                 // pinned, 2 x 1 KiB: the read-back slots of two consecutive steps (the host issues a step ahead)
+    hipEvent_t ev_fork = nullptr, ev_join[NCLS] = {}, ev_hot = nullptr, ev_copy = nullptr;
+    void *hot = nullptr;                 // pinned, 1 KiB: the read-back slot of the running step
     // named device buffers (grow-only)
     Buf codes, seq_off, seq_len, beam, beam_n, done, nsteps, ch_parent, ch_combo, ch_dcal, ch_h, seen, seen_off,
         seen_cap, seen_cnt, st, prod, nd, nlist, nd_slot, cslot, pos, br, sp, cand, looptab, trec, tsid,
@@ -202,14 +202,13 @@ int init_ws(Workspace &w)
 {
     if (w.ready) return 0;
     // Stream priorities: streams of another priority have HW queues of their own, so the kernels of one wave do not
-    // queue behind those of another.  Workspaces 1 and 3 serve the bulk lane (of consecutive batches): high and low;
-    // 0 and 2 the long-tail lane: normal.  (Measured with two waves: bulk high or low 13.4 ms, no priorities 17.3 ms,
-    // the long tail high 15.4 ms.)  RAFFT_PRIO=0 switches priorities off.
+    // queue behind those of another.  The long-tail lane keeps workspace 0 and the bulk lane takes 1-3 (scheduler_main):
+    // workspace 1 runs at high priority, 3 at low, 0 and 2 at normal.  (Measured with two waves: bulk high or low 13.4 ms,
+    // no priorities 17.3 ms, the long tail high 15.4 ms.)
     int plo = 0, phi = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&plo, &phi));
-    const int prio_mode = g.proc_cfg.prio;
     const int idx = (int)(&w - g.ws);
-    const int prio = prio_mode == 0 ? 0 : idx == 1 ? (prio_mode > 0 ? phi : plo) : idx == 3 ? (prio_mode > 0 ? plo : phi) : 0;
+    const int prio = idx == 1 ? phi : idx == 3 ? plo : 0;
     HIPCHK(hipStreamCreateWithPriority(&w.stream, hipStreamNonBlocking, prio));
     for (int c = 0; c < NCLS; c++) {
         HIPCHK(hipStreamCreateWithPriority(&w.cls_stream[c], hipStreamNonBlocking, prio));
@@ -218,9 +217,9 @@ int init_ws(Workspace &w)
     HIPCHK(hipStreamCreateWithFlags(&w.copy_stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&w.ev_fork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&w.ev_copy, hipEventDisableTiming));
-    for (int k = 0; k < 2; k++) HIPCHK(hipEventCreateWithFlags(&w.ev_hot[k], hipEventDisableTiming | hipEventBlockingSync));   // (the scheduler sleeps on it when it has spun long enough)
+    HIPCHK(hipEventCreateWithFlags(&w.ev_hot, hipEventDisableTiming | hipEventBlockingSync));   // (the scheduler sleeps on it when it has spun long enough)
     static_assert(offsetof(Counters, node) <= 1024, "hot counters must fit the pinned read-back slot");
-    HIPCHK(hipHostMalloc(&w.hot, 2048, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(&w.hot, 1024, hipHostMallocDefault));
     w.ready = true;
     return 0;
 }
@@ -258,7 +257,7 @@ int init_ctx(int device)
     return init_ws(g.ws[0]);
 }
 
-struct ClsCfg { int nt, Pmax, Lmax, nmax, brmax, Kmax, lds, grid; bool tab; int wpb; bool nofft; bool direct3 = false; };   // grid: teams (wavefronts of the packed one-wavefront class, workgroups otherwise)
+struct ClsCfg { int nt, Pmax, Lmax, nmax, brmax, Kmax, lds, grid; int wpb; bool nofft; bool direct3 = false; };   // grid: teams (wavefronts of the packed one-wavefront class, workgroups otherwise)
 
 // limits of the one-wavefront class: its LDS per wavefront (hence its occupancy) follows from them
 // (not below 256: the kernel addresses the staged bases through a pointer shifted back by up to 4095 positions, which must stay
@@ -274,26 +273,23 @@ static int cls1_br(const Config &cfg) { return std::min(CLS1_BR, (8 * cls1_P(cfg
 int class_cfg(const Config &cfg, int K, int maxL, ClsCfg out[NGEN + 1], bool nofft1 = false, bool nofft2 = false, bool direct3_ok = false)
 {
     // sequences longer than LDS_SEQ: classes 2 and 3 read the bases of a loop from HBM/L2 (no LDS copy), class 0 takes the
-    // regions whose FFT would not fit
+    // regions beyond 4096 positions, whose FFT would not fit (node_class)
     const bool longseq = maxL > LDS_SEQ;
     const int P[NGEN] = {CLS0_P, cls1_P(cfg), CLS2_P, MAX_P}, LM[NGEN] = {0, CLS01_L, longseq ? 0 : LDS_SEQ, longseq ? 0 : LDS_SEQ};
-    const int NT[NGEN] = {512, 64, cfg.nt2, 512}, BR[NGEN] = {BIG_BR + 1, nofft1 ? 128 : cls1_br(cfg), MAX_BR, MAX_BR};
-    // class 0 (tiny regions in their own kernel) is kept compiled for experiments but receives no work (see node_class)
-    const int tabm = cfg.tab;      // bit c: energy tables of class c in LDS
+    const int NT[NGEN] = {512, 64, 256, 512}, BR[NGEN] = {BIG_BR + 1, nofft1 ? 128 : cls1_br(cfg), MAX_BR, MAX_BR};
     // The one-wavefront class packs 12 wavefronts - what a CU holds of them anyway - into one workgroup that shares ONE LDS
     // copy of the energy tables and twiddles: the table look-ups of the dE phase stop being dependent L2 round trips
     // (measured: 5.9 -> 5.4 ms per benchmark batch in this kernel; with 4 or 8 per workgroup a CU holds fewer wavefronts
-    // and loses more than it gains).  Falls back to one wavefront per workgroup, tables in L2, when nb_mode makes the
-    // per-wavefront arrays too big for 12 to fit.  RAFFT_WPB=1/4/12 overrides.
-    int wpb1 = cfg.wpb ? cfg.wpb : (nofft1 ? 16 : 12);
-    if (!(wpb1 == 4 || wpb1 == 12 || (wpb1 == 16 && nofft1))) wpb1 = 1;
-    if (wpb1 > 1) {
+    // and loses more than it gains); sixteen without FFT buffers.  Falls back to twelve, then to one wavefront per workgroup,
+    // tables in L2, when nb_mode makes the per-wavefront arrays too big to fit.
+    int wpb1 = nofft1 ? 16 : 12;
+    {
         const int Kmax1 = std::max(1, std::min(K, cls1_P(cfg) - 1));
         if (wpb1 == 16 && expand_lds(cls1_P(cfg), CLS01_L, cls1_P(cfg) / 2, BR[1], Kmax1, true, wpb1, nofft1, 64).total > 160 * 1024) wpb1 = 12;
         if (expand_lds(cls1_P(cfg), CLS01_L, cls1_P(cfg) / 2, BR[1], Kmax1, true, wpb1, nofft1, 64).total > 160 * 1024) wpb1 = 1;
     }
     const int WPB[NGEN] = {1, wpb1, 1, 1};
-    const bool TAB[NGEN] = {false, (tabm & 2) != 0 || WPB[1] > 1, (tabm & 4) != 0, false};    // (LDS tables come with LDS twiddles: FFT sizes <= CLS2_P only)
+    const bool TAB[NGEN] = {false, WPB[1] > 1, false, false};    // energy tables in LDS: one copy shared by the wavefronts of a packed workgroup
     for (int c = 0; c < NGEN; c++) {
         // (class 0 is planned for 16 384 positions unless a sequence of the wave is longer: the 64 KiB of 32 768 positions leave
         //  its scratch room for nb_mode <= 106 only, where the plan for 16 384 takes ~400)
@@ -312,9 +308,8 @@ int class_cfg(const Config &cfg, int K, int maxL, ClsCfg out[NGEN + 1], bool nof
             return fail(RAFFT_ERR_PARAM, "internal: expand LDS plan does not fit its size class");
         if (c >= 1 && LM[c] > 0 && l.off_S < LDS_SEQ)      // (expand_kernel's Sl: the staged bases are addressed by sequence position)
             return fail(RAFFT_ERR_PARAM, "internal: the LDS copy of the bases sits too low for its shifted pointer");
-        int per_cu = std::max(1, std::min(32 / (NT[c] / 64), WPB[c] * ((160 * 1024) / l.total)));      // teams per CU
-        if (c == 1 && cfg.c1_per_cu > 0) per_cu = std::max(1, std::min(per_cu, cfg.c1_per_cu));
-        out[c] = {NT[c], P[c], LM[c], nmax, BR[c], Kmax, l.total, g.n_cu * per_cu, TAB[c], WPB[c], nf};
+        const int per_cu = std::max(1, std::min(32 / (NT[c] / 64), WPB[c] * ((160 * 1024) / l.total)));      // teams per CU
+        out[c] = {NT[c], P[c], LM[c], nmax, BR[c], Kmax, l.total, g.n_cu * per_cu, WPB[c], nf};
         // a size class that no region of this batch can reach need not fit (class 3 needs n > 1024, class 0 n > 4096)
         const bool reachable = c == 0 ? longseq : (c < 3 || maxL > CLS2_P / 2);
         if (l.total > 160 * 1024 && reachable)
@@ -340,7 +335,7 @@ int class_cfg(const Config &cfg, int K, int maxL, ClsCfg out[NGEN + 1], bool nof
         if (fits && l.total <= 80 * 1024) {
             const int per_cu = std::max(1, std::min(3, (160 * 1024) / l.total));
             out[NGEN] = out[3];          // the FFT plan stays for the steps with few such regions (launch_expand_cls)
-            out[3] = {256, Pd, 0, nmax, MAX_BR, Kmax, l.total, g.n_cu * per_cu, false, 1, false, true};
+            out[3] = {256, Pd, 0, nmax, MAX_BR, Kmax, l.total, g.n_cu * per_cu, 1, false, true};
         }
     }
     return 0;
@@ -360,40 +355,33 @@ int launch_expand(const Dev &d, int cls, const ClsCfg &cf, unsigned n_teams, hip
     return 0;
 }
 
-int launch_expand_cls(const Config &cfg, const Dev &d, int cls, const ClsCfg cf[NGEN + 1], unsigned n_blocks, hipStream_t st, bool dry = false)
+int launch_expand_cls(const Config &cfg, const Dev &d, int cls, const ClsCfg cf[NGEN + 1], unsigned n_blocks, hipStream_t st)
 {
+    // the production builds: no diagnostics of any kind asked for (RAFFT_PROD=0: the general builds)
+    const bool prod_ok = cfg.prod != 0;
     if (cls >= NGEN) {        // small regions: teams of 16 / 32 lanes, four wavefronts per workgroup (n_blocks = workgroups)
-        const int arg = cls | (cfg.small_diag << 8);
-        const bool prod_ok = cfg.prod != 0;
-        const bool prod = prod_ok && arg == cls && d.prof_e == nullptr && d.dbg.lag == nullptr;      // no diagnostics asked for: the production build
-        if (cls == 4 && prod) hipLaunchKernelGGL((expand_small_kernel<16, true>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<16>(), st, d, arg);
-        else if (cls == 4) hipLaunchKernelGGL((expand_small_kernel<16, false>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<16>(), st, d, arg);
-        else if (prod) hipLaunchKernelGGL((expand_small_kernel<32, true>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<32>(), st, d, arg);
-        else hipLaunchKernelGGL((expand_small_kernel<32, false>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<32>(), st, d, arg);
+        const bool prod = prod_ok && d.prof_e == nullptr && d.dbg.lag == nullptr;
+        if (cls == 4 && prod) hipLaunchKernelGGL((expand_small_kernel<16, true>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<16>(), st, d, cls);
+        else if (cls == 4) hipLaunchKernelGGL((expand_small_kernel<16, false>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<16>(), st, d, cls);
+        else if (prod) hipLaunchKernelGGL((expand_small_kernel<32, true>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<32>(), st, d, cls);
+        else hipLaunchKernelGGL((expand_small_kernel<32, false>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<32>(), st, d, cls);
         HIPCHK(hipGetLastError());
         return 0;
     }
     const bool longseq = cf[2].Lmax == 0;          // (class_cfg: no LDS copy of the bases)
-    const int nf = cls < NGEN && cf[cls].nofft ? 0x2000 : 0;
-    // the production build of the classes without FFT buffers: no diagnostics of any kind asked for (RAFFT_PROD=0: the general build)
-    const bool prod_ok = cfg.prod != 0;
-    const bool nodiag = prod_ok && !dry && d.prof_e == nullptr && d.rep == 0 && d.dbg.lag == nullptr && !d.force_fft && d.gc >= 0.0 && d.au >= 0.0 && d.gu >= 0.0;
-    const bool prod = nodiag && nf;
+    const int nf = cf[cls].nofft ? 0x2000 : 0;
+    const bool nodiag = prod_ok && d.prof_e == nullptr && d.dbg.lag == nullptr && !d.force_fft && d.gc >= 0.0 && d.au >= 0.0 && d.gu >= 0.0;
+    const bool prod = nodiag && nf;                // (the classes without FFT buffers)
     if (cls == 0) return nodiag ? launch_expand<512, false, 1, 2, 2>(d, 0, cf[0], n_blocks, st) : launch_expand<512, false, 1, 2>(d, 0, cf[0], n_blocks, st);
-    if (longseq && cls == 2 && cf[2].nt == 256) return prod ? launch_expand<256, false, 1, 1, 1>(d, 2 | nf, cf[2], n_blocks, st) : launch_expand<256, false, 1, 1>(d, 2 | nf, cf[2], n_blocks, st);
-    if (longseq && cls >= 2) return nodiag && !nf ? launch_expand<512, false, 1, 1, 2>(d, cls, cf[cls], n_blocks, st) : launch_expand<512, false, 1, 1>(d, cls | nf, cf[cls], n_blocks, st);
-    if (cls == 1) {
-        if (cf[1].wpb == 4) return launch_expand<64, true, 4>(d, 1, cf[1], n_blocks, st);
+    if (longseq && cls == 2) return prod ? launch_expand<256, false, 1, 1, 1>(d, 2 | nf, cf[2], n_blocks, st) : launch_expand<256, false, 1, 1>(d, 2 | nf, cf[2], n_blocks, st);
+    if (longseq && cls == 3) return nodiag && !nf ? launch_expand<512, false, 1, 1, 2>(d, 3, cf[3], n_blocks, st) : launch_expand<512, false, 1, 1>(d, 3 | nf, cf[3], n_blocks, st);
+    if (cls == 1) {                                // (class_cfg: the energy tables are in LDS exactly when wavefronts are packed)
         if (cf[1].wpb == 16 && prod) return launch_expand<64, true, 16, 0, 1>(d, 1 | nf, cf[1], n_blocks, st);
-        if (cf[1].wpb == 16) return launch_expand<64, true, 16>(d, 1 | (cf[1].nofft ? 0x2000 : 0), cf[1], n_blocks, st);
-        if (cf[1].wpb == 12) return launch_expand<64, true, 12>(d, (dry ? (0x101 | (std::max(0, cfg.twice - 2) << 9)) : 1) | (cf[1].nofft ? 0x2000 : 0), cf[1], n_blocks, st);
-        return cf[1].tab ? launch_expand<64, true>(d, 1, cf[1], n_blocks, st) : launch_expand<64, false>(d, 1, cf[1], n_blocks, st);
+        if (cf[1].wpb == 16) return launch_expand<64, true, 16>(d, 1 | nf, cf[1], n_blocks, st);
+        if (cf[1].wpb == 12) return launch_expand<64, true, 12>(d, 1 | nf, cf[1], n_blocks, st);
+        return launch_expand<64, false>(d, 1, cf[1], n_blocks, st);
     }
-    if (cls == 2) {
-        if (cf[2].nt == 512) return cf[2].tab ? launch_expand<512, true>(d, 2 | nf, cf[2], n_blocks, st) : launch_expand<512, false>(d, 2 | nf, cf[2], n_blocks, st);
-        if (prod && !cf[2].tab) return launch_expand<256, false, 1, 0, 1>(d, 2 | nf, cf[2], n_blocks, st);
-        return cf[2].tab ? launch_expand<256, true>(d, 2 | nf, cf[2], n_blocks, st) : launch_expand<256, false>(d, 2 | nf, cf[2], n_blocks, st);
-    }
+    if (cls == 2) return prod ? launch_expand<256, false, 1, 0, 1>(d, 2 | nf, cf[2], n_blocks, st) : launch_expand<256, false>(d, 2 | nf, cf[2], n_blocks, st);
     if (cf[3].direct3) {
         // Two kernels share the class's work list; the length of the list decides ON THE DEVICE which of them works (the other one's
         // workgroups leave at once): up to Dev::c3_switch regions - every region has a CU to itself either way - the FFT plan, whose
@@ -404,8 +392,7 @@ int launch_expand_cls(const Config &cfg, const Dev &d, int cls, const ClsCfg cf[
         const unsigned nb_fft = std::min<unsigned>(n_blocks, (unsigned)cf[NGEN].grid);
         return nodiag ? launch_expand<512, false, 1, 0, 2>(d, 3 | 0x4000, cf[NGEN], nb_fft, st) : launch_expand<512, false>(d, 3 | 0x4000, cf[NGEN], nb_fft, st);
     }
-    if (nodiag && !cf[3].tab) return launch_expand<512, false, 1, 0, 2>(d, 3, cf[3], n_blocks, st);
-    return cf[3].tab ? launch_expand<512, true>(d, 3, cf[3], n_blocks, st) : launch_expand<512, false>(d, 3, cf[3], n_blocks, st);
+    return nodiag ? launch_expand<512, false, 1, 0, 2>(d, 3, cf[3], n_blocks, st) : launch_expand<512, false>(d, 3, cf[3], n_blocks, st);
 }
 
 // timing events: handed out from a free list and returned when their batch has been finalised, so the spans of a
@@ -646,7 +633,6 @@ struct Wave {
     size_t S = 0, sumL = 0, B = 0, bs_lds[2] = {0, 0}, mat_lds = RAFFT_MAX_LEN, out_row_lds = RAFFT_MAX_LEN;
     double reserve = 1.0;         // buffers are allocated for a wave this many times bigger (merged batches to come)
     bool longseq = false;         // a sequence longer than LDS_SEQ: its loops' bases are read from HBM, regions beyond 4096 positions exist
-    unsigned dedupe_per_cu = 1024 / DEDUPE_NT;
     std::vector<int> off, len;
     std::vector<uint32_t> seen_cap0;      // initial slots of every sequence's `seen` set (seen_slots0)
     size_t seen0_total = 0;
@@ -660,11 +646,6 @@ struct Wave {
     int depth = 0;                // regrowths of this job so far
     bool big_prod = false, want_big_prod = false;   // long productive-region lists (1024 per structure) for this run / asked for by it
     bool finished = false;
-    // (round 5) read-backs issued / looked at.  In step-ahead mode the host queues the materialize step and the next folding step
-    // BEFORE it has seen the counters of the running one (grids and class choices from the step before, counts from the device's own
-    // counters): the 24 lock-step steps of a lone batch no longer wait 150 us each for the host's round trip
-    int rb_issued = 0, rb_seen = 0;
-    bool step_ahead = false;
     long long last_rows_bytes = 0;
     std::vector<OutRec> early_recs, late_recs;
     PinBuf stage{};               // pinned staging of the wave's inputs (setup)
@@ -688,13 +669,13 @@ struct Wave {
     }
     hipEvent_t next_event() { return ::next_event(bt.events); }
     // a wave whose steps still create many structures keeps the whole GPU busy; afterwards it is latency-bound
-    bool heavy(unsigned below) const { return below != 0x7fffffffu && S >= 256 && !finished && (steps < 3 || last_mat >= below); }
+    bool heavy(unsigned below) const { return S >= 256 && !finished && (steps < 3 || last_mat >= below); }
     int setup();
     int issue_step();
     // 1: the step's read-back has landed, 0: not yet, -1: the device reported an error (sticky: the wave is failed, not polled forever)
     int ready()
     {
-        const hipError_t e = hipEventQuery(g.ev_hot[rb_seen & 1]);
+        const hipError_t e = hipEventQuery(g.ev_hot);
         if (e == hipSuccess) return 1;
         if (e == hipErrorNotReady) return 0;
         fail(RAFFT_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
@@ -702,7 +683,7 @@ struct Wave {
     }
     std::chrono::steady_clock::time_point t_issued;      // when the running step was issued (the scheduler blocks on the oldest)
     int after_beam();
-    int issue_materialize(unsigned n_mat_known, unsigned n_mat_guess);
+    int issue_materialize(unsigned n_mat);
     // (every error exit of the two leaves `finished` and `result` set: the scheduler reads `result` of a finished wave, and a failure
     //  while the rows are gathered - a device error, a pinned allocation - must not be released as a batch-level success)
     int finish() { const int rc = finish_body(); if (rc) { finished = true; draining = false; if (!result) result = rc; } return rc; }
@@ -745,9 +726,8 @@ int Wave::setup()
     for (size_t i = 0; i < S; i++) maxL = std::max(maxL, len[i]);
     const int direct_n_ = cfg.direct_n;
     const bool force_fft_ = cfg.force_fft != 0;
-    const bool nofft1 = !seam && !force_fft_ && direct_n_ >= cls1_P(cfg) / 2 && p.gc_wei >= 0.0 && p.au_wei >= 0.0 && p.gu_wei >= 0.0 &&
-                        !cfg.c1_fft;
-    const bool nofft2 = nofft1 && direct_n_ >= CLS2_P / 2 && !cfg.c2_fft;
+    const bool nofft1 = !seam && !force_fft_ && direct_n_ >= cls1_P(cfg) / 2 && p.gc_wei >= 0.0 && p.au_wei >= 0.0 && p.gu_wei >= 0.0;
+    const bool nofft2 = nofft1 && direct_n_ >= CLS2_P / 2;
     if (int rc = class_cfg(cfg, p.nb_mode, maxL, cf, nofft1, nofft2, nofft1)) return rc;      // (direct class 3: the same conditions as the other FFT-free plans)
     if (cfg.trace)
         for (int c = 0; c < NGEN; c++)
@@ -869,7 +849,6 @@ int Wave::setup()
     d.sp_shard_cap = c.sp / NSHARD;
     d.br_shard_cap = c.br / NSHARD; d.cand_shard_cap = c.cand / NSHARD;
     if (seam) d.dbg = seam->dbg;
-    d.rep = cfg.rep;
     static unsigned long long *prof_buf = nullptr;
     if (cfg.trace >= 3) {
         if (!prof_buf) HIPCHK(hipMalloc((void **)&prof_buf, 128));
@@ -937,18 +916,7 @@ int Wave::setup()
     }
     mat_lds = 20 * (size_t)d.max_prod;
     out_row_lds = ((size_t)maxL + 15) & ~(size_t)15;      // output_kernel builds a dot-bracket row in LDS: the longest sequence of the wave
-    if (cfg.dedupe_per_cu > 0) dedupe_per_cu = (unsigned)cfg.dedupe_per_cu;
     n_active = (unsigned)S;
-    {
-        // step-ahead (RAFFT_STEP_AHEAD=0: lock-step as in rounds 1-4): needs the kernel that takes the device's own count
-        // (materialize_team_kernel: short productive-region lists, no phase stamps), and no per-step diagnostics that read counters back
-        // MEASURED AND LEFT OFF (round 5, tools/ab_stepahead.sh, tools/single_probe.py): the host's round trip is not what a folding step
-        // waits for.  One synchronous call on the benchmark batch takes 9.8-10.9 ms either way (it is bound by its kernels), the
-        // pipelined rate falls 3 % (an empty step per wave, guessed grids), and a lone 76-nt sequence takes 1.07 ms instead of 0.91
-        // (its 6 steps cost ~150 us each on the DEVICE - eight dependent kernels at ~20 us of dispatch latency - and step-ahead
-        // adds a seventh).  RAFFT_STEP_AHEAD=1 switches it on.
-        step_ahead = cfg.step_ahead != 0 && cfg.mat4 != 0 && !seam && cfg.trace < 2 && d.prof_e == nullptr && d.max_prod <= MAT4_PROD && cfg.test_ovf_at < 0;
-    }
     ms_setup = since(tw0);
     if (cfg.trace) fprintf(stderr, "[rafft] setup: encode %.3f ms, plan+buffers %.3f ms, copies+init %.3f ms\n", ms_enc, ms_plan - ms_enc, ms_setup - ms_plan);
     tw1 = std::chrono::steady_clock::now();
@@ -968,16 +936,14 @@ int Wave::issue_step()
     HIPCHK(hipEventRecord(g.ev_fork, st));
     Span wall{next_event(), next_event(), 4};
     SPAN_REC(wall.a, st, 4);
-    static const int order_big_first[NCLS] = {3, 0, 2, 1, 5, 4}, order_small_first[NCLS] = {5, 4, 3, 0, 2, 1};    // big-LDS classes first
-    const int *order = cfg.small_first ? order_small_first : order_big_first;
+    static const int order[NCLS] = {3, 0, 2, 1, 5, 4};    // big-LDS classes first
     for (int oi = 0; oi < NCLS; oi++) {
         const int cls = order[oi];
         if (cls == 0 && !longseq) continue;                      // regions beyond 4096 positions: only sequences longer than that have them
         if (cls == 3 && merge_target == 2) continue;             // no sequence long enough for a region of that class
         if (merged_now == 3 && cls != 3 && cls != 0) continue;   // the dedupe of the last step sent everything to one class
         if (merged_now == 2 && cls == 1) continue;               // ... or the one-wavefront class to the 256-thread one
-        const bool small_step0 = cfg.small_step0 != 0;      // diagnostic: empty launches (their fixed cost)
-        if (cls >= NGEN && (merged_now != 0 || (steps == 0 && !small_step0) || (cls == 4 ? d.sm_n4 : d.sm_n5) == 0 || (cls == 5 && d.sm_n5 == d.sm_n4))) continue;   // small-region classes: off, or nothing was sent there
+        if (cls >= NGEN && (merged_now != 0 || steps == 0 || (cls == 4 ? d.sm_n4 : d.sm_n5) == 0 || (cls == 5 && d.sm_n5 == d.sm_n4))) continue;   // small-region classes: off, or nothing was sent there
         const bool inline_ = serial || (merged_now == 3 && !longseq);   // a single kernel: no fork/join through another stream
         hipStream_t cs = inline_ ? st : g.cls_stream[cls];
         if (!inline_) HIPCHK(hipStreamWaitEvent(cs, g.ev_fork, 0));
@@ -986,19 +952,11 @@ int Wave::issue_step()
         // persistent workgroups loop over the work list, so any grid is correct: when few structures were
         // materialized (the tail of a batch) a small grid avoids dispatching thousands of empty workgroups
         unsigned grid = cls >= NGEN ? (unsigned)::g.n_cu * small_wg_per_cu : (unsigned)cf[cls].grid;
-        const unsigned c1_wgs = (unsigned)std::max(0, cfg.c1_wgs);     // A/B: fewer workgroups of the one-wavefront class
-        if (cls == 1 && c1_wgs && cf[1].wpb > 1) grid = std::min(grid, c1_wgs * (unsigned)cf[1].wpb);
-        if (steps > 0 && !(step_ahead && steps < 3)) {       // (step-ahead: `last_mat` is the step before's - doubled; the first steps grow faster)
-            const unsigned long long bound = (unsigned long long)last_mat * (step_ahead ? 2ULL : 1ULL) * (cls == 1 ? 8ULL : 4ULL) + 32ULL;
+        if (steps > 0) {
+            const unsigned long long bound = (unsigned long long)last_mat * (cls == 1 ? 8ULL : 4ULL) + 32ULL;
             if (bound < grid) grid = (unsigned)bound;
         }
         if (int rc = launch_expand_cls(cfg, d, cls, cf, grid, cs)) return rc;
-        const int twice = cfg.twice;   // diagnostic: the same work again, caches warm
-        if (twice && cls == 1) {
-            HIPCHK(hipMemsetAsync((char *)g.counters.p + offsetof(Counters, wcur) + sizeof(ShardCtr) * NSHARD * cls, 0, sizeof(ShardCtr) * NSHARD, cs));
-            HIPCHK(hipMemsetAsync((char *)g.counters.p + offsetof(Counters, wdone) + 8 * cls, 0, 8, cs));
-            if (int rc = launch_expand_cls(cfg, d, cls, cf, grid, cs, twice >= 2)) return rc;
-        }
         if (cls == 1) bt.stats.n_expand_launches++;       // launches of the dominant kernel (ms_expand is their sum)
         SPAN_REC(sp.b, cs, sp.kind);
         spans.push_back(sp);
@@ -1027,32 +985,25 @@ int Wave::issue_step()
         spans.push_back(sp);
     }
     steps++;
-    HIPCHK(hipMemcpyAsync((char *)g.hot + 1024 * (rb_issued & 1), g.counters.p, hot_len, hipMemcpyDeviceToHost, st));   // pinned: truly asynchronous
-    HIPCHK(hipEventRecord(g.ev_hot[rb_issued & 1], st));
-    rb_issued++;
+    HIPCHK(hipMemcpyAsync(g.hot, g.counters.p, hot_len, hipMemcpyDeviceToHost, st));   // pinned: truly asynchronous
+    HIPCHK(hipEventRecord(g.ev_hot, st));
     t_issued = std::chrono::steady_clock::now();
     return 0;
 }
 
-// materialize the new beam members of the step whose beam step is queued or done, and find the loops among their regions that
-// are known already.  `n_mat_known`: the step's count when its counters have been read back, 0 when they have not (step-ahead mode:
-// the kernel takes the device's own counter and `n_mat_guess` only sizes its grid and chooses the size classes of the next step)
-int Wave::issue_materialize(unsigned n_mat_known, unsigned n_mat_guess)
+// materialize the `nm` new beam members of the step whose counters have just been read back, and find the loops among their
+// regions that are known already
+int Wave::issue_materialize(unsigned nm)
 {
     hipStream_t st = g.stream;
-    const unsigned nm = n_mat_known ? n_mat_known : n_mat_guess;
     Span sp{next_event(), next_event(), 2};
     SPAN_REC(sp.a, st, sp.kind);
     // (four structures per wavefront, teams of 16 lanes, when the short productive-region lists are in use -
-    //  materialize_team_kernel; RAFFT_MAT4=0: one structure per wavefront)
-    const bool mat4_on = cfg.mat4 != 0;
-    if (mat4_on && d.prof_e == nullptr && d.max_prod <= MAT4_PROD) {
-        const unsigned grid = n_mat_known ? (n_mat_known + MAT4_TEAMS - 1) / MAT4_TEAMS
-                                          : std::min<unsigned>((unsigned)((c.mat + MAT4_TEAMS - 1) / MAT4_TEAMS), std::max<unsigned>(64u, nm / 2u + 64u));
-        hipLaunchKernelGGL(materialize_team_kernel, dim3(grid), dim3(64), 0, st, d, n_mat_known ? (int)n_mat_known : -1);
-    }
-    else if (d.prof_e == nullptr) hipLaunchKernelGGL(materialize_kernel<true>, dim3(n_mat_known), dim3(MAT_NT), mat_lds, st, d);
-    else hipLaunchKernelGGL(materialize_kernel<false>, dim3(n_mat_known), dim3(MAT_NT), mat_lds, st, d);
+    //  materialize_team_kernel; otherwise one structure per wavefront)
+    if (d.prof_e == nullptr && d.max_prod <= MAT4_PROD)
+        hipLaunchKernelGGL(materialize_team_kernel, dim3((nm + MAT4_TEAMS - 1) / MAT4_TEAMS), dim3(64), 0, st, d, (int)nm);
+    else if (d.prof_e == nullptr) hipLaunchKernelGGL(materialize_kernel<true>, dim3(nm), dim3(MAT_NT), mat_lds, st, d);
+    else hipLaunchKernelGGL(materialize_kernel<false>, dim3(nm), dim3(MAT_NT), mat_lds, st, d);
     HIPCHK(hipGetLastError());
     // tail of the batch: so few new structures that their regions fit one wave of workgroups of the widest class
     // (measured on the benchmark batch: 18.8 -> 17.3 ms; thresholds in new structures per step, per CU)
@@ -1064,7 +1015,7 @@ int Wave::issue_materialize(unsigned n_mat_known, unsigned n_mat_guess)
     merged_now = d.merge_cls;
     // (a thread per region created in this step - two or three per new structure: light steps launch a handful of workgroups instead
     //  of two per CU, which used to queue behind the expand kernels of the other waves only to find nothing)
-    const unsigned dd_grid = std::min<unsigned>((unsigned)::g.n_cu * dedupe_per_cu, (unsigned)std::min<unsigned long long>(0x7fffffffULL, (unsigned long long)nm * 4ULL / DEDUPE_NT + 2ULL));
+    const unsigned dd_grid = std::min<unsigned>((unsigned)::g.n_cu * (1024u / DEDUPE_NT), (unsigned)std::min<unsigned long long>(0x7fffffffULL, (unsigned long long)nm * 4ULL / DEDUPE_NT + 2ULL));
     hipLaunchKernelGGL(dedupe_kernel, dim3(dd_grid), dim3(DEDUPE_NT), 0, st, d);
     HIPCHK(hipGetLastError());
     SPAN_REC(sp.b, st, sp.kind);
@@ -1080,8 +1031,7 @@ int Wave::after_beam()
     hipStream_t st = g.stream;
     if (draining) return finish_done();            // the last rows have landed
     const size_t hot_len = offsetof(Counters, node);
-    memcpy(&hc, (const char *)g.hot + 1024 * (rb_seen & 1), hot_len);
-    rb_seen++;
+    memcpy(&hc, g.hot, hot_len);
     if (hc.overflow) { ovf = hc.overflow; return finish(); }
     // test hook: pretend an arena overflowed at this step of the first attempt (regrowth late in a wave)
     if (cfg.test_ovf_at >= 0 && depth == 0 && steps == cfg.test_ovf_at) { ovf = OVF_STRUCT; return finish(); }
@@ -1090,11 +1040,9 @@ int Wave::after_beam()
     last_mat = hc.n_mat;
     // most sequences of the wave have finished: their rows leave beside the folding steps of the others - once this step's kernels
     // are queued (below): the host's share of it, a millisecond or two for a wave of 16 k sequences, is off the wave's own path
-    const bool harvest_now = !p.traj && !seam && !harvested && S >= 256 && (size_t)hc.trec_n * 10 >= S * 7 && !cfg.no_harvest;
+    const bool harvest_now = !p.traj && !seam && !harvested && S >= 256 && (size_t)hc.trec_n * 10 >= S * 7;
     const size_t harvest_n = (size_t)hc.trec_n;
-    // step-ahead mode: this step's materialize and the next folding step are queued already (when the step before was looked at);
-    // what is issued now is the materialize of the step in flight and the folding step after it, sized by this step's counters
-    if (int rc = issue_materialize(step_ahead ? 0u : hc.n_mat, hc.n_mat)) return rc;
+    if (int rc = issue_materialize(hc.n_mat)) return rc;
     if (cfg.trace >= 2) {
         Counters h2;
         HIPCHK(hipMemcpyAsync(&h2, g.counters.p, hot_len, hipMemcpyDeviceToHost, st));
@@ -1197,9 +1145,7 @@ int Wave::finish_body()
     finished = true;
     const double ms_loop = ms_loop_ = since(tw1);
     auto tw2 = tw2_ = std::chrono::steady_clock::now();
-    bt.stats.n_steps = std::max<int64_t>(bt.stats.n_steps, step_ahead ? rb_seen : steps);
-    // (step-ahead: the step queued behind the last read-back has nothing to do - every sequence is done, no work list holds anything -
-    //  and touches none of the counters and records read below)
+    bt.stats.n_steps = std::max<int64_t>(bt.stats.n_steps, steps);
     if (ovf && cfg.trace) fprintf(stderr, "[rafft] wave S=%zu est %.1f overflowed (bits %u) after %d steps, %.1f ms\n", S, est, ovf, steps, since(tw0));
     if (ovf) {
         HIPCHK(hipStreamSynchronize(st));
@@ -1265,10 +1211,7 @@ int Wave::finish_body()
         HIPCHK(hipEventRecord(g.ev_copy, g.copy_stream));
         HIPCHK(hipStreamWaitEvent(st, g.ev_copy, 0));
     }
-    // (a step queued ahead of the last read-back has nothing to do - every sequence is done - and its read-back is never looked at)
-    rb_seen = rb_issued;
-    HIPCHK(hipEventRecord(g.ev_hot[rb_issued & 1], st));
-    rb_issued++;
+    HIPCHK(hipEventRecord(g.ev_hot, st));
     finished = false; draining = true;
     (void)ms_loop;
     return 0;
@@ -1319,7 +1262,6 @@ int Wave::finish_done_body()
             fprintf(stderr, "[rafft]   class %d: inside fetch+header: claiming items %llu Mcycles, work-list entry %llu Mcycles (of %llu)\n", c, pe[c * PROF_E + 40] / 1000000, pe[c * PROF_E + 41] / 1000000, pe[c * PROF_E] / 1000000);
             fprintf(stderr, "[rafft]   class %d: inside dE: branch prefix sums %llu, candidates %llu Mcycles; inside emit: compaction %llu, candidate slots %llu, keys+rank %llu, hashes+cuts+stores %llu Mcycles\n", c,
                     pe[c * PROF_E + 42] / 1000000, pe[c * PROF_E + 43] / 1000000, pe[c * PROF_E + 44] / 1000000, pe[c * PROF_E + 45] / 1000000, pe[c * PROF_E + 46] / 1000000, pe[c * PROF_E + 47] / 1000000);
-            if (pe[c * PROF_E + 32]) fprintf(stderr, "[rafft]   class %d: draining the previous region's stores (RAFFT_REP=256): %llu Mcycles\n", c, pe[c * PROF_E + 32] / 1000000);
             if (c == 1) {
                 fprintf(stderr, "[rafft]   class 1, regions without any stem / without a kept candidate (share of the size class):");
                 for (int k = 0; k < 6; k++) {
@@ -1427,15 +1369,13 @@ void free_out(HostOut *o);
 //   * every queued job is admitted as soon as a workspace is free: the bulk of the next batch starts while the running
 //     one is still folding, so the tail of a batch - and its long-tail wave - run beside the next batch's busy steps
 //     (measured on the benchmark batch, three batches in flight: 11.9 ms per batch against 13.1 for synchronous
-//     calls; holding the next bulk wave back until the running one has turned light - RAFFT_ADMIT_BELOW=<structures
-//     per step> - was 2-4 % slower);
+//     calls; holding the next bulk wave back until the running one has turned light was 2-4 % slower);
 //   * a job that does not fit the HBM still free is split (or waits for running waves to release theirs).
 struct Slot { std::unique_ptr<Wave> wave; Job job; int lane = 0; };
 
 static unsigned admit_below()
 {
-    const unsigned v = (unsigned)std::max(0, g.sched_cfg.admit_below);
-    return v ? v : 128u * (unsigned)g.n_cu;     // = the step size below which the one-wavefront expand class is merged away
+    return 128u * (unsigned)g.n_cu;     // = the step size below which the one-wavefront expand class is merged away
 }
 // sequences one merged wave may hold (a wave of the whole benchmark set four times over folds 25 % faster per sequence
 // than the set alone: fewer, fuller launches; five times over - with ten batches in flight, so that two such waves run side by
@@ -1688,8 +1628,7 @@ static void scheduler_main()
         for (int i = 0; i < MAX_PIPES; i++) if (slot[i].wave) { n_running++; heavy_running = heavy_running || slot[i].wave->heavy(admit_below()); }
         // The long-tail lane has a wave slot of its own: a long-tail wave (a handful of sequences, two dozen latency-bound steps)
         // never keeps a second bulk wave from starting (288 -> 294 k sequences/s with eight batches in flight, three interleaved
-        // pairs of runs; RAFFT_TAIL_SLOT=0: the lanes share the `max_waves` slots as in round 2)
-        const bool tail_slot = scfg.tail_slot != 0;
+        // pairs of runs, against the lanes sharing the `max_waves` slots as in round 2)
         int n_lane[2] = {0, 0};
         for (int i = 0; i < MAX_PIPES; i++) if (slot[i].wave) n_lane[slot[i].lane]++;
         // A caller that streams batches (two or more in flight) queues them microseconds apart: a bulk wave admitted the moment the
@@ -1712,7 +1651,7 @@ static void scheduler_main()
         }
         for (int ln = 0; ln < 2; ln++) {
             if (linger) break;          // (both lanes: the long-tail jobs of a burst are merged into one wave too - the lane runs one at a time)
-            while (!queue[ln].empty() && (tail_slot ? (ln == 0 ? n_lane[0] < 1 : n_lane[1] < max_waves && n_running < MAX_PIPES) : n_running < max_waves)) {
+            while (!queue[ln].empty() && (ln == 0 ? n_lane[0] < 1 : n_lane[1] < max_waves && n_running < MAX_PIPES)) {
                 Job &front = queue[ln].front();
                 if (!strip_failed(front)) {                       // every member already failed elsewhere: nothing to fold
                     Job j = std::move(front); queue[ln].pop_front(); release(j, 0, ""); progressed = true; continue;
@@ -1726,7 +1665,7 @@ static void scheduler_main()
                 // and one hipMalloc in a few hundred takes SECONDS - measured 3.4 s, a run of 13 k sequences/s instead of 500 k.)
                 int w = -1;
                 auto better = [&](int k) { return w < 0 || (job_heavy ? g.ws[k].bytes() > g.ws[w].bytes() : g.ws[k].bytes() < g.ws[w].bytes()); };
-                for (int k = 0; k < MAX_PIPES; k++) if (!slot[k].wave && (tail_slot ? (k == 0) == (ln == 0) : true) && better(k)) w = k;
+                for (int k = 0; k < MAX_PIPES; k++) if (!slot[k].wave && (k == 0) == (ln == 0) && better(k)) w = k;
                 if (w < 0) for (int k = 0; k < MAX_PIPES; k++) if (!slot[k].wave && better(k)) w = k;
                 if (w < 0) break;
                 // continuous batching: queued jobs with the same parameters join this one (first regrowths stay alone)
@@ -1796,7 +1735,7 @@ static void scheduler_main()
                     // seconds (bench.py: a run in six allocated its third workspace inside the timed region, 300 k instead of 500 k).
                     // Only workspaces that are not bulk-sized yet (less than a quarter of this one): one that merely lags behind a
                     // workspace that grew for some wave is left alone - following it would put 2 x 47 GB of hipMalloc into the stream.
-                    if (!rc && job_heavy && tail_slot && g.n_inflight >= 2) {
+                    if (!rc && job_heavy && g.n_inflight >= 2) {
                         size_t held = 0, add = 0;
                         for (int k = 0; k < MAX_PIPES; k++) held += g.ws[k].bytes();
                         for (int k = 1; k <= max_waves && k < MAX_PIPES; k++) if (k != w && !slot[k].wave && g.ws[k].bytes() < g.ws[w].bytes() / 4) add += g.ws[w].bytes() - g.ws[k].bytes();
@@ -1808,12 +1747,6 @@ static void scheduler_main()
                                 if (k != w && !slot[k].wave && g.ws[k].bytes() < g.ws[w].bytes() / 4) { rc = init_ws(g.ws[k]); if (!rc) rc = g.ws[k].match(g.ws[w]); }
                     }
                     if (!rc) rc = sl.wave->issue_step();
-                    // step-ahead: the materialize of the first step and the second step are queued at once (counts from the device,
-                    // no size class merged away: the first steps are the big ones)
-                    if (!rc && sl.wave->step_ahead) {
-                        rc = sl.wave->issue_materialize(0u, 0x7fffffffu);
-                        if (!rc) rc = sl.wave->issue_step();
-                    }
                 }
                 progressed = true;
                 if (rc) {

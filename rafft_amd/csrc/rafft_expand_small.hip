@@ -44,12 +44,11 @@ __device__ __forceinline__ uint32_t sm_shift(uint32_t x, int s)          // x >>
     return s >= 0 ? (s < 32 ? x >> s : 0u) : (s > -32 ? x << -s : 0u);
 }
 
-// PROD: the production build (no seam, no phase stamps, no diagnostic exits compiled in): fewer live registers, fewer spills
+// PROD: the production build (no seam, no phase stamps compiled in): fewer live registers, fewer spills
 template <int TL, bool PROD = false>
 __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_small_kernel(Dev d, int cls_arg)
 {
-    const int cls = cls_arg & 0xFF, diag = PROD ? 0 : cls_arg >> 8;       // diag: diagnostic early exits (RAFFT_SMALL_DIAG)
-    if (diag == 1) return;
+    const int cls = cls_arg & 0xFF;
     using LY = SmLds<TL>;
     constexpr int TPW = 64 / TL;                  // teams per wavefront
     extern __shared__ __align__(16) unsigned char lds_all[];
@@ -59,7 +58,6 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
         for (int i = threadIdx.x; i < (int)(sizeof(SmallT) / 4); i += 64 * SM_WG_WAVES) dst[i] = src[i];
         __syncthreads();                          // the only workgroup-wide barrier: from here on every wavefront is on its own
     }
-    if (diag == 2) return;
     const SmallT *T = (const SmallT *)lds_all;
     const BigT *B = &d.T->b;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -78,7 +76,6 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
 
     if (d.c->overflow) return;                    // (an arena overflowed earlier in this wave: see expand_kernel)
     const unsigned n_items = d.c->n_work[cls].v;
-    if (diag == 3) return;
     const unsigned gw = blockIdx.x * SM_WG_WAVES + wv, n_waves = gridDim.x * SM_WG_WAVES;
     if (gw == 0 && lane == 0) d.c->n_mat = 0;                // the beam step that follows counts its new structures here
     const int shard = gw & (NSHARD - 1);
@@ -93,7 +90,6 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
     const bool dbg = !PROD && d.dbg.lag != nullptr;                                    // kernel-level seam (one region, team 0)
     const double par_none = 0.0; (void)par_none;
 
-    if (diag == 4) return;
     const bool eprof = !PROD && d.prof_e != nullptr && lane == 0;      // diagnostic phase stamps (RAFFT_TRACE=3)
     unsigned long long eacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, et = eprof ? clock64() : 0, n_rounds = 0;
 #define SSTAMP(k) do { if (eprof) { const unsigned long long tn_ = clock64(); eacc[k] += tn_ - et; et = tn_; } } while (0)

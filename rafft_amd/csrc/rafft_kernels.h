@@ -177,7 +177,6 @@ struct Dev {
     unsigned long long *prof; int prof_seq;   // diagnostic stamps of beam_step_kernel (RAFFT_TRACE=3)
     unsigned long long *prof_e;               // RAFFT_TRACE=3: expand_kernel phase cycles, regions and cycles by region size, phase cycles by region size [NCLS][PROF_E]
     unsigned long long *prof_ws;              // RAFFT_TRACE=3: per sequence [cycles, chunks, max cycles of one step]
-    int rep;                     // profiling only (RAFFT_REP env): bit k doubles phase k of expand_kernel
 };
 
 // expand-kernel size classes: 1 small (FFT size P <= 512: one wavefront per region), 2 medium (P <= 2048: 256 threads),

@@ -289,10 +289,8 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
 {
     const int cls = cls_arg & 0xFF;
     const DebugOut dbg = PROD ? DebugOut{} : d.dbg;
-    const int rep = PROD ? 0 : d.rep, force_fft = PROD ? 0 : d.force_fft;
+    const int force_fft = PROD ? 0 : d.force_fft;
     unsigned long long *const prof_e = PROD ? nullptr : d.prof_e;
-    const bool dry = !PROD && (cls_arg & 0x100) != 0;      // diagnostic (RAFFT_TWICE=2): everything but the result stores
-    const int skip_lvl = PROD ? 0 : (cls_arg >> 9) & 15;      // diagnostic (RAFFT_TWICE=3..7): a region stops after window_slide (1), ranking (2), lag values (3), FFTs (4), LDS fill (5)
 
     static_assert(WPB == 1 || NT == 64, "only the one-wavefront class packs several wavefronts into a workgroup");
     static_assert(LONGSEQ == 0 || NT > 64, "long sequences never reach the one-wavefront class");
@@ -345,7 +343,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         wtab[tid] = (tp == 5 || tp == 6) ? d.au : (tp == 1 || tp == 2) ? d.gc : (tp == 3 || tp == 4) ? d.gu : 0.0;
     }
     // an arena overflowed in an earlier kernel of this wave: the host regrows and folds the wave again, whatever is queued behind
-    // that kernel (the host issues a step ahead of its read-backs) finds records that were never written - and does nothing
+    // that kernel (the rest of its step) finds records that were never written - and does nothing
     if (d.c->overflow) return;
     const unsigned n_items = d.c->n_work[cls].v;
     if (gteam == 0 && tid == 0) d.c->n_mat = 0;                // the beam step that follows counts its new structures here
@@ -371,11 +369,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
 
     for (;;) {
         ESYNC();                       // previous region's LDS use is over
-        if (prof_e != nullptr && (rep & 256)) {      // diagnostic: how long the previous region's stores take to drain
-            const unsigned long long t0_ = clock64();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (tid == 0) atomicAdd(&prof_e[cls * PROF_E + 32], (unsigned long long)(clock64() - t0_));
-        }
         unsigned long long ft0 = eprof ? clock64() : 0;
         if (fetch_left == 0) {
             unsigned fcount = 1;
@@ -418,12 +411,9 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         const int Pk = LONGSEQ == 2 ? 0 : P;       // the lag values occupy 8 P bytes of region A - unless they live in HBM
         const int size_bk = n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : n <= 64 ? 3 : n <= 128 ? 4 : 5;      // (diagnostic: regions and cycles by size)
         ESTAMP(0);   // fetch + header
-        if (skip_lvl >= 7) continue;
-        if (skip_lvl >= 6) { if (tid == 0 && n + ci + cj + nbr + L + par_dcal == -12345) d.c->overflow = 1; continue; }     // (header values consumed)
         const unsigned long long t_region0 = eprof ? clock64() : 0;
         const int Kp = d.K < m ? (d.K > 0 ? d.K : 0) : m;
 
-        for (int rep_ = 0; rep_ < 1 + ((rep >> 4) & 1); rep_++) {
         // (every lane of the team walks the loop, so that the rows of 16 lanes that pack the bases - 2 bits each, SmallT::stk4 - are whole)
         for (int t0 = 0; t0 < n; t0 += NT) {
             const int t = t0 + tid;
@@ -446,10 +436,8 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         }
         for (int t = tid; t < nbr; t += NT) brl[t] = d.pos_packed ? (brg[t] & 0x0FFF0FFFu) : brg[t];   // (Dev::pos_packed: the codes ride along)
         ESYNC();
-        }
 
         ESTAMP(1);   // LDS fill
-        if (skip_lvl >= 5) continue;
         // ---- correlation: conv(A,U), conv(G,C), conv(G,U).
         // Regions of <= 64 positions (one wavefront holds the whole strand in 64-bit masks) use the exact
         // direct form: popcount(mask & shifted reversed mask) per lag - the analogue of scipy's own
@@ -463,8 +451,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         // scipy's convolve makes the same kind of choice); same integer pair counts either way.
         const bool mw = !direct && LONGSEQ != 2 && (nofft || (n <= d.direct_n && P >= 128 && dbg.lag == nullptr && !force_fft &&
                         d.gc >= 0.0 && d.au >= 0.0 && d.gu >= 0.0));
-        if (!direct && !mw && LONGSEQ != 2)
-        for (int rep_ = 0; rep_ < 1 + (rep & 1); rep_++) {   // rep: profiling-only phase doubling
+        if (!direct && !mw && LONGSEQ != 2) {
             for (int t = tid; t < P; t += NT) {
                 int c = t < n ? code[t] : 0;
                 z1[t] = make_float2(c == 1 ? 1.f : 0.f, c == 3 ? 1.f : 0.f); // A + iG
@@ -570,7 +557,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         }
 
         ESTAMP(2);   // FFTs
-        if (skip_lvl >= 4) continue;
         // ---- lag values (exact integer pair counts, IEEE fp64 divide) and ranking
         // Which lags are searched (rafft/rafft.py:117-118 takes the nb_mode best by (value desc, lag desc)):
         //  - all of them when 2n-1 <= nb_mode: nothing to rank;
@@ -645,7 +631,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             const int c = tid < n ? code[tid] : 0;
             const unsigned long long mA = __ballot(c == 1), mC = __ballot(c == 2), mG = __ballot(c == 3), mU = __ballot(c == 4);
             const unsigned long long rU = __brevll(mU) >> (64 - n), rC = __brevll(mC) >> (64 - n);   // strand reversed
-            for (int rep_ = 0; rep_ < 1 + (rep & 1) + ((rep >> 5) & 1); rep_++)
             for (int k = tid; k < P; k += NT) {
                 double v = -INFINITY;
                 if (k < m) {
@@ -691,11 +676,9 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             }
         }
         ESTAMP(3);   // lag values
-        if (skip_lvl >= 3) continue;
         if (selected) {
             int *hist = (int *)(lds + lay.offA + (LONGSEQ == 2 ? lay.szA - 2048 : nofft ? 8 * P + 8 * MASK_WORDS * ((nmax + 63) >> 6) : 9 * P));      // 256 bins behind the lag values and the bit masks (8 P + 0.69 P at most); at region A's end when the masks of the biggest regions are already there
             int *shs = hist + 256;                                   // scan scratch [32]
-            for (int rep_ = 0; rep_ < 1 + ((rep >> 1) & 1); rep_++) {
             auto ukey = [&](int i) -> unsigned long long {
                 unsigned long long u = (unsigned long long)__double_as_longlong(keyv[i]);
                 return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
@@ -788,14 +771,12 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                     ESYNC();
                 }
             }
-            }
             for (int r = tid; r < Kp; r += NT)
                 if (dbg.lag) { dbg.lag[r] = rk[r]; dbg.corval[r] = keyv[rk[r]]; }
             if (tid == 0 && dbg.n_ranked) *dbg.n_ranked = Kp;
             ESYNC();
         } else {
         if (inplace)
-        for (int rep_ = 0; rep_ < 1 + ((rep >> 1) & 1); rep_++)
             for (int k2 = 2; k2 <= P; k2 <<= 1) {
                 for (int j = k2 >> 1; j > 0; j >>= 1) {
                     for (int i = tid; i < P; i += NT) {
@@ -823,7 +804,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         }
 
         ESTAMP(4);   // ranking
-        if (skip_lvl >= 2) continue;
         // ---- window_slide (rafft/rafft.py:36-83).  Small regions: one lane per ranked lag.  Big regions:
         // each diagonal is cut into C chunks handled by different lanes; a lane first walks back to the last
         // zero cell before its chunk and replays the recurrence from there (same fp64 operation order, so
@@ -847,8 +827,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             unsigned long long *F = (unsigned long long *)(lds + lay.offA + (inplace ? 0 : 8 * Pk));
             unsigned long long *R = F + MASK_F_WORDS * W;
             parts = (WsPart *)(R + 5 * W);
-            if (LONGSEQ != 2 && (!mw || inplace))   // (the direct correlation on multi-word masks has built them already - behind the lag values)
-            for (int rep_ = 0; rep_ < 1 + ((rep >> 7) & 1); rep_++) {
+            if (LONGSEQ != 2 && (!mw || inplace)) {   // (the direct correlation on multi-word masks has built them already - behind the lag values)
                 build_masks<NT>(F, R, W, n, code_at, pos, tid);
                 ESYNC();
             }
@@ -866,7 +845,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             double wgc = d.gc, wau = d.au, wgu = d.gu;
             asm volatile("" : "+v"(wgc), "+v"(wau), "+v"(wgu));
             auto win = [](const uint32_t *X, int start) -> uint32_t { const int q_ = start >> 5; return __builtin_amdgcn_alignbit(X[q_ + 1], X[q_], (uint32_t)(start & 31)); };
-            for (int rep_ = 0; rep_ < 1 + ((rep >> 2) & 1); rep_++) {
             for (int q = tid; q < Kp * C; q += NT) {
                 const int r = q / C, c = q - r * C;
                 const int lagp = rk[r];
@@ -960,9 +938,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                     if (dbg.nb) { dbg.nb[r] = mx_nb; dbg.mi[r] = mx_i; dbg.mj[r] = mx_j; dbg.score[r] = mx_s; }
                 }
             }
-            }
-        } else
-        for (int rep_ = 0; rep_ < 1 + ((rep >> 2) & 1); rep_++) {
+        } else {
             for (int q = tid; q < Kp * C; q += NT) {
                 const int r = q / C, c = q - r * C;
                 const int lagp = rk[r];
@@ -1010,7 +986,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         ESYNC();
 
         ESTAMP(5);   // window_slide
-        if (skip_lvl >= 1) continue;
         // ---- dE of every candidate stem: only the loops it changes, from the branch list
         const double par_e = dcal_to_energy(par_dcal);
         // prefix sums of the branches' stem terms (region A is free now except, when nothing was ranked, the
@@ -1056,47 +1031,46 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             nst += tot;
         }
         ESYNC();
-        for (int rep_ = 0; rep_ < 1 + ((rep >> 3) & 1); rep_++)
-            for (int si = tid; si < nst; si += NT) {
-                const int r = widx[si];
-                const int nb = wnb[r];
-                {
-                    int g = g_old;
-                    const int mi = wmi[r], mj = (int)rk[r] - mi;
-                    const int a0 = pos[mi], b0 = pos[mj], ao = pos[mi - nb + 1], bo = pos[mj + nb - 1];
-                    int lo, hi, lo_o, hi_o;
-                    br_lower4(brl, nbr, a0, b0, ao, bo, lo, hi, lo_o, hi_o);
-                    BrList outer{brl, 0, lo_o, hi_o, nbr, 1, ao, bo};
-                    int e_new = loop_energy_pre(T, B, Sl, L, ci, cj, outer, pf, g);
-                    BrList inner{brl, lo, hi, 0, 0, 0, 0, 0};
-                    e_new += loop_energy_pre(T, B, Sl, L, a0, b0, inner, pf, g);
-                    // the stem itself: a contiguous one (both strands without a gap - nearly all of them) of up to 16 pairs takes its
-                    // stacking energies from the packed strands, one look-up per pair (stem_stack_windows); the others pair by pair
-                    if (CODE_LDS && nb <= 16 && a0 - ao == nb - 1 && bo - b0 == nb - 1)
-                        e_new += stem_stack_windows(T, strand_window(P2, mi - nb + 1), strand_window(P2, mj), nb);
+        for (int si = tid; si < nst; si += NT) {
+            const int r = widx[si];
+            const int nb = wnb[r];
+            {
+                int g = g_old;
+                const int mi = wmi[r], mj = (int)rk[r] - mi;
+                const int a0 = pos[mi], b0 = pos[mj], ao = pos[mi - nb + 1], bo = pos[mj + nb - 1];
+                int lo, hi, lo_o, hi_o;
+                br_lower4(brl, nbr, a0, b0, ao, bo, lo, hi, lo_o, hi_o);
+                BrList outer{brl, 0, lo_o, hi_o, nbr, 1, ao, bo};
+                int e_new = loop_energy_pre(T, B, Sl, L, ci, cj, outer, pf, g);
+                BrList inner{brl, lo, hi, 0, 0, 0, 0, 0};
+                e_new += loop_energy_pre(T, B, Sl, L, a0, b0, inner, pf, g);
+                // the stem itself: a contiguous one (both strands without a gap - nearly all of them) of up to 16 pairs takes its
+                // stacking energies from the packed strands, one look-up per pair (stem_stack_windows); the others pair by pair
+                if (CODE_LDS && nb <= 16 && a0 - ao == nb - 1 && bo - b0 == nb - 1)
+                    e_new += stem_stack_windows(T, strand_window(P2, mi - nb + 1), strand_window(P2, mj), nb);
+                else {
+                int pa = a0, pb = b0, ty_in = pair_type(Sl[a0], Sl[b0]);
+                for (int t = 1; t < nb; t++) {
+                    const int a = pos[mi - t], b = pos[mj + t];
+                    const int ty = pair_type(Sl[a], Sl[b]);
+                    if (pa == a + 1 && pb == b - 1)
+                        e_new += T->stack[ty][rtype(ty_in)];
                     else {
-                    int pa = a0, pb = b0, ty_in = pair_type(Sl[a0], Sl[b0]);
-                    for (int t = 1; t < nb; t++) {
-                        const int a = pos[mi - t], b = pos[mj + t];
-                        const int ty = pair_type(Sl[a], Sl[b]);
-                        if (pa == a + 1 && pb == b - 1)
-                            e_new += T->stack[ty][rtype(ty_in)];
-                        else {
-                            const int lo2 = br_lower(brl, nbr, a), hi2 = br_lower(brl, nbr, b);
-                            BrList mid{brl, lo2, lo, hi, hi2, 1, pa, pb};
-                            e_new += loop_energy_pre(T, B, Sl, L, a, b, mid, pf, g);
-                            lo = lo2; hi = hi2;
-                        }
-                        pa = a; pb = b; ty_in = ty;
+                        const int lo2 = br_lower(brl, nbr, a), hi2 = br_lower(brl, nbr, b);
+                        BrList mid{brl, lo2, lo, hi, hi2, 1, pa, pb};
+                        e_new += loop_energy_pre(T, B, Sl, L, a, b, mid, pf, g);
+                        lo = lo2; hi = hi2;
                     }
-                    }
-                    const int ddc = e_new - e_old;
-                    dd[r] = ddc;
-                    const double dE = dcal_to_energy(par_dcal + ddc) - par_e;
-                    keep[r] = (uint16_t)(((dE < d.min_nrj) ? 1 : 0) | (g ? 2 : 0) | 4);     // bit 0 kept, bit 1 involves a rule / model value, bit 2 evaluated
-                    if (dbg.ddcal) dbg.ddcal[r] = ddc;
+                    pa = a; pb = b; ty_in = ty;
                 }
+                }
+                const int ddc = e_new - e_old;
+                dd[r] = ddc;
+                const double dE = dcal_to_energy(par_dcal + ddc) - par_e;
+                keep[r] = (uint16_t)(((dE < d.min_nrj) ? 1 : 0) | (g ? 2 : 0) | 4);     // bit 0 kept, bit 1 involves a rule / model value, bit 2 evaluated
+                if (dbg.ddcal) dbg.ddcal[r] = ddc;
             }
+        }
         if (dbg.ddcal) for (int r = tid; r < Kp; r += NT) if (wnb[r] == 0) dbg.ddcal[r] = INT_MIN;
         ESYNC();
 
@@ -1145,7 +1119,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             wave_sync();                      // the ballots are in LDS
             FSTAMP(13);  // (emit: counts, candidate slots)
             if (nkept && !ovf_i)
-            for (int rep_ = 0; rep_ < 1 + ((rep >> 6) & 1); rep_++)
             for (int x = tid; x < nkept; x += 64) {
                 {
                     const int r = keep[x];
@@ -1184,11 +1157,11 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                     cd.ddcal = my; cd.mi = (uint16_t)mi; cd.mj = (uint16_t)mj; cd.nb = (uint16_t)nb;
                     { int c0, c1, c2, c3; br_lower4(brl, nbr, a0, b0, ao, bo, c0, c1, c2, c3); cd.set_cuts(c0, c1, c2, c3); }
                     cd.h1 = h1; cd.h2 = h2;
-                    if (!dry) { d.cand[cbase + rank] = cd; d.cslot[cbase + rank] = 0ULL; }   // (both child slots: nobody has asked yet)
+                    d.cand[cbase + rank] = cd; d.cslot[cbase + rank] = 0ULL;   // (both child slots: nobody has asked yet)
                     if (dbg.kept) dbg.kept[rank] = r;
                 }
             }
-            if (tid == 0 && !dry) {
+            if (tid == 0) {
                 d.nd[nid].cand = cbase;
                 d.nd[nid].ncand = ovf_i ? 0 : nkept;
                 if (dbg.n_ranked) dbg.n_ranked[1] = nkept;
@@ -1246,8 +1219,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         FSTAMP(13);  // (emit: candidate slots)
         const unsigned long long cbase = *(unsigned long long *)&misc[4];
         const bool ovf = misc[2] != 0;
-        if (!ovf)
-        for (int rep_ = 0; rep_ < 1 + ((rep >> 6) & 1); rep_++) {
+        if (!ovf) {
             // packed sort key of every kept candidate: (dE biased to unsigned) << 32 | lag rank.  (They take the place of
             // the branch prefix sums in region A, which dE is done with: 8 * Kp bytes behind the lag values.)
             unsigned long long *ck = (unsigned long long *)(lds + lay.offA + (inplace ? 0 : 8 * Pk));
@@ -1291,11 +1263,11 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                 cd.ddcal = my; cd.mi = (uint16_t)mi; cd.mj = (uint16_t)mj; cd.nb = (uint16_t)nb;
                 { int c0, c1, c2, c3; br_lower4(brl, nbr, a0, b0, ao, bo, c0, c1, c2, c3); cd.set_cuts(c0, c1, c2, c3); }
                 cd.h1 = h1; cd.h2 = h2;
-                if (!dry) { d.cand[cbase + rank] = cd; d.cslot[cbase + rank] = 0ULL; }   // (both child slots: nobody has asked yet)
+                d.cand[cbase + rank] = cd; d.cslot[cbase + rank] = 0ULL;   // (both child slots: nobody has asked yet)
                 if (dbg.kept) dbg.kept[rank] = r;
             }
         }
-        if (tid == 0 && !dry) {
+        if (tid == 0) {
             d.nd[nid].cand = cbase;
             d.nd[nid].ncand = ovf ? 0 : nkept;
             if (dbg.n_ranked) dbg.n_ranked[1] = nkept;
@@ -2341,10 +2313,7 @@ __global__ __launch_bounds__(64, RAFFT_MAT_WAVES) void materialize_team_kernel(D
     int *ps = ps_[team], *bs = bs_[team], *ns = ns_[team];
     const int tb = team * MAT4_TL;                       // first lane of my team
     const unsigned long long tmask = ((1ULL << MAT4_TL) - 1ULL) << tb;
-    // (round 5) n_mat < 0: the count is the device's own (the beam step's counter) and the grid whatever the host guessed - it issues
-    // this kernel before it has read the step's counters back; the workgroups stride over the list
     if (d.c->overflow) return;                           // (see expand_kernel)
-    if (n_mat < 0) n_mat = (int)d.c->n_mat;
     for (int mat_i0 = blockIdx.x * MAT4_TEAMS; mat_i0 < n_mat; mat_i0 += gridDim.x * MAT4_TEAMS) {
     const int mat_i = mat_i0 + team;
     const bool live = mat_i < n_mat;

@@ -330,7 +330,7 @@ def test_bench_self_launch_ends_the_run_when_a_rank_dies(tmp_path):
     assert time.time() - t0 < 100
 
 
-def test_one_config_struct_is_the_only_reader_of_the_environment(tmp_path):
+def test_config_struct_is_the_only_reader_of_the_environment(tmp_path):
     """every environment switch of the library is a field of Config (rafft_config.h), read_config() there is the ONLY getenv
     caller of the library, defaults / parsing / snapshot equality hold, and the test hooks compile out with -DRAFFT_NO_TEST_HOOKS"""
     import subprocess
@@ -341,7 +341,7 @@ def test_one_config_struct_is_the_only_reader_of_the_environment(tmp_path):
     cfg = open(os.path.join(csrc, "rafft_config.h")).read()
     fields = set(re.findall(r"//\s+(RAFFT_[A-Z0-9_]+)", cfg))
     read = set(re.findall(r'"(RAFFT_[A-Z0-9_]+)"', cfg))
-    assert read and read <= fields | {"RAFFT_TAPER", "RAFFT_C2_FFT", "RAFFT_SCHED_NAP_US"}, sorted(read - fields)
+    assert read and read <= fields | {"RAFFT_TAPER", "RAFFT_SCHED_NAP_US"}, sorted(read - fields)
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "rafft_config.h" in doc and "RAFFT_NO_TEST_HOOKS" in doc
     for flags in ([], ["-DRAFFT_NO_TEST_HOOKS"]):
