@@ -360,7 +360,7 @@ int launch_expand_cls(const Config &cfg, const Dev &d, int cls, const ClsCfg cf[
     // the production builds: no diagnostics of any kind asked for (RAFFT_PROD=0: the general builds)
     const bool prod_ok = cfg.prod != 0;
     if (cls >= NGEN) {        // small regions: teams of 16 / 32 lanes, four wavefronts per workgroup (n_blocks = workgroups)
-        const bool prod = prod_ok && d.prof_e == nullptr && d.dbg.lag == nullptr;
+        const bool prod = prod_ok && d.dbg.lag == nullptr;
         if (cls == 4 && prod) hipLaunchKernelGGL((expand_small_kernel<16, true>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<16>(), st, d, cls);
         else if (cls == 4) hipLaunchKernelGGL((expand_small_kernel<16, false>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<16>(), st, d, cls);
         else if (prod) hipLaunchKernelGGL((expand_small_kernel<32, true>), dim3(n_blocks), dim3(64 * SM_WG_WAVES), small_lds_bytes<32>(), st, d, cls);
@@ -370,7 +370,7 @@ int launch_expand_cls(const Config &cfg, const Dev &d, int cls, const ClsCfg cf[
     }
     const bool longseq = cf[2].Lmax == 0;          // (class_cfg: no LDS copy of the bases)
     const int nf = cf[cls].nofft ? 0x2000 : 0;
-    const bool nodiag = prod_ok && d.prof_e == nullptr && d.dbg.lag == nullptr && !d.force_fft && d.gc >= 0.0 && d.au >= 0.0 && d.gu >= 0.0;
+    const bool nodiag = prod_ok && d.dbg.lag == nullptr && !d.force_fft && d.gc >= 0.0 && d.au >= 0.0 && d.gu >= 0.0;
     const bool prod = nodiag && nf;                // (the classes without FFT buffers)
     if (cls == 0) return nodiag ? launch_expand<512, false, 1, 2, 2>(d, 0, cf[0], n_blocks, st) : launch_expand<512, false, 1, 2>(d, 0, cf[0], n_blocks, st);
     if (longseq && cls == 2) return prod ? launch_expand<256, false, 1, 1, 1>(d, 2 | nf, cf[2], n_blocks, st) : launch_expand<256, false, 1, 1>(d, 2 | nf, cf[2], n_blocks, st);
@@ -849,24 +849,6 @@ int Wave::setup()
     d.sp_shard_cap = c.sp / NSHARD;
     d.br_shard_cap = c.br / NSHARD; d.cand_shard_cap = c.cand / NSHARD;
     if (seam) d.dbg = seam->dbg;
-    static unsigned long long *prof_buf = nullptr;
-    if (cfg.trace >= 3) {
-        if (!prof_buf) HIPCHK(hipMalloc((void **)&prof_buf, 128));
-        HIPCHK(hipMemset(prof_buf, 0, 128));
-        d.prof = prof_buf;
-        int best = 0;
-        for (size_t i = 0; i < S; i++) if (len[i] > len[best]) best = (int)i;
-        d.prof_seq = best;
-        if (cfg.prof_seq != INT_MIN) d.prof_seq = cfg.prof_seq;
-        static unsigned long long *ws_buf = nullptr; static size_t ws_cap = 0;
-        if (ws_cap < S) { if (ws_buf) HIPCHK(hipFree(ws_buf)); HIPCHK(hipMalloc((void **)&ws_buf, S * 24)); ws_cap = S; }
-        HIPCHK(hipMemset(ws_buf, 0, S * 24));
-        d.prof_ws = ws_buf;
-        static unsigned long long *pe_buf = nullptr;
-        if (!pe_buf) HIPCHK(hipMalloc((void **)&pe_buf, NCLS * PROF_E * 8));
-        HIPCHK(hipMemset(pe_buf, 0, NCLS * PROF_E * 8));
-        d.prof_e = pe_buf;
-    }
 
 
     const double ms_plan = since(tw0);
@@ -972,14 +954,8 @@ int Wave::issue_step()
         SPAN_REC(sp.a, st, sp.kind);
         // few sequences left (the long ones): a 1024-thread workgroup per sequence shortens the serial
         // chains (16 wavefronts for the prepass, 1024 combos per chunk); many sequences: 256 threads
-        const bool bs_prod = d.prof == nullptr && d.prof_ws == nullptr;          // no diagnostic stamps asked for: the production builds
-        if (n_active < wide_below) {
-            if (bs_prod) hipLaunchKernelGGL((beam_step_kernel<1024, true>), dim3((unsigned)S), dim3(1024), bs_lds[1], st, d, c.sort_cap);
-            else hipLaunchKernelGGL((beam_step_kernel<1024, false>), dim3((unsigned)S), dim3(1024), bs_lds[1], st, d, c.sort_cap);
-        } else {
-            if (bs_prod) hipLaunchKernelGGL((beam_step_kernel<256, true>), dim3((unsigned)S), dim3(256), bs_lds[0], st, d, c.sort_cap);
-            else hipLaunchKernelGGL((beam_step_kernel<256, false>), dim3((unsigned)S), dim3(256), bs_lds[0], st, d, c.sort_cap);
-        }
+        if (n_active < wide_below) hipLaunchKernelGGL((beam_step_kernel<1024>), dim3((unsigned)S), dim3(1024), bs_lds[1], st, d, c.sort_cap);
+        else hipLaunchKernelGGL((beam_step_kernel<256>), dim3((unsigned)S), dim3(256), bs_lds[0], st, d, c.sort_cap);
         HIPCHK(hipGetLastError());
         SPAN_REC(sp.b, st, sp.kind);
         spans.push_back(sp);
@@ -1000,10 +976,9 @@ int Wave::issue_materialize(unsigned nm)
     SPAN_REC(sp.a, st, sp.kind);
     // (four structures per wavefront, teams of 16 lanes, when the short productive-region lists are in use -
     //  materialize_team_kernel; otherwise one structure per wavefront)
-    if (d.prof_e == nullptr && d.max_prod <= MAT4_PROD)
+    if (d.max_prod <= MAT4_PROD)
         hipLaunchKernelGGL(materialize_team_kernel, dim3((nm + MAT4_TEAMS - 1) / MAT4_TEAMS), dim3(64), 0, st, d, (int)nm);
-    else if (d.prof_e == nullptr) hipLaunchKernelGGL(materialize_kernel<true>, dim3(nm), dim3(MAT_NT), mat_lds, st, d);
-    else hipLaunchKernelGGL(materialize_kernel<false>, dim3(nm), dim3(MAT_NT), mat_lds, st, d);
+    else hipLaunchKernelGGL(materialize_kernel, dim3(nm), dim3(MAT_NT), mat_lds, st, d);
     HIPCHK(hipGetLastError());
     // tail of the batch: so few new structures that their regions fit one wave of workgroups of the widest class
     // (measured on the benchmark batch: 18.8 -> 17.3 ms; thresholds in new structures per step, per CU)
@@ -1224,77 +1199,6 @@ int Wave::finish_done_body()
     const double ms_loop = ms_loop_, tl_stats = tl_stats_, tl_gather = tl_gather_;
     const double tl_copy = since(tw2);
     const long long tot_bytes = last_rows_bytes;
-    if (d.prof_e) {
-        unsigned long long pe[NCLS * PROF_E];
-        HIPCHK(hipMemcpy(pe, d.prof_e, sizeof pe, hipMemcpyDeviceToHost));
-        static const char *nm[8] = {"fetch+header", "LDS fill", "FFT", "lag values", "ranking", "window_slide", "dE", "emit"};
-        {
-            static const char *mn[7] = {"header+list+digits", "pass 1 (sizes)", "allocation", "parent row", "pass 2 descriptors", "region copies", "row out"};
-            unsigned long long t = 0;
-            for (int k = 0; k < 7; k++) t += pe[k];
-            fprintf(stderr, "[rafft] materialize phase shares (%llu Mcycles):", t / 1000000);
-            for (int k = 0; k < 7; k++) fprintf(stderr, " %s %.1f%%", mn[k], t ? 100.0 * (double)pe[k] / (double)t : 0.0);
-            fprintf(stderr, "\n");
-        }
-        for (int c = NGEN; c < NCLS; c++) {
-            static const char *sn[7] = {"fetch", "header+fill+masks", "window_slide", "branch prefix sums", "dE", "values+compaction+slots", "order+emit"};
-            unsigned long long t = 0;
-            for (int k = 0; k < 7; k++) t += pe[c * PROF_E + k];
-            fprintf(stderr, "[rafft] small-region class %d (lane 0 of every wavefront, %llu Mcycles, %llu rounds by %llu wavefronts = %.1f kcycles per round):", c, t / 1000000,
-                    pe[c * PROF_E + 8], pe[c * PROF_E + 9], pe[c * PROF_E + 8] ? (double)t / (double)pe[c * PROF_E + 8] / 1e3 : 0.0);
-            for (int k = 0; k < 7; k++) fprintf(stderr, " %s %.1f%%", sn[k], t ? 100.0 * (double)pe[c * PROF_E + k] / (double)t : 0.0);
-            fprintf(stderr, "\n");
-        }
-        for (int c = 1; c < NGEN; c++) {
-            unsigned long long t = 0;
-            for (int k = 0; k < 8; k++) t += pe[c * PROF_E + k];
-            fprintf(stderr, "[rafft] expand class %d phase shares (lane 0 of every wavefront, %llu Mcycles):", c, t / 1000000);
-            for (int k = 0; k < 8; k++) fprintf(stderr, " %s %.1f%%", nm[k], t ? 100.0 * (double)pe[c * PROF_E + k] / (double)t : 0.0);
-            fprintf(stderr, "\n");
-            unsigned long long hn = 0, hc_ = 0;
-            for (int k = 0; k < 6; k++) { hn += pe[c * PROF_E + 8 + k]; hc_ += pe[c * PROF_E + 16 + k]; }
-            static const char *bn[6] = {"n<=8", "<=16", "<=32", "<=64", "<=128", ">128"};
-            fprintf(stderr, "[rafft] expand class %d by region size (share of regions / share of cycles / kcycles per region):", c);
-            for (int k = 0; k < 6; k++)
-                fprintf(stderr, "  %s %.1f%% / %.1f%% / %.1f", bn[k], hn ? 100.0 * pe[c * PROF_E + 8 + k] / hn : 0.0, hc_ ? 100.0 * pe[c * PROF_E + 16 + k] / hc_ : 0.0,
-                        pe[c * PROF_E + 8 + k] ? (double)pe[c * PROF_E + 16 + k] / (double)pe[c * PROF_E + 8 + k] / 1e3 : 0.0);
-            fprintf(stderr, "\n");
-            fprintf(stderr, "[rafft]   class %d: inside fetch+header: claiming items %llu Mcycles, work-list entry %llu Mcycles (of %llu)\n", c, pe[c * PROF_E + 40] / 1000000, pe[c * PROF_E + 41] / 1000000, pe[c * PROF_E] / 1000000);
-            fprintf(stderr, "[rafft]   class %d: inside dE: branch prefix sums %llu, candidates %llu Mcycles; inside emit: compaction %llu, candidate slots %llu, keys+rank %llu, hashes+cuts+stores %llu Mcycles\n", c,
-                    pe[c * PROF_E + 42] / 1000000, pe[c * PROF_E + 43] / 1000000, pe[c * PROF_E + 44] / 1000000, pe[c * PROF_E + 45] / 1000000, pe[c * PROF_E + 46] / 1000000, pe[c * PROF_E + 47] / 1000000);
-            if (c == 1) {
-                fprintf(stderr, "[rafft]   class 1, regions without any stem / without a kept candidate (share of the size class):");
-                for (int k = 0; k < 6; k++) {
-                    const double nreg = (double)pe[c * PROF_E + 8 + k];
-                    fprintf(stderr, "  %s %.1f%% / %.1f%%", bn[k], nreg ? 100.0 * pe[c * PROF_E + 80 + k] / nreg : 0.0, nreg ? 100.0 * pe[c * PROF_E + 88 + k] / nreg : 0.0);
-                }
-                fprintf(stderr, "\n");
-            }
-        }
-    }
-    if (d.prof_ws) {
-        std::vector<unsigned long long> wsv(S * 3);
-        HIPCHK(hipMemcpy(wsv.data(), d.prof_ws, S * 24, hipMemcpyDeviceToHost));
-        std::vector<int> ord(S);
-        for (size_t i = 0; i < S; i++) ord[i] = (int)i;
-        std::sort(ord.begin(), ord.end(), [&](int a, int b) { return wsv[3 * a] > wsv[3 * b]; });
-        unsigned long long tot = 0, totc = 0;
-        unsigned long long totp = 0, totk = 0;
-        for (size_t i = 0; i < S; i++) { tot += wsv[3 * i]; totc += wsv[3 * i + 1] & 0xFFFFFF; totk += wsv[3 * i + 1] >> 24; totp += wsv[3 * i + 2]; }
-        fprintf(stderr, "[rafft] beam_step per sequence: total cycles %llu, chunks %llu, combos %llu, parents walked %llu over %zu sequences\n", tot, totc, totk, totp, S);
-        for (size_t k = 0; k < std::min<size_t>(S, 12); k++) {
-            int i = ord[k];
-            fprintf(stderr, "[rafft]   #%zu local seq %d (L=%d): cycles %llu, chunks %llu, combos %llu, parents walked %llu\n", k, i, len[i], wsv[3 * i], wsv[3 * i + 1] & 0xFFFFFF, wsv[3 * i + 1] >> 24, wsv[3 * i + 2]);
-        }
-    }
-    if (d.prof) {
-        unsigned long long pv[16];
-        HIPCHK(hipMemcpy(pv, d.prof, 128, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[rafft]   product loop detail: head %llu, decode+lookup %llu, scans %llu, write+insert %llu; %llu growths of `seen` in the walk: before %llu, allocation %llu, zero fill %llu, rehash %llu\n",
-                pv[6], pv[8], pv[9], pv[10], pv[14], pv[7], pv[11], pv[12], pv[13]);
-        fprintf(stderr, "[rafft] beam_step stamps of the longest sequence (cycles): prepass %llu, product loop %llu, single phase %llu, sort %llu, survivors %llu over %llu steps\n",
-                pv[0], pv[1], pv[2], pv[3], pv[4], pv[5]);
-    }
     if (cfg.trace) {
         auto mx = [&](const ShardCtr *sc) { unsigned long long m = 0, t = 0; for (int i = 0; i < NSHARD; i++) { m = std::max(m, sc[i].v); t += sc[i].v; } return std::make_pair(m, t); };
         auto nd = mx(hc.node), po = mx(hc.pos), br = mx(hc.br), spr = mx(hc.sp), ca = mx(hc.cand), pr = mx(hc.prod), nl = mx(hc.nlist);
@@ -1384,7 +1288,7 @@ static unsigned admit_below()
 // one at a time)
 static size_t merge_cap()
 {
-    return (size_t)std::max(1L, g.sched_cfg.merge_seqs);
+    return (size_t)std::max(1, g.sched_cfg.merge_seqs);
 }
 
 static bool same_params(const rafft_params &a, const rafft_params &b)

@@ -12,7 +12,6 @@
 //        -DRAFFT_NO_TEST_HOOKS).
 // INTEGRATION.md section 5 lists them for callers.
 #pragma once
-#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,7 +20,6 @@ struct Config {
     // ---- the 8-byte fields first (no padding inside the struct: two snapshots are compared as bytes)
     double reserve_frac = 0.10;// RAFFT_RESERVE_FRAC  T  workspaces are reserved for the merge cap when that stays below this share of the HBM
     double est = 0.0;          // RAFFT_EST           H  arena estimate (survivors per beam slot); 0: from the lengths
-    long merge_seqs = 16384;   // RAFFT_MERGE_SEQS    T  sequences one merged wave may hold
     long linger_us = 600;      // RAFFT_LINGER_US     T  a stream of submissions is merged while they keep coming this close together (round 5: 150 -> 600 us - a Python caller queues a batch of the benchmark set every 250-300 us, and the first one of a burst was folded alone)
     long spin_us = 200, nap_us = 50; // RAFFT_SCHED_SPIN_US / RAFFT_SCHED_NAP_US  T  the scheduler thread polls this long after progress, then naps in slices
     double big_wave_frac = 0.10; // RAFFT_BIG_WAVE_FRAC T  waves whose arenas pass this share of the HBM run one at a time
@@ -31,7 +29,7 @@ struct Config {
     int c3_switch = -1;        // RAFFT_C3_SWITCH     T  ... up to this many regions per step the FFT plan works (-1: one per CU)
     int direct_n = 1024;       // RAFFT_DIRECT_N      T  wide classes: popcount correlation up to this region size, FFT beyond
     int force_fft = 0;         // RAFFT_FORCE_FFT     D  FFT correlation for short regions too (parity tests)
-    int prod = 1;              // RAFFT_PROD          D  0: the general builds of the kernels (seam, stamps compiled in)
+    int prod = 1;              // RAFFT_PROD          D  0: the general builds of the kernels (seam, forced FFT, negative weights compiled in)
     int no_memo = 0;           // RAFFT_NO_MEMO       D  1: every structure expands its own regions (no sharing of identical loops)
     int small_n4 = 16, small_n5 = 32; // RAFFT_SMALL="n4,n5" T  region sizes of the two small-region classes ("0,0": off)
     int small_wg = 4;          // RAFFT_SMALL_WG      T  their workgroups per CU
@@ -45,11 +43,11 @@ struct Config {
     int split = -1;            // RAFFT_SPLIT         T  long-tail cut of a batch: -1 automatic, 0 never, > 0 at that length
     int serial = 0;            // RAFFT_SERIAL        D  every kernel of a step on one stream (per-kernel profiles)
     // ---- D: diagnostics (per batch)
-    int trace = 0;             // RAFFT_TRACE         D  1: per-wave summaries, 2: per-step work lists, 3: phase stamps (general builds)
+    int trace = 0;             // RAFFT_TRACE         D  1: per-wave summaries, 2: per-step work lists (higher values act as 2)
     int spans = -1;            // RAFFT_SPANS         D  HIP-event spans: 0 none, 1 dominant kernel (default), 2 every stage
-    int prof_seq = INT_MIN;    // RAFFT_PROF_SEQ      D  sequence whose beam step is stamped (-1: all)
     // ---- scheduler (read when the scheduler thread starts)
     int max_waves = 3;         // RAFFT_MAX_WAVES     T  bulk waves in flight
+    int merge_seqs = 16384;    // RAFFT_MERGE_SEQS    T  sequences one merged wave may hold
     // ---- process-wide (read at rafft_init)
     int trace_alloc = 0;       // RAFFT_TRACE_ALLOC   D  log every device / pinned allocation
     // ---- H: test hooks
@@ -59,7 +57,7 @@ struct Config {
     int seen_fixed = 0;        // RAFFT_SEEN_FIXED    H  1: every `seen` set starts at SEEN0 slots instead of a table sized from the length (the growth path)
     int test_cand_limit = 0;   // RAFFT_TEST_CAND_LIMIT H  lower the 31-bit limit of the candidate table (split path on small jobs)
 };
-static_assert(sizeof(Config) == 8 * 7 + 4 * 30, "Config: 8-byte fields first, an even number of ints - no padding (same_config compares bytes)");
+static_assert(sizeof(Config) == 8 * 6 + 4 * 30, "Config: 8-byte fields first, an even number of ints - no padding (same_config compares bytes)");
 
 inline Config read_config()
 {
@@ -75,8 +73,8 @@ inline Config read_config()
     I("RAFFT_WIDE_BELOW", c.wide_below); I("RAFFT_MERGE_BELOW", c.merge_below); I("RAFFT_MERGE2_BELOW", c.merge2_below);
     F("RAFFT_RESERVE_FRAC", c.reserve_frac); I("RAFFT_SPLIT", c.split); I("RAFFT_SERIAL", c.serial);
     I("RAFFT_TRACE", c.trace); if (getenv("RAFFT_TRACE") && c.trace < 1) c.trace = 1;      // (set to anything: at least the summaries)
-    I("RAFFT_SPANS", c.spans); I("RAFFT_PROF_SEQ", c.prof_seq);
-    I("RAFFT_MAX_WAVES", c.max_waves); L("RAFFT_MERGE_SEQS", c.merge_seqs);
+    I("RAFFT_SPANS", c.spans);
+    I("RAFFT_MAX_WAVES", c.max_waves); I("RAFFT_MERGE_SEQS", c.merge_seqs);
     L("RAFFT_LINGER_US", c.linger_us); L("RAFFT_SCHED_SPIN_US", c.spin_us); L("RAFFT_SCHED_NAP_US", c.nap_us); F("RAFFT_BIG_WAVE_FRAC", c.big_wave_frac);
     B("RAFFT_TRACE_ALLOC", c.trace_alloc);
 #ifndef RAFFT_NO_TEST_HOOKS

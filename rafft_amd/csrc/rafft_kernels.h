@@ -56,7 +56,6 @@ static_assert(sizeof(Cand) == 32, "Cand must be 32 bytes");
 #endif
 #define NCLS 6          // expand size classes: 0-3 the general kernel (NGEN), 4-5 the small-region kernel (teams of 16 / 32 lanes)
 #define NGEN 4
-#define PROF_E 96      // RAFFT_TRACE=3: 64-bit diagnostic slots per expand class (Dev::prof_e)
 struct ShardCtr { unsigned long long v; unsigned long long pad[7]; };   // one 64-byte line each
 
 // structure row: one beam survivor (see the file header)
@@ -174,9 +173,6 @@ struct Dev {
     MatRec *mat; uint32_t mat_cap;
     Counters *c;
     DebugOut dbg;
-    unsigned long long *prof; int prof_seq;   // diagnostic stamps of beam_step_kernel (RAFFT_TRACE=3)
-    unsigned long long *prof_e;               // RAFFT_TRACE=3: expand_kernel phase cycles, regions and cycles by region size, phase cycles by region size [NCLS][PROF_E]
-    unsigned long long *prof_ws;              // RAFFT_TRACE=3: per sequence [cycles, chunks, max cycles of one step]
 };
 
 // expand-kernel size classes: 1 small (FFT size P <= 512: one wavefront per region), 2 medium (P <= 2048: 256 threads),

@@ -8,9 +8,9 @@
 //                       (rafft/rafft.py:36-83), local Turner dE of every candidate stem from
 //                       prefix sums over the loop's branch list + filter/sort
 //                       (rafft/rafft.py:86-109)
-//                       Template switch PROD: production builds with the debug seam, the phase
-//                       stamps and - for the classes whose regions all take the popcount
-//                       correlation - the FFT compiled out (no register spills).
+//                       Template switch PROD: production builds with the debug seam and - for
+//                       the classes whose regions all take the popcount correlation - the FFT
+//                       compiled out (no register spills).
 //   expand_small_kernel  (rafft_expand_small.hip) the same for regions of up to 16 / 32 positions:
 //                       teams of 16 / 32 lanes, four or two regions per wavefront
 //   beam_step_kernel    one workgroup per sequence: helix combination in product order, flat
@@ -278,9 +278,10 @@ __device__ __forceinline__ void wave_sync()
 //              correlation is the exact direct form on multi-word bit masks - popcount(base mask AND shifted reversed base
 //              mask), the analogue of scipy's own direct branch (rafft/utils.py:121) - and the lag values live in a
 //              per-workgroup scratch in HBM instead of LDS.  Same integer pair counts, same fp64 values, same ranking.
-// PROD: the production build of a class without FFT buffers (no seam, no forced FFT, no negative weights, no diagnostics): the
-// debug-seam stores, the phase stamps, the FFT and the cell-by-cell window_slide are compiled out - fewer live registers, fewer spills.
-// PROD 2: the same for a class that keeps its FFT (regions beyond Dev::direct_n positions): only the diagnostics go.
+// PROD: the production build of a class without FFT buffers (no seam, no forced FFT, no negative weights): the debug-seam
+// stores, the FFT and the cell-by-cell window_slide are compiled out - fewer live registers, fewer spills.
+// PROD 2: the same for a class that keeps its FFT (regions beyond Dev::direct_n positions): only the seam, forced FFT and negative
+//         weights go.
 // PROD 3 (with LONGSEQ 2): the same kernel as the class for regions beyond 4096 positions, compiled for FOUR wavefronts per SIMD: it
 //         serves the regions of 1025-4096 positions of ordinary sequences when the host routes them here (RAFFT_C3_DIRECT, class_cfg) -
 //         ~50 KiB of LDS instead of the 150 KiB of the FFT plan, two or three workgroups per CU instead of one.
@@ -290,7 +291,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
     const int cls = cls_arg & 0xFF;
     const DebugOut dbg = PROD ? DebugOut{} : d.dbg;
     const int force_fft = PROD ? 0 : d.force_fft;
-    unsigned long long *const prof_e = PROD ? nullptr : d.prof_e;
 
     static_assert(WPB == 1 || NT == 64, "only the one-wavefront class packs several wavefronts into a workgroup");
     static_assert(LONGSEQ == 0 || NT > 64, "long sequences never reach the one-wavefront class");
@@ -356,10 +356,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
     // Work items are fetched FETCH at a time and candidate slots are reserved in slabs, so that the
     // two atomics with a returned value (a full L2 round trip each) are paid once per several regions.
     // (only when there is plenty of work: with fewer regions than workgroups every region gets its own)
-    const bool eprof = prof_e != nullptr && tid == 0;      // diagnostic phase stamps (RAFFT_TRACE=3)
-    unsigned long long eacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, et = eprof ? clock64() : 0, ft1 = 0;
-#define ESTAMP(k) do { if (eprof) { const unsigned long long tn_ = clock64(); eacc[k] += tn_ - et; et = tn_; ft1 = tn_; } } while (0)
-#define FSTAMP(k) do { if (eprof) { const unsigned long long tn_ = clock64(); eacc[k] += tn_ - ft1; ft1 = tn_; } } while (0)   // inside dE (10, 11) and emit (12-15)
     const unsigned FETCH = (NT == 64 && n_items > 4u * n_teams) ? (unsigned)d.fetch_bulk : 1u;
     const FetchPlan fplan = fetch_plan(d, n_items, NT == 64 ? FETCH : 1u, 1u);
     unsigned fetch_base = 0, fetch_left = 0;                 // uniform across the workgroup
@@ -369,7 +365,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
 
     for (;;) {
         ESYNC();                       // previous region's LDS use is over
-        unsigned long long ft0 = eprof ? clock64() : 0;
         if (fetch_left == 0) {
             unsigned fcount = 1;
             if (NT == 64) fetch_base = fetch_chunk(d, cls, fplan, fshard, ffailed, fcount);
@@ -387,9 +382,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         const unsigned item = NT == 64 ? (unsigned)__builtin_amdgcn_readfirstlane((int)fetch_base) : fetch_base;
         fetch_base++; fetch_left--;
         if (item >= n_items) { fetch_left = 0; continue; }       // (tail of the list's last chunk; other shards may still hold chunks)
-        if (eprof) { const unsigned long long t_ = clock64(); eacc[8] += t_ - ft0; ft0 = t_; }
         const int nid = NT == 64 ? __builtin_amdgcn_readfirstlane(d.work[cls][item]) : d.work[cls][item];
-        if (eprof) { const unsigned long long t_ = clock64(); eacc[9] += t_ - ft0 + (unsigned long long)(nid & 0); ft0 = t_; }
         const int L = d.nd[nid].L;                 // (the record carries its sequence's length and offset: no look-up keyed on `seq`)
         const int n = d.nd[nid].n, ci = d.nd[nid].ci, cj = d.nd[nid].cj, nbr = d.nd[nid].nbr;
         const int par_dcal = d.nd[nid].pdcal;
@@ -409,9 +402,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         const int P = next_pow2_ge(m);
         const int logP = 31 - __clz(P);
         const int Pk = LONGSEQ == 2 ? 0 : P;       // the lag values occupy 8 P bytes of region A - unless they live in HBM
-        const int size_bk = n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : n <= 64 ? 3 : n <= 128 ? 4 : 5;      // (diagnostic: regions and cycles by size)
-        ESTAMP(0);   // fetch + header
-        const unsigned long long t_region0 = eprof ? clock64() : 0;
         const int Kp = d.K < m ? (d.K > 0 ? d.K : 0) : m;
 
         // (every lane of the team walks the loop, so that the rows of 16 lanes that pack the bases - 2 bits each, SmallT::stk4 - are whole)
@@ -437,7 +427,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         for (int t = tid; t < nbr; t += NT) brl[t] = d.pos_packed ? (brg[t] & 0x0FFF0FFFu) : brg[t];   // (Dev::pos_packed: the codes ride along)
         ESYNC();
 
-        ESTAMP(1);   // LDS fill
         // ---- correlation: conv(A,U), conv(G,C), conv(G,U).
         // Regions of <= 64 positions (one wavefront holds the whole strand in 64-bit masks) use the exact
         // direct form: popcount(mask & shifted reversed mask) per lag - the analogue of scipy's own
@@ -556,7 +545,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             }
         }
 
-        ESTAMP(2);   // FFTs
         // ---- lag values (exact integer pair counts, IEEE fp64 divide) and ranking
         // Which lags are searched (rafft/rafft.py:117-118 takes the nb_mode best by (value desc, lag desc)):
         //  - all of them when 2n-1 <= nb_mode: nothing to rank;
@@ -675,7 +663,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                 ESYNC();
             }
         }
-        ESTAMP(3);   // lag values
         if (selected) {
             int *hist = (int *)(lds + lay.offA + (LONGSEQ == 2 ? lay.szA - 2048 : nofft ? 8 * P + 8 * MASK_WORDS * ((nmax + 63) >> 6) : 9 * P));      // 256 bins behind the lag values and the bit masks (8 P + 0.69 P at most); at region A's end when the masks of the biggest regions are already there
             int *shs = hist + 256;                                   // scan scratch [32]
@@ -803,7 +790,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         ESYNC();
         }
 
-        ESTAMP(4);   // ranking
         // ---- window_slide (rafft/rafft.py:36-83).  Small regions: one lane per ranked lag.  Big regions:
         // each diagonal is cut into C chunks handled by different lanes; a lane first walks back to the last
         // zero cell before its chunk and replays the recurrence from there (same fp64 operation order, so
@@ -985,7 +971,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         }
         ESYNC();
 
-        ESTAMP(5);   // window_slide
         // ---- dE of every candidate stem: only the loops it changes, from the branch list
         const double par_e = dcal_to_energy(par_dcal);
         // prefix sums of the branches' stem terms (region A is free now except, when nothing was ranked, the
@@ -1013,7 +998,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             if (tid == 0) { pe_ext[nbr] = c_e; pe_ml[nbr] = c_m; psp[nbr] = (uint16_t)c_s; }
         }
         ESYNC();
-        FSTAMP(10);  // (dE: branch prefix sums)
         const BrPrefix pf{pe_ext, pe_ml, psp};
         const BrList all_br{brl, 0, nbr, 0, 0, 0, 0, 0};
         int g_old = 0;           // (g: the energy involves a rule / model value of the built-in tables - SmallT::lsb)
@@ -1074,8 +1058,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
         if (dbg.ddcal) for (int r = tid; r < Kp; r += NT) if (wnb[r] == 0) dbg.ddcal[r] = INT_MIN;
         ESYNC();
 
-        FSTAMP(11);  // (dE: the loop as it is + every candidate)
-        ESTAMP(6);   // dE
         // ---- stable sort of the kept candidates by dE (ties keep lag-rank order), emit
         int nkept = 0;
         if constexpr (NT == 64) {
@@ -1117,7 +1099,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                 if (!ovf_i) { cbase = slab_base; slab_base += nkept; slab_left -= nkept; }
             }
             wave_sync();                      // the ballots are in LDS
-            FSTAMP(13);  // (emit: counts, candidate slots)
             if (nkept && !ovf_i)
             for (int x = tid; x < nkept; x += 64) {
                 {
@@ -1142,7 +1123,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                             }
                         }
                     }
-                    FSTAMP(14);  // (emit: rank)
                     const int mi = wmi[r], mj = (int)rk[r] - mi, nb = wnb[r];
                     const int a0 = pos[mi], b0 = pos[mj], ao = pos[mi - nb + 1], bo = pos[mj + nb - 1];
                     uint64_t h1 = 0, h2 = 0;
@@ -1198,7 +1178,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             }
             ESYNC();
         }
-        FSTAMP(12);  // (emit: compaction)
         if (tid == 0) {
             unsigned long long base = 0;
             misc[2] = 0;
@@ -1216,7 +1195,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             st_items++; st_n += n; st_lags += Kp; st_nbr += nbr;
         }
         ESYNC();
-        FSTAMP(13);  // (emit: candidate slots)
         const unsigned long long cbase = *(unsigned long long *)&misc[4];
         const bool ovf = misc[2] != 0;
         if (!ovf) {
@@ -1248,7 +1226,6 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                             rank += ky < kx ? 1 : 0;
                     }
                 }
-                FSTAMP(14);  // (emit: sort keys, rank)
                 int mi = wmi[r], mj = (int)rk[r] - mi, nb = wnb[r];
                 const int a0 = pos[mi], b0 = pos[mj], ao = pos[mi - nb + 1], bo = pos[mj + nb - 1];
                 uint64_t h1 = 0, h2 = 0;
@@ -1273,24 +1250,7 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
             if (dbg.n_ranked) dbg.n_ranked[1] = nkept;
         }
         }
-        FSTAMP(15);  // (emit: pair hashes, cuts, stores)
-        ESTAMP(7);   // emit
-        if (NT == 64 && prof_e != nullptr) {         // diagnostic: regions without any candidate stem / without a kept one, by size
-            int has = 0;
-            for (int r = tid; r < Kp; r += NT) has |= wnb[r] > 0 ? 1 : 0;
-            const bool anystem = __ballot(has) != 0ULL;
-            if (tid == 0 && !anystem) atomicAdd(&prof_e[cls * PROF_E + 80 + size_bk], 1ULL);
-            if (tid == 0 && nkept == 0) atomicAdd(&prof_e[cls * PROF_E + 88 + size_bk], 1ULL);
-        }
-        if (eprof) { atomicAdd(&prof_e[cls * PROF_E + 8 + size_bk], 1ULL); atomicAdd(&prof_e[cls * PROF_E + 16 + size_bk], (unsigned long long)(clock64() - t_region0)); }
     }
-    if (eprof) {
-        for (int k = 0; k < 8; k++) atomicAdd(&prof_e[cls * PROF_E + k], eacc[k]);
-        atomicAdd(&prof_e[cls * PROF_E + 40], eacc[8]); atomicAdd(&prof_e[cls * PROF_E + 41], eacc[9]);
-        for (int k = 10; k < 16; k++) atomicAdd(&prof_e[cls * PROF_E + 32 + k], eacc[k]);
-    }
-#undef ESTAMP
-#undef FSTAMP
     if (tid == 0 && st_items) {
         Counters::StatLine *sl = &d.c->xstat[cls][gteam & (NSHARD - 1)];
         atomicAdd(&sl->items, st_items);
@@ -1410,7 +1370,7 @@ __device__ __forceinline__ unsigned long long sat_mul(unsigned long long a, unsi
 }
 
 // LDS: sort keys (dynamic) + product description + per-parent prepass records
-template <int BS_NT, bool PROD = false>      // (PROD: the diagnostic stamps compiled out - see expand_kernel)
+template <int BS_NT>
 __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(Dev d, int sort_cap)
 {
     extern __shared__ __align__(16) unsigned char lds[];
@@ -1441,14 +1401,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
     if (tid == 0) sh[27] = d.c->overflow != 0 ? 1 : 0;
     __syncthreads();
     if (sh[27]) return;
-    const bool prof = !PROD && d.prof && (d.prof_seq < 0 || sq == d.prof_seq) && tid == 0;   // diagnostic stamps (RAFFT_TRACE=3; RAFFT_PROF_SEQ=-1: summed over all sequences)
-    unsigned long long tprev = prof ? clock64() : 0;
-    unsigned long long *const prof_ws = PROD ? nullptr : d.prof_ws;
-    const unsigned long long t_begin = prof_ws ? clock64() : 0;
-    unsigned long long n_chunks = 0, n_par = 0, n_combos = 0;
-#define WS_END() do { if (prof_ws && tid == 0) { unsigned long long dt_ = clock64() - t_begin; prof_ws[3 * sq] += dt_; prof_ws[3 * sq + 1] += n_chunks | (n_combos << 24); \
-        prof_ws[3 * sq + 2] += n_par; } } while (0)
-#define STAMP(k) do { if (prof) { unsigned long long tn_ = clock64(); atomicAdd(&d.prof[k], tn_ - tprev); tprev = tn_; } } while (0)
     const int nbeam = d.beam_n[sq];
     const int step_no = d.nsteps[sq];          // (read by everyone before the barrier below; thread 0 counts the step after it)
     int *beam = d.beam + (size_t)sq * d.B;
@@ -1603,7 +1555,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
         }
     }
     __syncthreads();
-    STAMP(0);
 
     // ---- the product walk (rafft/rafft.py:173-204), flat over all parents: position p of the walk is combo
     // cur_b + (p - ppre[b]) of the parent b whose range holds p, in beam order and itertools.product order.
@@ -1644,8 +1595,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
         if ((unsigned long long)(scnt + chunk) * 2 > scap) {   // grow the seen set (rehash into a zeroed region)
             uint32_t ncap = scap;
             while ((unsigned long long)(scnt + BS_NT) * 2 > ncap) ncap <<= 1;
-            STAMP(7);
-            if (prof) atomicAdd(&d.prof[14], 1ULL);
             if (tid == 0) {
                 unsigned long long o = atomicAdd(&d.c->seen_top, (unsigned long long)ncap);
                 if (o + ncap > d.seen_cap_total) { atomicOr(&d.c->overflow, OVF_SEEN); *(unsigned long long *)&sh[8] = ~0ULL; }
@@ -1656,18 +1605,13 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
             __syncthreads();
             if (o == ~0ULL) { d.done[sq] = 1; return; }
             uint64_t *ntab = d.seen + 2 * o;
-            STAMP(11);
             for (uint32_t i = tid; i < ncap; i += BS_NT) ((ulonglong2 *)ntab)[i] = make_ulonglong2(0ULL, 0ULL);   // arena is not pre-zeroed
             __syncthreads();
-            STAMP(12);
             seen_rehash<BS_NT>(stab, scap, ntab, ncap, tid);
             __syncthreads();
-            STAMP(13);
             stab = ntab; scap = ncap;
             if (tid == 0) { d.seen_off[sq] = o; d.seen_cap[sq] = ncap; }
         }
-        n_chunks++; n_combos += chunk;
-        STAMP(6);   // loop head / seen growth
         const int need = d.max_branch - nb_branch;      // > 0
         int b = 0, sidb = 0, cd = 0, slot = -1;
         uint32_t free_sl = 0;
@@ -1749,7 +1693,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
             }
             slot = (int)sl;
         }
-        STAMP(8);   // decode + seen lookups
         __syncthreads();
         const bool isnew = cand_new && wk_tab[slot < 0 ? 0 : slot] == (unsigned int)tid + 1u;
         const unsigned long long bal = __ballot(isnew);
@@ -1770,7 +1713,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
             } else atomicOr(&d.c->overflow, OVF_SORT);
             seen_insert_at(stab, scap, h1, h2, free_sl);
         }
-        STAMP(9);
         if (hit) {
             // the reference stops walking after the combo that brings nb_branch to max_branch
             if (accepted && ex == need - 1) {
@@ -1790,9 +1732,7 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
         W += (unsigned long long)chunk;
         for (int i = tid; i < 2 * BS_NT; i += BS_NT) wk_tab[i] = 0;
         __syncthreads();
-        STAMP(10);  // child records + seen insert
     }
-    STAMP(1);
     if (single_from < nbeam) {
         // ---- parents in "one combo then break" mode: combo 0 of each (from the prepass), accepted in
         // beam order if its structure is new; a parent whose cursor already moved replays a known combo
@@ -1853,7 +1793,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
             __syncthreads();
         }
     }
-    STAMP(2);
     if (tid == 0) { d.seen_cnt[sq] = scnt; atomicAdd(&d.c->xstat[1][sq & (NSHARD - 1)].children, (unsigned long long)nchild); }
     if (nchild > d.ch_cap) nchild = d.ch_cap;
 
@@ -1902,7 +1841,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
             }
         }
     }
-    STAMP(3);
     const int nnew = N < d.B ? N : d.B;
     // children among the survivors
     int nsurv_child = 0;
@@ -1928,7 +1866,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
                 }
             }
         }
-        WS_END();
         return;
     }
     if (tid == 0) {
@@ -1980,11 +1917,6 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
         __syncthreads();
     }
     if (tid == 0) d.beam_n[sq] = nnew;
-    STAMP(4);
-    if (prof) atomicAdd(&d.prof[5], 1ULL);
-    WS_END();
-#undef WS_END
-#undef STAMP
 }
 
 // ------------------------------------------------------- materialize kernel
@@ -2110,7 +2042,6 @@ __device__ __forceinline__ void mat_copy_tile(const Dev &d, int l, int kb, int k
 #endif
 // (dynamic LDS: the productive-region lists only - a structure is stored as the pairs it adds to its parent's, no dot-bracket row is
 //  staged or written here; a latency-bound kernel of one-wavefront workgroups lives on the number of them a CU holds)
-template <bool PROD>      // (PROD: the phase stamps of RAFFT_TRACE=3 compiled out - see expand_kernel)
 __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(Dev d)
 {
     extern __shared__ __align__(16) uint8_t mat_dyn[];
@@ -2126,10 +2057,6 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
     __shared__ unsigned long long sh64[5];
     __shared__ int shi[8];
     const int tid = threadIdx.x;
-    // diagnostic phase stamps (RAFFT_TRACE=3) of every 64th workgroup, kept in the slots of class 0
-    const bool mprof = !PROD && d.prof_e != nullptr && tid == 0 && (blockIdx.x & 63) == 0;
-    unsigned long long mt = mprof ? clock64() : 0, macc[7] = {0, 0, 0, 0, 0, 0, 0};
-#define MSTAMP(k) do { if (mprof) { const unsigned long long tn_ = clock64(); macc[k] += tn_ - mt; mt = tn_; } } while (0)
     const MatRec rec = d.mat[blockIdx.x];              // written by the beam step: no chain of look-ups to get started
     const int sid = rec.sid, sq = rec.sq, L = rec.L, my_dcal = rec.dcal;
     const uint64_t soff = rec.soff;
@@ -2155,7 +2082,6 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
         }
     }
     __syncthreads();
-    MSTAMP(0);   // header, productive-region list, combo digits
 
     // pass 1: sizes, and who creates what.  A child region is a function of (parent region, candidate, side) alone
     // (rafft/rafft.py:127-152, rafft/utils.py:141-152): the beam member whose compare-and-swap finds the slot empty creates it, everybody
@@ -2195,7 +2121,6 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
         }
         tot_nodes += nnod; tot_new += nnew; tot_pos += npos; tot_br += nbrr; tot_sp += nsp;
     }
-    MSTAMP(1);   // pass 1
     if (tid < 5) {
         // bump allocation from one of NSHARD sub-arenas (spreads the same-address atomics); one lane per arena
         const int shd = blockIdx.x & (NSHARD - 1);
@@ -2214,7 +2139,6 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
     __syncthreads();
     if (!shi[0]) { if (tid == 0) { d.st[sid].nnodes = 0; d.st[sid].node0 = 0; d.st[sid].sp = 0; d.st[sid].nsp = 0; } return; }
     const unsigned long long nbase = sh64[0], pbase = sh64[1], sbase = sh64[2], bbase = sh64[3], lbase = sh64[4];
-    MSTAMP(2);   // allocation
 
     // pass 2: per tile: descriptors -> LDS, prefix sums, node-list entries, records and flat copies of the regions created here
     int run_nodes = 0, run_new = 0, run_pos = 0, run_br = 0, run_sp = 0;
@@ -2274,17 +2198,12 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
             }
         }
         __syncthreads();
-        MSTAMP(4);   // pass 2 descriptors + records
         mat_copy_tile<MAT_NT, 4>(d, tid, 0, kt, ps, bs, ns, k_srcpos, k_srcbr, k_mi, k_mj, k_nb, k_lo0, k_loo, k_hio, k_newbr, tp, tb, ts,
                                  pbase + run_pos, bbase + run_br, sbase + run_sp, pmask);
         run_nodes += tn; run_new += tw; run_pos += tp; run_br += tb; run_sp += ts;
         __syncthreads();
-        MSTAMP(5);   // region copies
     }
     if (tid == 0) { d.st[sid].node0 = (int)lbase; d.st[sid].nnodes = tot_nodes; d.st[sid].sp = sbase; d.st[sid].nsp = tot_sp; }
-    MSTAMP(6);   // structure record
-    if (mprof) for (int k = 0; k < 7; k++) atomicAdd(&d.prof_e[k], macc[k]);
-#undef MSTAMP
 }
 
 // The same with TEAMS of 16 lanes: four new beam members per wavefront (round 4).  materialize_kernel is a chain of four dependent

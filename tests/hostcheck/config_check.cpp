@@ -16,10 +16,10 @@ int main()
     CHECK(same_config(d, read_config()));
     setenv("RAFFT_TRACE", "", 1);                 // set to anything: at least the summaries
     CHECK(read_config().trace == 1);
-    setenv("RAFFT_TRACE", "3", 1); setenv("RAFFT_SMALL", "8,24", 1); setenv("RAFFT_MERGE_SEQS", "4000", 1); setenv("RAFFT_TRACE_ALLOC", "0", 1);
+    setenv("RAFFT_TRACE", "2", 1); setenv("RAFFT_SMALL", "8,24", 1); setenv("RAFFT_MERGE_SEQS", "4000", 1); setenv("RAFFT_TRACE_ALLOC", "0", 1);
     setenv("RAFFT_PROD", "0", 1); setenv("RAFFT_SPLIT", "0", 1); setenv("RAFFT_BIG_WAVE_FRAC", "0.25", 1); setenv("RAFFT_SPANS", "2", 1);
     const Config e = read_config();
-    CHECK(e.trace == 3 && e.small_n4 == 8 && e.small_n5 == 24 && e.merge_seqs == 4000 && e.trace_alloc == 1 && e.prod == 0 && e.split == 0 && e.big_wave_frac == 0.25 && e.spans == 2);
+    CHECK(e.trace == 2 && e.small_n4 == 8 && e.small_n5 == 24 && e.merge_seqs == 4000 && e.trace_alloc == 1 && e.prod == 0 && e.split == 0 && e.big_wave_frac == 0.25 && e.spans == 2);
     CHECK(!same_config(d, e));
 #ifdef RAFFT_NO_TEST_HOOKS
     setenv("RAFFT_TEST_OVF_AT", "3", 1); setenv("RAFFT_EST", "2.5", 1); setenv("RAFFT_RL_CAP", "0", 1); setenv("RAFFT_SEEN_FIXED", "1", 1);
