@@ -978,7 +978,7 @@ int Wave::issue_materialize(unsigned nm)
     //  materialize_team_kernel; otherwise one structure per wavefront)
     if (d.max_prod <= MAT4_PROD)
         hipLaunchKernelGGL(materialize_team_kernel, dim3((nm + MAT4_TEAMS - 1) / MAT4_TEAMS), dim3(64), 0, st, d, (int)nm);
-    else hipLaunchKernelGGL(materialize_kernel, dim3(nm), dim3(MAT_NT), mat_lds, st, d);
+    else hipLaunchKernelGGL(materialize_kernel, dim3(nm), dim3(MAT_NT), mat_lds, st, d, (int)nm);
     HIPCHK(hipGetLastError());
     // tail of the batch: so few new structures that their regions fit one wave of workgroups of the widest class
     // (measured on the benchmark batch: 18.8 -> 17.3 ms; thresholds in new structures per step, per CU)

@@ -16,8 +16,8 @@
 //   beam_step_kernel    one workgroup per sequence: helix combination in product order, flat
 //                       over all parents of the beam, with `seen` dedupe and the max_branch
 //                       rule, stable energy sort and beam cut (rafft/rafft.py:176-214)
-//   materialize_kernel  one wavefront per new beam member: dot-bracket row + child
-//                       regions (rafft/rafft.py:127-152, rafft/utils.py:141-152)
+//   materialize_team_kernel / materialize_kernel  a team of 16 / 64 lanes per new beam member:
+//                       child regions (rafft/rafft.py:127-152, rafft/utils.py:141-152)
 //   dedupe_kernel       identical loops reached through different structures share one
 //                       expansion (no counterpart in the reference, which recomputes)
 //   output_kernel       gathers dot-bracket rows (rafft/utils.py:42-50)
@@ -1921,14 +1921,13 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
 
 // ------------------------------------------------------- materialize kernel
 
-#define MAT_NT 64
-// One wavefront per new beam member.  Child regions are spliced from the parent's
+// One team of lanes per new beam member.  Child regions are spliced from the parent's
 // regions: inner = positions/branches strictly inside the innermost stem pair, outer =
 // the rest of the parent's loop with the whole stem as one new branch.
 //
 // One lane describes one productive region of the parent (chosen stem, the branch indices it cuts the
 // loop at, sizes of the two child regions); the copies then run FLAT over all output elements of the
-// tile (binary search element -> child region), so every load of the wavefront is independent and in
+// tile (binary search element -> child region), so every load of the team is independent and in
 // flight at once instead of one dependent round trip per region.
 struct MatDesc {
     unsigned long long srcpos, srcbr, cidx;      // cidx: the candidate (its two child slots are cslot[2 cidx], cslot[2 cidx + 1])
@@ -2040,35 +2039,70 @@ __device__ __forceinline__ void mat_copy_tile(const Dev &d, int l, int kb, int k
 #ifndef RAFFT_MAT_WAVES
 #define RAFFT_MAT_WAVES 1
 #endif
-// (dynamic LDS: the productive-region lists only - a structure is stored as the pairs it adds to its parent's, no dot-bracket row is
-//  staged or written here; a latency-bound kernel of one-wavefront workgroups lives on the number of them a CU holds)
-__global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(Dev d)
+constexpr int MAT_NT = 64;              // materialize_kernel: one team of 64 lanes, the wavefront
+constexpr int MAT4_TL = 16;             // materialize_team_kernel: teams of 16 lanes ...
+constexpr int MAT4_TEAMS = 64 / MAT4_TL;
+constexpr int MAT4_PROD = 64;           // ... with productive-region lists of this many entries in static LDS
+
+// sums and inclusive scans over a team of TL lanes: DPP row scans for a team of 16 (one row), shuffles for the whole wavefront
+template <int TL>
+__device__ __forceinline__ int team_incl_scan(int x, int tl)
 {
-    extern __shared__ __align__(16) uint8_t mat_dyn[];
-    // dynamic LDS: the productive-region lists (d.max_prod entries each)
-    unsigned long long *prod_off = (unsigned long long *)mat_dyn;
-    int *prod_node = (int *)(prod_off + d.max_prod);
-    int *prod_cnt = prod_node + d.max_prod;
-    int *sel = prod_cnt + d.max_prod;
-    // per-tile descriptors (one lane per productive region) and the flat-copy prefix sums (two slots per region)
+    if constexpr (TL == 16) return row16_incl_scan(x);
+    else {
+        static_assert(TL == 64, "a team is one DPP row or the whole wavefront");
+        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (tl >= o) x += y; }
+        return x;
+    }
+}
+template <int TL>
+__device__ __forceinline__ int team_sum(int x)
+{
+    if constexpr (TL == 16) return __shfl(row16_incl_scan(x), TL - 1, TL);
+    else {
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        return x;
+    }
+}
+
+// One new beam member per team of TL lanes, 64 / TL of them per wavefront at a time (the reference's create_childs,
+// rafft/rafft.py:112-153).  The workgroup is one wavefront.  `prod_off` .. `sel`: my team's productive-region lists, `cap`
+// entries each.  A structure is stored as the pairs it adds to its parent's: no dot-bracket row is staged or written here.
+// (`d` by value, as the kernels get it: through a reference the compiler must assume that the stores below may alias its fields,
+//  and the team kernel came out with other code and SGPR spills)
+template <int TL>
+__device__ __forceinline__ void materialize_body(const Dev d, int n_mat, unsigned long long *prod_off, int *prod_node, int *prod_cnt,
+                                                 int *sel, int cap)
+{
+    constexpr int TEAMS = 64 / TL;
+    const int tid = threadIdx.x, team = tid / TL, tl = tid % TL;
+    // per-tile descriptors (one lane per productive region; index = lane of the wavefront) and the flat-copy prefix sums of every
+    // team (two slots per region)
     __shared__ unsigned long long k_srcpos[64], k_srcbr[64];
     __shared__ int k_mi[64], k_mj[64], k_nb[64], k_lo0[64], k_loo[64], k_hio[64], k_newbr[64];
-    __shared__ int ps[129], bs[129], ns[65];
-    __shared__ unsigned long long sh64[5];
-    __shared__ int shi[8];
-    const int tid = threadIdx.x;
-    const MatRec rec = d.mat[blockIdx.x];              // written by the beam step: no chain of look-ups to get started
+    __shared__ int ps_[TEAMS][2 * TL + 1], bs_[TEAMS][2 * TL + 1], ns_[TEAMS][TL + 1];
+    __shared__ unsigned long long sh64_[TEAMS][5];
+    int *ps = ps_[team], *bs = bs_[team], *ns = ns_[team];
+    const int tb = team * TL;                            // first lane of my team
+    const unsigned long long tmask = (~0ULL >> (64 - TL)) << tb;
+    if (d.c->overflow) return;                           // (see expand_kernel)
+    for (int mat_i0 = blockIdx.x * TEAMS; mat_i0 < n_mat; mat_i0 += gridDim.x * TEAMS) {
+    const int mat_i = mat_i0 + team;
+    const bool live = mat_i < n_mat;
+    MatRec rec;
+    rec.sid = 0; rec.sq = 0; rec.L = 0; rec.dcal = 0; rec.nprod = 0; rec.combo = 0; rec.prod = 0; rec.soff = 0;
+    if (live) rec = d.mat[mat_i];                        // written by the beam step: no chain of look-ups to get started
     const int sid = rec.sid, sq = rec.sq, L = rec.L, my_dcal = rec.dcal;
     const uint64_t soff = rec.soff;
     const int pmask = d.pos_packed ? 0x0FFF : 0xFFFF;
     int mprod = rec.nprod;
-    if (mprod > d.max_prod) mprod = d.max_prod;
+    if (mprod > cap) mprod = cap;
     {
         const ProdEnt *pl = d.prod + rec.prod;             // the parent's productive regions (beam_step prepass)
-        for (int k = tid; k < mprod; k += MAT_NT) { const ProdEnt pe = pl[k]; prod_node[k] = pe.node; prod_cnt[k] = (int)pe.cnt; prod_off[k] = pe.off; sel[k] = 0; }
+        for (int k = tl; k < mprod; k += TL) { const ProdEnt pe = pl[k]; prod_node[k] = pe.node; prod_cnt[k] = (int)pe.cnt; prod_off[k] = pe.off; sel[k] = 0; }
     }
-    __syncthreads();
-    if (tid == 0) {      // digits of the combo, last region fastest; high digits of a small index stay 0
+    wave_sync();
+    if (tl == 0) {       // digits of the combo, last region fastest; high digits of a small index stay 0
         unsigned long long idx = rec.combo;
         for (int k = mprod - 1; k >= 0 && idx; k--) {
             const unsigned int c = (unsigned int)prod_cnt[k];
@@ -2081,7 +2115,7 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
             } else { const unsigned long long q = idx / c; sel[k] = (int)(idx - q * c); idx = q; }
         }
     }
-    __syncthreads();
+    wave_sync();
 
     // pass 1: sizes, and who creates what.  A child region is a function of (parent region, candidate, side) alone
     // (rafft/rafft.py:127-152, rafft/utils.py:141-152): the beam member whose compare-and-swap finds the slot empty creates it, everybody
@@ -2089,16 +2123,16 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
     // list (the next beam step reads the region id out of the slot, once this kernel and dedupe_kernel are done: nobody reads a slot's
     // value in here).  Without memoization (min_nrj != 0: a region's filter depends on its parent's energy) every member creates its own.
     // (a single tile - the usual case - keeps its descriptors in registers for pass 2; with several the claims ride in sel[])
-    const int TILE = d.mat_tile;          // 64; smaller only in tests (several tiles per structure)
+    const int TILE = d.mat_tile < TL ? d.mat_tile : TL;       // d.mat_tile is 64; smaller only in tests (several tiles per structure)
     const bool one_tile = mprod <= TILE;
     const bool memo = d.memo != 0;
     MatDesc md;
     md.flags = 0; md.win = 0; md.nnod = 0; md.npos_in = md.npos_out = md.nbr_in = md.nbr_out = 0; md.nb = 0; md.cidx = 0;
     int tot_nodes = 0, tot_new = 0, tot_pos = 0, tot_br = 0, tot_sp = 0;
     for (int base = 0; base < mprod; base += TILE) {
-        const int k = base + tid;
+        const int k = base + tl;
         int nnod = 0, nnew = 0, npos = 0, nbrr = 0, nsp = 0;
-        if (k < mprod && tid < TILE) {
+        if (k < mprod && tl < TILE) {
             // the claim of both child slots of the chosen candidate: ONE returning atomic, issued before anything else is loaded (its
             // round trip runs beside those of the region header, the candidate and the positions).  A slot word is inner | outer << 32;
             // bit 31 of a half says "claimed", and whoever finds it clear has claimed that half.  (Claiming the half of a child that
@@ -2115,56 +2149,55 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
             npos = ((win & 1) ? md.npos_in : 0) + ((win & 2) ? md.npos_out : 0);
             nbrr = ((win & 1) ? md.nbr_in : 0) + ((win & 2) ? md.nbr_out : 0);
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            nnod += __shfl_xor(nnod, o, 64); nnew += __shfl_xor(nnew, o, 64); npos += __shfl_xor(npos, o, 64); nbrr += __shfl_xor(nbrr, o, 64);
-            nsp += __shfl_xor(nsp, o, 64);
-        }
+        nnod = team_sum<TL>(nnod); nnew = team_sum<TL>(nnew); npos = team_sum<TL>(npos); nbrr = team_sum<TL>(nbrr); nsp = team_sum<TL>(nsp);
         tot_nodes += nnod; tot_new += nnew; tot_pos += npos; tot_br += nbrr; tot_sp += nsp;
     }
-    if (tid < 5) {
+    bool ok = live;
+    if (tl < 5 && live) {
         // bump allocation from one of NSHARD sub-arenas (spreads the same-address atomics); one lane per arena
-        const int shd = blockIdx.x & (NSHARD - 1);
-        unsigned long long *ctr = tid == 0 ? &d.c->node[shd].v : tid == 1 ? &d.c->pos[shd].v : tid == 2 ? &d.c->sp[shd].v : tid == 3 ? &d.c->br[shd].v : &d.c->nlist[shd].v;
-        const unsigned long long want = tid == 0 ? (unsigned long long)tot_new : tid == 1 ? (unsigned long long)tot_pos
-                                      : tid == 2 ? (unsigned long long)tot_sp : tid == 3 ? (unsigned long long)tot_br : (unsigned long long)tot_nodes;
-        const unsigned long long cap = tid == 0 || tid == 4 ? d.nd_shard_cap : tid == 1 ? d.pos_shard_cap : tid == 2 ? d.sp_shard_cap : d.br_shard_cap;
+        const int shd = mat_i & (NSHARD - 1);
+        unsigned long long *ctr = tl == 0 ? &d.c->node[shd].v : tl == 1 ? &d.c->pos[shd].v : tl == 2 ? &d.c->sp[shd].v : tl == 3 ? &d.c->br[shd].v : &d.c->nlist[shd].v;
+        const unsigned long long want = tl == 0 ? (unsigned long long)tot_new : tl == 1 ? (unsigned long long)tot_pos
+                                      : tl == 2 ? (unsigned long long)tot_sp : tl == 3 ? (unsigned long long)tot_br : (unsigned long long)tot_nodes;
+        const unsigned long long cap = tl == 0 || tl == 4 ? d.nd_shard_cap : tl == 1 ? d.pos_shard_cap : tl == 2 ? d.sp_shard_cap : d.br_shard_cap;
         const unsigned long long b0 = want ? atomicAdd(ctr, want) : 0ULL;
         const bool bad = b0 + want > cap;
-        if (bad) atomicOr(&d.c->overflow, tid == 0 || tid == 4 ? OVF_NODE : tid == 1 ? OVF_POS : tid == 2 ? OVF_SP : OVF_BR);
-        const unsigned long long origin = tid == 0 || tid == 4 ? d.nd_base : tid == 1 ? d.pos_base : 0ULL;
-        sh64[tid] = origin + (unsigned long long)shd * cap + b0;
-        const unsigned long long anybad = __ballot(bad);
-        if (tid == 0) shi[0] = anybad ? 0 : 1;
+        if (bad) atomicOr(&d.c->overflow, tl == 0 || tl == 4 ? OVF_NODE : tl == 1 ? OVF_POS : tl == 2 ? OVF_SP : OVF_BR);
+        const unsigned long long origin = tl == 0 || tl == 4 ? d.nd_base : tl == 1 ? d.pos_base : 0ULL;
+        sh64_[team][tl] = origin + (unsigned long long)shd * cap + b0;
+        ok = !bad;
     }
-    __syncthreads();
-    if (!shi[0]) { if (tid == 0) { d.st[sid].nnodes = 0; d.st[sid].node0 = 0; d.st[sid].sp = 0; d.st[sid].nsp = 0; } return; }
-    const unsigned long long nbase = sh64[0], pbase = sh64[1], sbase = sh64[2], bbase = sh64[3], lbase = sh64[4];
+    // (every lane of the team learns whether all five allocations fit)
+    ok = ((__ballot(!ok) & tmask) == 0ULL) && live;
+    wave_sync();
+    if (!ok) { if (tl == 0 && live) { d.st[sid].nnodes = 0; d.st[sid].node0 = 0; d.st[sid].sp = 0; d.st[sid].nsp = 0; } }
+    const unsigned long long nbase = sh64_[team][0], pbase = sh64_[team][1], sbase = sh64_[team][2], bbase = sh64_[team][3], lbase = sh64_[team][4];
 
     // pass 2: per tile: descriptors -> LDS, prefix sums, node-list entries, records and flat copies of the regions created here
     int run_nodes = 0, run_new = 0, run_pos = 0, run_br = 0, run_sp = 0;
-    for (int base = 0; base < mprod; base += TILE) {
-        const int k = base + tid;
-        const int kt = mprod - base < TILE ? mprod - base : TILE;
+    const int mp2 = ok ? mprod : 0;
+    for (int base = 0; base < mp2; base += TILE) {
+        const int k = base + tl;
+        const int kt = mp2 - base < TILE ? mp2 - base : TILE;
         if (!one_tile) {
             md.flags = 0; md.win = 0; md.nnod = 0; md.npos_in = md.npos_out = md.nbr_in = md.nbr_out = 0; md.nb = 0;
-            if (k < mprod && tid < TILE) { md = mat_describe(d, prod_node[k], prod_off[k] + (unsigned long long)(sel[k] & 0x0FFFFFFF)); md.win = (sel[k] >> 28) & 3; }
+            if (k < mp2 && tl < TILE) { md = mat_describe(d, prod_node[k], prod_off[k] + (unsigned long long)(sel[k] & 0x0FFFFFFF)); md.win = (sel[k] >> 28) & 3; }
         }
-        const bool act = k < mprod && tid < TILE;
+        const bool act = k < mp2 && tl < TILE;
         const int cp_in = act && (md.win & 1) ? md.npos_in : 0, cp_out = act && (md.win & 2) ? md.npos_out : 0;
         const int cb_in = act && (md.win & 1) ? md.nbr_in : 0, cb_out = act && (md.win & 2) ? md.nbr_out : 0;
         // inclusive scans over the tile: node-list entries, regions created, their pos and branch elements, stem pairs
         int xn = act ? md.nnod : 0, xw = act ? (md.win & 1) + (md.win >> 1) : 0, xp = cp_in + cp_out, xb = cb_in + cb_out, xs = act ? md.nb : 0;
         const int vn = xn, vw = xw, vp = xp, vb = xb, vs = xs;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int yn = __shfl_up(xn, o, 64), yw = __shfl_up(xw, o, 64), yp = __shfl_up(xp, o, 64), yb = __shfl_up(xb, o, 64), ys = __shfl_up(xs, o, 64);
-            if (tid >= o) { xn += yn; xw += yw; xp += yp; xb += yb; xs += ys; }
-        }
-        const int tn = __shfl(xn, 63, 64), tw = __shfl(xw, 63, 64), tp = __shfl(xp, 63, 64), tb = __shfl(xb, 63, 64), ts = __shfl(xs, 63, 64);
+        xn = team_incl_scan<TL>(xn, tl); xw = team_incl_scan<TL>(xw, tl); xp = team_incl_scan<TL>(xp, tl); xb = team_incl_scan<TL>(xb, tl);
+        xs = team_incl_scan<TL>(xs, tl);
+        const int tn = __shfl(xn, TL - 1, TL), tw = __shfl(xw, TL - 1, TL), tp = __shfl(xp, TL - 1, TL), tbr = __shfl(xb, TL - 1, TL),
+                  ts = __shfl(xs, TL - 1, TL);
         const int p0 = xp - vp, b0 = xb - vb;          // exclusive
-        ps[2 * tid] = p0; ps[2 * tid + 1] = p0 + cp_in;
-        bs[2 * tid] = b0; bs[2 * tid + 1] = b0 + cb_in;
-        ns[tid] = xs - vs;
-        if (tid == 0) { ps[128] = tp; bs[128] = tb; ns[64] = ts; }
+        ps[2 * tl] = p0; ps[2 * tl + 1] = p0 + cp_in;
+        bs[2 * tl] = b0; bs[2 * tl + 1] = b0 + cb_in;
+        ns[tl] = xs - vs;
+        if (tl == 0) { ps[2 * TL] = tp; bs[2 * TL] = tbr; ns[TL] = ts; }
         if (act) {
             k_srcpos[tid] = md.srcpos; k_srcbr[tid] = md.srcbr;
             k_mi[tid] = md.mi; k_mj[tid] = md.mj; k_nb[tid] = md.nb; k_lo0[tid] = md.lo0; k_loo[tid] = md.loo; k_hio[tid] = md.hio;
@@ -2197,188 +2230,40 @@ __global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(De
                 } else d.nlist[le] = -(slot0 + 2);
             }
         }
-        __syncthreads();
-        mat_copy_tile<MAT_NT, 4>(d, tid, 0, kt, ps, bs, ns, k_srcpos, k_srcbr, k_mi, k_mj, k_nb, k_lo0, k_loo, k_hio, k_newbr, tp, tb, ts,
-                                 pbase + run_pos, bbase + run_br, sbase + run_sp, pmask);
-        run_nodes += tn; run_new += tw; run_pos += tp; run_br += tb; run_sp += ts;
-        __syncthreads();
-    }
-    if (tid == 0) { d.st[sid].node0 = (int)lbase; d.st[sid].nnodes = tot_nodes; d.st[sid].sp = sbase; d.st[sid].nsp = tot_sp; }
-}
-
-// The same with TEAMS of 16 lanes: four new beam members per wavefront (round 4).  materialize_kernel is a chain of four dependent
-// round trips per structure (record -> parent's lists -> slot claim / region headers / candidates -> stem positions and
-// arena allocation -> writes) in which a lane stands for one productive region of the parent - three to five of them on the benchmark
-// set - so a wavefront per structure keeps 60 lanes idle through the chain, and what a CU holds of such wavefronts (20, by registers)
-// bounds the structures in flight.  With four structures per wavefront the same CU holds four times as many.  Used when the
-// productive-region lists are the short ones (max_prod <= MAT4_PROD; host: Wave::after_beam); identical results -
-// the arenas are bump allocated, so only the PLACES of records and lists differ from the one-structure form.
-#define MAT4_TL 16
-#define MAT4_TEAMS (64 / MAT4_TL)
-#define MAT4_PROD 64
-__global__ __launch_bounds__(64, RAFFT_MAT_WAVES) void materialize_team_kernel(Dev d, int n_mat)
-{
-    const int tid = threadIdx.x, team = tid / MAT4_TL, tl = tid % MAT4_TL;
-    // LDS per team: the productive-region lists (MAT4_PROD entries each)
-    __shared__ unsigned long long prod_off_[MAT4_TEAMS][MAT4_PROD];
-    __shared__ int prod_node_[MAT4_TEAMS][MAT4_PROD], prod_cnt_[MAT4_TEAMS][MAT4_PROD], sel_[MAT4_TEAMS][MAT4_PROD];
-    unsigned long long *prod_off = prod_off_[team];
-    int *prod_node = prod_node_[team], *prod_cnt = prod_cnt_[team], *sel = sel_[team];
-    // per-tile descriptors (one lane per productive region; index = lane of the wavefront) and the flat-copy prefix sums of every team
-    __shared__ unsigned long long k_srcpos[64], k_srcbr[64];
-    __shared__ int k_mi[64], k_mj[64], k_nb[64], k_lo0[64], k_loo[64], k_hio[64], k_newbr[64];
-    __shared__ int ps_[MAT4_TEAMS][2 * MAT4_TL + 1], bs_[MAT4_TEAMS][2 * MAT4_TL + 1], ns_[MAT4_TEAMS][MAT4_TL + 1];
-    __shared__ unsigned long long sh64_[MAT4_TEAMS][5];
-    int *ps = ps_[team], *bs = bs_[team], *ns = ns_[team];
-    const int tb = team * MAT4_TL;                       // first lane of my team
-    const unsigned long long tmask = ((1ULL << MAT4_TL) - 1ULL) << tb;
-    if (d.c->overflow) return;                           // (see expand_kernel)
-    for (int mat_i0 = blockIdx.x * MAT4_TEAMS; mat_i0 < n_mat; mat_i0 += gridDim.x * MAT4_TEAMS) {
-    const int mat_i = mat_i0 + team;
-    const bool live = mat_i < n_mat;
-    MatRec rec;
-    rec.sid = 0; rec.sq = 0; rec.L = 0; rec.dcal = 0; rec.nprod = 0; rec.combo = 0; rec.prod = 0; rec.soff = 0;
-    if (live) rec = d.mat[mat_i];
-    const int sid = rec.sid, sq = rec.sq, L = rec.L, my_dcal = rec.dcal;
-    const uint64_t soff = rec.soff;
-    const int pmask = d.pos_packed ? 0x0FFF : 0xFFFF;
-    int mprod = rec.nprod;
-    if (mprod > MAT4_PROD) mprod = MAT4_PROD;
-    {
-        const ProdEnt *pl = d.prod + rec.prod;             // the parent's productive regions (beam_step prepass)
-        for (int k = tl; k < mprod; k += MAT4_TL) { const ProdEnt pe = pl[k]; prod_node[k] = pe.node; prod_cnt[k] = (int)pe.cnt; prod_off[k] = pe.off; sel[k] = 0; }
-    }
-    wave_sync();
-    if (tl == 0) {       // digits of the combo, last region fastest; high digits of a small index stay 0
-        unsigned long long idx = rec.combo;
-        for (int k = mprod - 1; k >= 0 && idx; k--) {
-            const unsigned int c = (unsigned int)prod_cnt[k];
-            if (idx < (1ULL << 24)) {
-                const unsigned int v = (unsigned int)idx;
-                unsigned int q = (unsigned int)((float)v * __frcp_rn((float)c));       // off by one at most
-                int r = (int)(v - q * c);
-                if (r < 0) { q--; r += (int)c; } else if (r >= (int)c) { q++; r -= (int)c; }
-                sel[k] = r; idx = q;
-            } else { const unsigned long long q = idx / c; sel[k] = (int)(idx - q * c); idx = q; }
-        }
-    }
-    wave_sync();
-    // pass 1: sizes and slot claims (see materialize_kernel)
-    const int TILE = d.mat_tile < MAT4_TL ? d.mat_tile : MAT4_TL;
-    const bool one_tile = mprod <= TILE;
-    const bool memo = d.memo != 0;
-    MatDesc md;
-    md.flags = 0; md.win = 0; md.nnod = 0; md.npos_in = md.npos_out = md.nbr_in = md.nbr_out = 0; md.nb = 0; md.cidx = 0;
-    int tot_nodes = 0, tot_new = 0, tot_pos = 0, tot_br = 0, tot_sp = 0;
-    for (int base = 0; base < mprod; base += TILE) {
-        const int k = base + tl;
-        int nnod = 0, nnew = 0, npos = 0, nbrr = 0, nsp = 0;
-        if (k < mprod && tl < TILE) {
-            const unsigned long long cidx = prod_off[k] + (unsigned long long)sel[k];
-            unsigned long long old = 0;
-            if (memo) old = atomicOr(&d.cslot[cidx], 0x8000000080000000ULL);
-            md = mat_describe(d, prod_node[k], cidx);
-            int win = md.flags;
-            if (memo) win &= ((old >> 31) & 1ULL ? 0 : 1) | ((old >> 63) & 1ULL ? 0 : 2);
-            md.win = win;
-            if (!one_tile) sel[k] |= win << 28;
-            nnod = md.nnod; nnew = (win & 1) + (win >> 1); nsp = md.nb;
-            npos = ((win & 1) ? md.npos_in : 0) + ((win & 2) ? md.npos_out : 0);
-            nbrr = ((win & 1) ? md.nbr_in : 0) + ((win & 2) ? md.nbr_out : 0);
-        }
-        // (round 5: sums over the team - a row of 16 lanes - by DPP row scans and one read of the row's last lane each, instead of four
-        //  rounds of five __shfl_xor through the LDS crossbar)
-        static_assert(MAT4_TL == 16, "a team is one DPP row");
-        nnod = __shfl(row16_incl_scan(nnod), MAT4_TL - 1, MAT4_TL); nnew = __shfl(row16_incl_scan(nnew), MAT4_TL - 1, MAT4_TL);
-        npos = __shfl(row16_incl_scan(npos), MAT4_TL - 1, MAT4_TL); nbrr = __shfl(row16_incl_scan(nbrr), MAT4_TL - 1, MAT4_TL);
-        nsp = __shfl(row16_incl_scan(nsp), MAT4_TL - 1, MAT4_TL);
-        tot_nodes += nnod; tot_new += nnew; tot_pos += npos; tot_br += nbrr; tot_sp += nsp;
-    }
-    bool ok = live;
-    if (tl < 5 && live) {
-        // bump allocation from one of NSHARD sub-arenas; one lane per arena
-        const int shd = mat_i & (NSHARD - 1);
-        unsigned long long *ctr = tl == 0 ? &d.c->node[shd].v : tl == 1 ? &d.c->pos[shd].v : tl == 2 ? &d.c->sp[shd].v : tl == 3 ? &d.c->br[shd].v : &d.c->nlist[shd].v;
-        const unsigned long long want = tl == 0 ? (unsigned long long)tot_new : tl == 1 ? (unsigned long long)tot_pos
-                                      : tl == 2 ? (unsigned long long)tot_sp : tl == 3 ? (unsigned long long)tot_br : (unsigned long long)tot_nodes;
-        const unsigned long long cap = tl == 0 || tl == 4 ? d.nd_shard_cap : tl == 1 ? d.pos_shard_cap : tl == 2 ? d.sp_shard_cap : d.br_shard_cap;
-        const unsigned long long b0 = want ? atomicAdd(ctr, want) : 0ULL;
-        const bool bad = b0 + want > cap;
-        if (bad) atomicOr(&d.c->overflow, tl == 0 || tl == 4 ? OVF_NODE : tl == 1 ? OVF_POS : tl == 2 ? OVF_SP : OVF_BR);
-        const unsigned long long origin = tl == 0 || tl == 4 ? d.nd_base : tl == 1 ? d.pos_base : 0ULL;
-        sh64_[team][tl] = origin + (unsigned long long)shd * cap + b0;
-        ok = !bad;
-    }
-    // (every lane of the team learns whether all five allocations fit)
-    ok = ((__ballot(!ok) & tmask) == 0ULL) && live;
-    wave_sync();
-    if (!ok) { if (tl == 0 && live) { d.st[sid].nnodes = 0; d.st[sid].node0 = 0; d.st[sid].sp = 0; d.st[sid].nsp = 0; } }
-    const unsigned long long nbase = sh64_[team][0], pbase = sh64_[team][1], sbase = sh64_[team][2], bbase = sh64_[team][3], lbase = sh64_[team][4];
-
-    // pass 2: per tile: descriptors -> LDS, prefix sums, node-list entries, records and flat copies of the regions created here
-    int run_nodes = 0, run_new = 0, run_pos = 0, run_br = 0, run_sp = 0;
-    const int mp2 = ok ? mprod : 0;
-    for (int base = 0; base < mp2; base += TILE) {
-        const int k = base + tl;
-        const int kt = mp2 - base < TILE ? mp2 - base : TILE;
-        if (!one_tile) {
-            md.flags = 0; md.win = 0; md.nnod = 0; md.npos_in = md.npos_out = md.nbr_in = md.nbr_out = 0; md.nb = 0;
-            if (k < mp2 && tl < TILE) { md = mat_describe(d, prod_node[k], prod_off[k] + (unsigned long long)(sel[k] & 0x0FFFFFFF)); md.win = (sel[k] >> 28) & 3; }
-        }
-        const bool act = k < mp2 && tl < TILE;
-        const int cp_in = act && (md.win & 1) ? md.npos_in : 0, cp_out = act && (md.win & 2) ? md.npos_out : 0;
-        const int cb_in = act && (md.win & 1) ? md.nbr_in : 0, cb_out = act && (md.win & 2) ? md.nbr_out : 0;
-        int xn = act ? md.nnod : 0, xw = act ? (md.win & 1) + (md.win >> 1) : 0, xp = cp_in + cp_out, xb = cb_in + cb_out, xs = act ? md.nb : 0;
-        const int vn = xn, vw = xw, vp = xp, vb = xb, vs = xs;
-        xn = row16_incl_scan(xn); xw = row16_incl_scan(xw); xp = row16_incl_scan(xp); xb = row16_incl_scan(xb); xs = row16_incl_scan(xs);
-        const int tn = __shfl(xn, MAT4_TL - 1, MAT4_TL), tw = __shfl(xw, MAT4_TL - 1, MAT4_TL), tp = __shfl(xp, MAT4_TL - 1, MAT4_TL),
-                  tbr = __shfl(xb, MAT4_TL - 1, MAT4_TL), ts = __shfl(xs, MAT4_TL - 1, MAT4_TL);
-        const int p0 = xp - vp, b0 = xb - vb;          // exclusive
-        ps[2 * tl] = p0; ps[2 * tl + 1] = p0 + cp_in;
-        bs[2 * tl] = b0; bs[2 * tl + 1] = b0 + cb_in;
-        ns[tl] = xs - vs;
-        if (tl == 0) { ps[2 * MAT4_TL] = tp; bs[2 * MAT4_TL] = tbr; ns[MAT4_TL] = ts; }
-        if (act) {
-            k_srcpos[tid] = md.srcpos; k_srcbr[tid] = md.srcbr;
-            k_mi[tid] = md.mi; k_mj[tid] = md.mj; k_nb[tid] = md.nb; k_lo0[tid] = md.lo0; k_loo[tid] = md.loo; k_hio[tid] = md.hio;
-            k_newbr[tid] = (int)md.newbr;
-            int nid = (int)(nbase + run_new + (xw - vw));
-            unsigned long long le = lbase + run_nodes + (xn - vn);
-            const unsigned long long poff = pbase + run_pos + p0, boff = bbase + run_br + b0;
-            const int slot0 = (int)(2 * md.cidx);
-            if (md.flags & 1) {
-                if (md.win & 1) {
-                    d.nd[nid].seq = sq; d.nd[nid].pdcal = my_dcal; d.nd[nid].pos = poff; d.nd[nid].n = md.npos_in;
-                    d.nd[nid].L = L; d.nd[nid].soff = soff;
-                    d.nd[nid].ci = md.a0; d.nd[nid].cj = md.b0; d.nd[nid].br = boff; d.nd[nid].nbr = md.nbr_in;
-                    d.nd[nid].ncand = -1; d.nd[nid].cand = 0;
-                    if (memo) { d.nd_slot[nid] = (uint32_t)slot0; ((uint32_t *)d.cslot)[slot0] = (uint32_t)(nid + 1) | 0x80000000u; }
-                    d.nlist[le] = memo ? -(slot0 + 1) : nid;
-                    nid++;
-                } else d.nlist[le] = -(slot0 + 1);
-                le++;
-            }
-            if (md.flags & 2) {
-                if (md.win & 2) {
-                    d.nd[nid].seq = sq; d.nd[nid].pdcal = my_dcal; d.nd[nid].pos = poff + cp_in; d.nd[nid].n = md.npos_out;
-                    d.nd[nid].L = L; d.nd[nid].soff = soff;
-                    d.nd[nid].ci = md.ci; d.nd[nid].cj = md.cj; d.nd[nid].br = boff + cb_in; d.nd[nid].nbr = md.nbr_out;
-                    d.nd[nid].ncand = -1; d.nd[nid].cand = 0;
-                    if (memo) { d.nd_slot[nid] = (uint32_t)(slot0 + 1); ((uint32_t *)d.cslot)[slot0 + 1] = (uint32_t)(nid + 1) | 0x80000000u; }
-                    d.nlist[le] = memo ? -(slot0 + 2) : nid;
-                } else d.nlist[le] = -(slot0 + 2);
-            }
-        }
         wave_sync();
         // (descriptor kk of my team sits at lane tb + kk)
-        mat_copy_tile<MAT4_TL, 4>(d, tl, tb, kt, ps, bs, ns, k_srcpos, k_srcbr, k_mi, k_mj, k_nb, k_lo0, k_loo, k_hio, k_newbr, tp, tbr, ts,
-                                  pbase + run_pos, bbase + run_br, sbase + run_sp, pmask);
+        mat_copy_tile<TL, 4>(d, tl, tb, kt, ps, bs, ns, k_srcpos, k_srcbr, k_mi, k_mj, k_nb, k_lo0, k_loo, k_hio, k_newbr, tp, tbr, ts,
+                             pbase + run_pos, bbase + run_br, sbase + run_sp, pmask);
         run_nodes += tn; run_new += tw; run_pos += tp; run_br += tbr; run_sp += ts;
         wave_sync();
     }
     if (ok && tl == 0) { d.st[sid].node0 = (int)lbase; d.st[sid].nnodes = tot_nodes; d.st[sid].sp = sbase; d.st[sid].nsp = tot_sp; }
     wave_sync();
     }
+}
+
+// One new beam member per wavefront, its lists in dynamic LDS (d.max_prod entries each, up to MAX_PROD_LONG).  Host: the long
+// lists - sequences longer than LDS_SEQ, or a wave folded again after a structure had more productive regions than MAX_PROD.
+__global__ __launch_bounds__(MAT_NT, RAFFT_MAT_WAVES) void materialize_kernel(Dev d, int n_mat)
+{
+    extern __shared__ __align__(16) uint8_t mat_dyn[];
+    unsigned long long *prod_off = (unsigned long long *)mat_dyn;
+    int *prod_node = (int *)(prod_off + d.max_prod);
+    int *prod_cnt = prod_node + d.max_prod;
+    int *sel = prod_cnt + d.max_prod;
+    materialize_body<MAT_NT>(d, n_mat, prod_off, prod_node, prod_cnt, sel, d.max_prod);
+}
+
+// Four new beam members per wavefront, teams of 16 lanes (round 4: a lane stands for one productive region of the parent - three to
+// five of them on the benchmark set - so a wavefront per structure keeps most lanes idle through its chain of dependent round trips,
+// and what a CU holds of such wavefronts bounds the structures in flight).  Host: the short lists (d.max_prod <= MAT4_PROD).
+// Identical results: the arenas are bump allocated, so only the PLACES of records and lists differ from the one-structure form.
+__global__ __launch_bounds__(64, RAFFT_MAT_WAVES) void materialize_team_kernel(Dev d, int n_mat)
+{
+    __shared__ unsigned long long prod_off_[MAT4_TEAMS][MAT4_PROD];
+    __shared__ int prod_node_[MAT4_TEAMS][MAT4_PROD], prod_cnt_[MAT4_TEAMS][MAT4_PROD], sel_[MAT4_TEAMS][MAT4_PROD];
+    const int team = threadIdx.x / MAT4_TL;
+    materialize_body<MAT4_TL>(d, n_mat, prod_off_[team], prod_node_[team], prod_cnt_[team], sel_[team], MAT4_PROD);
 }
 
 // ------------------------------------------------------------ dedupe kernel
