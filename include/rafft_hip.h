@@ -213,6 +213,33 @@ int rafft_get_stats(rafft_stats *out);
 int rafft_kin_rate_matrix(int n_steps, const int *step_size, int L, const char *rows, const int *uid, int n_unique,
                           const double *energy, double kt, double *rate_device);
 
+/* Folding landscape of a fast-folding graph.  Replaces the arithmetic of utility/surface.py; the drawing
+ * stays in Python.  All matrices live in DEVICE memory of the caller (HIP pointers, e.g. a torch tensor's data_ptr); the
+ * caller's own stream must be done with them.  Same input, same bits: every floating-point sum has a fixed order.
+ *
+ * rafft_landscape_distances - get_distance_matrix, surface.py:19-26.  `rows` = n dot-bracket rows of L bytes back to back
+ * (host; the unique structures of the graph, surface.py:29-40).  Output: the n x n base-pair distances, row-major 16-bit
+ * unsigned, zero diagonal: |A| + |B| - 2 |A n B|, the number of pairs in exactly one of the two structures (at most L).
+ * RAFFT_ERR_STRUCT for a malformed row, RAFFT_ERR_PARAM for n < 1 or L > 32767. */
+int rafft_landscape_distances(int n, int L, const char *rows, uint16_t *dist_device);
+/* rafft_landscape_mds - manifold.MDS(n_components=2, dissimilarity="precomputed").fit_transform, surface.py:98-101: metric
+ * SMACOF as sklearn.manifold._mds._smacof_single runs it (unnormalised stress), for n_init independent starts at once.
+ * x_init (host): n_init initial configurations of n x 2 doubles - the caller draws them, so the call is a deterministic
+ * function of its inputs.  A start stops after the first iteration >= 2 whose relative stress decrease is below eps, or
+ * after max_iter; the decision is taken on the device, the host looks at it every 64 iterations.  Output: x_device
+ * (n_init x n x 2 doubles, device), stress_out / n_iter_out (host, per start).  Two components only. */
+int rafft_landscape_mds(int n, const uint16_t *dist_device, int n_init, const double *x_init, int max_iter, double eps,
+                        double *x_device, double *stress_out, int *n_iter_out);
+/* rafft_landscape_surface - interpolate.Rbf(x, y, e, function="thin_plate") and its evaluation on meshgrid(ti, ti),
+ * ti = linspace(lo, hi, grid), surface.py:107-111; phi(r) = r^2 log r, phi(0) = 0.  x_device: n x 2 positions.
+ * phi_device != NULL: the n x n system matrix phi(||X_i - X_j||) is written there (solve it for the weights with the dense
+ * solver of your choice).  z_device != NULL: z[gy][gx] = sum_k w_device[k] phi(||(ti[gx], ti[gy]) - X_k||), grid x grid
+ * doubles.  Either may be NULL. */
+int rafft_landscape_surface(int n, const double *x_device, const double *w_device, int grid, double lo, double hi,
+                            double *z_device, double *phi_device);
+/* out[0..3] = MDS calls, SMACOF passes enqueued, host read-backs of the per-start `done` words, passes of the last call */
+int rafft_landscape_counters(long long out[4]);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

@@ -30,6 +30,7 @@
 // templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
+#include "rafft_landscape.hip"
 
 namespace {
 
@@ -2243,6 +2244,141 @@ int rafft_kin_rate_matrix(int n_steps, const int *step_size, int L, const char *
 #undef KCHK
     cleanup();
     if (bad) return fail(RAFFT_ERR_STRUCT, "malformed dot-bracket row");
+    return 0;
+}
+
+// ---- folding landscape (kernels in rafft_landscape.hip)
+
+static long long g_landscape_counters[4];      // MDS calls, SMACOF passes enqueued, host read-backs of the `done` words, passes of the last call
+#define LANDSCAPE_CHUNK 64                     // SMACOF passes enqueued between two read-backs
+
+int rafft_landscape_distances(int n, int L, const char *rows, uint16_t *dist_device)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!rows || !dist_device || n < 1 || L < 1 || L > 32767) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (int rc = init_ctx(-1)) return rc;
+    drain();
+    std::lock_guard<std::mutex> ws_lk(g.ws_mu);
+    if (int rc = init_ws(g.ws[0])) return rc;
+    hipStream_t st = g.ws[0].stream;
+    const int Lp = (L + LS_CHUNK - 1) / LS_CHUNK * LS_CHUNK;
+    void *d_rows = nullptr, *d_pt = nullptr, *d_stack = nullptr, *d_open = nullptr, *d_np = nullptr, *d_bad = nullptr;
+    auto cleanup = [&]() { for (void *q : {d_rows, d_pt, d_stack, d_open, d_np, d_bad}) if (q) { hipError_t fe = hipFree(q); (void)fe; } };
+#define KCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(RAFFT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
+    KCHK(hipMalloc(&d_rows, (size_t)n * L)); KCHK(hipMalloc(&d_pt, (size_t)n * L * 2)); KCHK(hipMalloc(&d_stack, (size_t)n * L * 2));
+    KCHK(hipMalloc(&d_open, (size_t)n * Lp * 2)); KCHK(hipMalloc(&d_np, (size_t)n * 4)); KCHK(hipMalloc(&d_bad, 4));
+    KCHK(hipMemcpyAsync(d_rows, rows, (size_t)n * L, hipMemcpyHostToDevice, st));
+    KCHK(hipMemsetAsync(d_bad, 0, 4, st));
+    hipLaunchKernelGGL(kin_pair_table_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, L, (const char *)d_rows,
+                       (int16_t *)d_pt, (int16_t *)d_stack, (int *)d_bad);
+    KCHK(hipGetLastError());
+    int bad = 0;
+    KCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    KCHK(hipStreamSynchronize(st));
+    if (bad) { cleanup(); return fail(RAFFT_ERR_STRUCT, "malformed dot-bracket row"); }
+    hipLaunchKernelGGL(landscape_open_table_kernel, dim3((unsigned)n), dim3(64), 0, st, n, L, Lp, (const int16_t *)d_pt, (uint16_t *)d_open, (int *)d_np);
+    KCHK(hipGetLastError());
+    const unsigned T = (unsigned)((n + LS_TILE - 1) / LS_TILE);
+    if (T > 65535) { cleanup(); return fail(RAFFT_ERR_PARAM, "too many structures"); }
+    hipLaunchKernelGGL(landscape_distance_kernel, dim3(T, T), dim3(256), 0, st, n, Lp, (const uint16_t *)d_open, (const int *)d_np, dist_device);
+    KCHK(hipGetLastError());
+    KCHK(hipStreamSynchronize(st));
+    cleanup();
+    return 0;
+}
+
+int rafft_landscape_mds(int n, const uint16_t *dist_device, int n_init, const double *x_init, int max_iter, double eps,
+                        double *x_device, double *stress_out, int *n_iter_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!dist_device || !x_init || !x_device || !stress_out || !n_iter_out || n < 1 || n_init < 1 || n_init > 65535 || max_iter < 1 || !(eps == eps))
+        return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (int rc = init_ctx(-1)) return rc;
+    drain();
+    std::lock_guard<std::mutex> ws_lk(g.ws_mu);
+    if (int rc = init_ws(g.ws[0])) return rc;
+    hipStream_t st = g.ws[0].stream;
+    void *d_x = nullptr, *d_rs = nullptr, *d_state = nullptr;
+    auto cleanup = [&]() { for (void *q : {d_x, d_rs, d_state}) if (q) { hipError_t fe = hipFree(q); (void)fe; } };
+    const size_t per = (size_t)n * 2 * sizeof(double);            // one configuration
+    KCHK(hipMalloc(&d_x, per * 2 * n_init)); KCHK(hipMalloc(&d_rs, per * n_init)); KCHK(hipMalloc(&d_state, sizeof(LandscapeMdsState) * n_init));
+    KCHK(hipMemsetAsync(d_state, 0, sizeof(LandscapeMdsState) * n_init, st));
+    for (int k = 0; k < n_init; k++)                               // X_0 of start k -> its buffer 0
+        KCHK(hipMemcpyAsync((char *)d_x + per * 2 * k, x_init + (size_t)k * n * 2, per, hipMemcpyHostToDevice, st));
+    // X in LDS up to 128 KiB (8192 points, one workgroup per CU); beyond that it is read through the caches
+    const size_t lds = (size_t)n * 16;
+    const bool xlds = lds <= ((size_t)128 << 10);
+    static bool lds_attr_set = false;
+    if (xlds && !lds_attr_set) {
+        KCHK(hipFuncSetAttribute((const void *)landscape_smacof_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 << 10));
+        lds_attr_set = true;
+    }
+    const int rows_per_wg = LS_SM_NT / 64;
+    int gx = (n + rows_per_wg - 1) / rows_per_wg;
+    const int cap = g.n_cu / n_init > 0 ? g.n_cu / n_init : 1;    // one workgroup per CU over all starts when X fills the LDS
+    if (gx > cap) gx = cap;
+    std::vector<LandscapeMdsState> hs(n_init);
+    g_landscape_counters[0]++;
+    g_landscape_counters[3] = 0;
+    bool all_done = false;
+    for (int pass = 0; pass <= max_iter && !all_done; ) {
+        const int stop = pass + LANDSCAPE_CHUNK < max_iter + 1 ? pass + LANDSCAPE_CHUNK : max_iter + 1;
+        for (; pass < stop; pass++) {
+            const int guttman = pass < max_iter;
+            if (xlds)
+                hipLaunchKernelGGL(landscape_smacof_kernel<true>, dim3((unsigned)gx, (unsigned)n_init), dim3(LS_SM_NT), lds, st, n, dist_device, (double *)d_x,
+                                   (double *)d_rs, (const LandscapeMdsState *)d_state, pass, guttman);
+            else
+                hipLaunchKernelGGL(landscape_smacof_kernel<false>, dim3((unsigned)gx, (unsigned)n_init), dim3(LS_SM_NT), 0, st, n, dist_device, (double *)d_x,
+                                   (double *)d_rs, (const LandscapeMdsState *)d_state, pass, guttman);
+            hipLaunchKernelGGL(landscape_smacof_finalize_kernel, dim3((unsigned)n_init), dim3(256), 0, st, n, (const double *)d_x, (const double *)d_rs,
+                               (LandscapeMdsState *)d_state, pass, max_iter, eps, x_device);
+            g_landscape_counters[1]++; g_landscape_counters[3]++;
+        }
+        KCHK(hipGetLastError());
+        KCHK(hipMemcpyAsync(hs.data(), d_state, sizeof(LandscapeMdsState) * n_init, hipMemcpyDeviceToHost, st));
+        KCHK(hipStreamSynchronize(st));
+        g_landscape_counters[2]++;
+        all_done = true;
+        for (int k = 0; k < n_init; k++) all_done = all_done && hs[k].done;
+    }
+    cleanup();
+    if (!all_done) return fail(RAFFT_ERR_HIP, "internal: SMACOF did not finish within max_iter + 1 passes");
+    for (int k = 0; k < n_init; k++) { stress_out[k] = hs[k].stress; n_iter_out[k] = hs[k].n_iter; }
+    return 0;
+}
+
+int rafft_landscape_surface(int n, const double *x_device, const double *w_device, int grid, double lo, double hi, double *z_device,
+                            double *phi_device)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!x_device || n < 1 || (!z_device && !phi_device) || (z_device && (!w_device || grid < 1 || grid > 32768 || !(lo <= hi))))
+        return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (int rc = init_ctx(-1)) return rc;
+    drain();
+    std::lock_guard<std::mutex> ws_lk(g.ws_mu);
+    if (int rc = init_ws(g.ws[0])) return rc;
+    hipStream_t st = g.ws[0].stream;
+    if (phi_device) {
+        if (n > 65535) return fail(RAFFT_ERR_PARAM, "too many structures");
+        hipLaunchKernelGGL(landscape_tps_fill_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, st, n, x_device, phi_device);
+        HIPCHK(hipGetLastError());
+    }
+    if (z_device) {
+        const long long pts = (long long)grid * grid;
+        hipLaunchKernelGGL(landscape_tps_kernel, dim3((unsigned)((pts + 255) / 256)), dim3(256), 0, st, n, x_device, w_device, grid, lo, hi, z_device);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+#undef KCHK
+
+int rafft_landscape_counters(long long out[4])
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = g_landscape_counters[k];
     return 0;
 }
 
