@@ -240,6 +240,46 @@ int rafft_landscape_surface(int n, const double *x_device, const double *w_devic
 /* out[0..3] = MDS calls, SMACOF passes enqueued, host read-backs of the per-start `done` words, passes of the last call */
 int rafft_landscape_counters(long long out[4]);
 
+/* Accuracy of predicted structures against known ones.  Both entry points replace test_one_seq,
+ * benchmark_results/scoring.py:76-94: one RNAstructure `scorer` process per structure of a beam (PPV and sensitivity with one
+ * position of slip: a pair (i,j) is found when the other structure holds (i,j), (i+-1,j) or (i,j+-1)), then the last structure
+ * that reaches the highest PPV (`>=`), or the first structure with --one.  Integer counts come back; the caller forms
+ * PPV = 100 hit_pred / n_pred and sensitivity = 100 hit_known / n_known (0 when the denominator is 0, scoring.py:70-72), and
+ * ViennaRNA's bp_distance to the known structure is n_pred + n_known - 2 n_exact. */
+typedef struct {
+    int32_t n_pred;      /* pairs of the predicted row */
+    int32_t hit_pred;    /* ... found in the known structure */
+    int32_t hit_known;   /* pairs of the known structure found in the predicted row */
+    int32_t n_exact;     /* pairs in both, no slip */
+    int32_t status;      /* RAFFT_ERR_STRUCT: the row holds something else than ( ) . or is unbalanced (counts are 0) */
+} rafft_score_row;       /* 20 bytes */
+
+typedef struct {
+    int32_t status;      /* RAFFT_ERR_STRUCT: malformed known structure or one of another length than the sequence (see
+                            rafft_last_error() for the position); rafft_score_result: the fold's status when it failed */
+    int32_t n_known;     /* pairs of the known structure */
+    int32_t n_rows;
+    int32_t row0;        /* index of the sequence's first record in row_out */
+    int32_t pick_ppv;    /* last row with the highest PPV among the rows that parsed (PPVs compared as integer fractions, a row
+                            without pairs counts as 0; a beam without any hit picks its last row); -1 when there is none */
+    int32_t pick_first;  /* 0 (--one), or -1 for a sequence without rows */
+    rafft_score_row best;    /* the record of row pick_ppv */
+    rafft_score_row first;   /* the record of row 0 */
+} rafft_score_seq;       /* 64 bytes */
+
+/* rows[s]: the n_rows[s] dot-bracket rows of sequence s, lens[s] characters each (( ) . only), row_stride[s] bytes apart
+ * (lens[s] for rows back to back, lens[s] + 1 for rafft_seq_result.db).  known[s]: the known structure, NUL terminated, lens[s]
+ * characters of ( ) < > [ ] . read as rafft/utils.py:53-67 reads them (two stacks: ( and < share one, [ has its own).
+ * row_out (may be NULL): one record per row, sequence after sequence in input order; seq_out: one record per sequence.
+ * A malformed row or known structure is an error of that row / sequence only: the call still returns RAFFT_OK.
+ * RAFFT_ERR_PARAM: n_seq < 0, a length above 32767, a negative count, a stride below the length. */
+int rafft_score_rows(int n_seq, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                     const char *const *known, rafft_score_row *row_out, rafft_score_seq *seq_out);
+/* The same for the final beam of every sequence of a fold result, read where the fold left it (the result's pinned rows go
+ * to the device as they lie, no repacking).  known[s] as above, one per sequence of `r`.  A sequence whose fold failed keeps
+ * that status and has no rows.  row_out (may be NULL) holds the sum of the final beams' sizes. */
+int rafft_score_result(const rafft_result *r, const char *const *known, rafft_score_row *row_out, rafft_score_seq *seq_out);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

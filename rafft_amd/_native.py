@@ -46,7 +46,8 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
            "rafft_param_value", "rafft_kin_rate_matrix", "rafft_shutdown", "rafft_alloc_counters", "rafft_eval_structures_info", "rafft_params_unpinned",
-           "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters"]
+           "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
+           "rafft_score_rows", "rafft_score_result"]
 
 _lib = None
 
@@ -127,6 +128,9 @@ def lib():
                                       C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.rafft_landscape_surface.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     L.rafft_landscape_counters.argtypes = [C.POINTER(C.c_longlong * 4)]
+    L.rafft_score_rows.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
+    L.rafft_score_result.argtypes = [C.POINTER(Result), C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -39,6 +39,14 @@ _OPTIONS = [
                                                   "benchmark_cleaned_all_length.csv has `seq`).  With --bench this replaces the process pool of\n"
                                                   "benchmark_results/bench_fft.py")),
     (("--csv_column",), dict(default="seq", help="sequence column of a CSV given to -sf --batch (default: seq)")),
+    (("--scores",), dict(metavar="OUT.csv", help="with -sf CSV --batch: score the final beam of every sequence against its known structure on the\n"
+                                                 "GPU (PPV / sensitivity as RNAstructure's scorer, one position of slip) and write the table of\n"
+                                                 "benchmark_results/scoring.py: seq,len_seq,struct,nrj,nbp,pvv,sens,name.  The CSV has a header\n"
+                                                 "(columns by name) or is the reference's headerless seq,struct,name file")),
+    (("--select",), dict(choices=("ppv", "energy"), default="ppv", help="structure reported by --scores: the last one of the beam that reaches the\n"
+                                                                        "highest PPV (scoring.py), or the first one (scoring.py --one)")),
+    (("--known_column",), dict(default="struct", help="known-structure column of a CSV with a header (default: struct)")),
+    (("--name_column",), dict(default="name", help="name column of a CSV with a header (default: name)")),
     (("--output", "-o"), dict(help="write the result there instead of stdout")),
     (("--sidecar",), dict(help="with --traj: also write the fast-folding graph as a binary side-car (exact dcal energies,\n"
                                "no strings to re-parse) that `rafft_kin --sidecar` reads; with several sequences the\n"
@@ -53,21 +61,38 @@ def parse_arguments(argv=None):
     return parser.parse_args(argv)
 
 
-def read_sequences(args):
+_SEQ_LETTERS = frozenset("ACGUTN")
+_DB_LETTERS = frozenset("().<>[]")
+
+
+def read_records(args):
+    """(sequences, known structures or None, names or None) of the input.  Known structures and names exist for a CSV only:
+    with a header line the columns --csv_column / --known_column / --name_column, without one the reference's three columns
+    seq,struct,name (benchmark_cleaned_all_length.csv, read by read_true_struct, benchmark_results/scoring.py:31-36).  A first
+    line is data, not a header, when its first field consists of the upper-case sequence letters only and its second field is a
+    dot-bracket string of the same length."""
     assert args.sequence is not None or args.seq_file is not None, "error, the sequence is missing!"
     if args.sequence is not None:
-        return [args.sequence]
+        return [args.sequence], None, None
     lines = [l.strip() for l in open(args.seq_file)]
     if not args.batch:   # reference behaviour: all non-header lines joined (bin/rafft:42)
-        return ["".join(l for l in lines if not l.startswith(">")).replace("T", "U")]
+        return ["".join(l for l in lines if not l.startswith(">")).replace("T", "U")], None, None
     seqs, cur = [], []
-    if lines and "," in lines[0] and not lines[0].startswith(">"):     # CSV with a header line
+    if lines and "," in lines[0] and not lines[0].startswith(">"):     # CSV
         import csv
+        first = [f.strip() for f in lines[0].split(",")]
         with open(args.seq_file, newline="") as fh:
+            if first[0] and set(first[0]) <= _SEQ_LETTERS and set(first[1]) <= _DB_LETTERS and len(first[1]) == len(first[0]):   # no header line: seq,struct,name
+                rows = [r for r in csv.reader(fh) if r and r[0].strip()]
+                col = lambda k: [r[k].strip() for r in rows] if all(len(r) > k for r in rows) else None
+                return [r[0].strip().replace("T", "U") for r in rows], col(1), col(2)
             rd = csv.DictReader(fh)
             if args.csv_column not in (rd.fieldnames or []):
                 raise SystemExit(f"{args.seq_file}: no column {args.csv_column!r} (columns: {rd.fieldnames})")
-            return [r[args.csv_column].strip().replace("T", "U") for r in rd if r[args.csv_column].strip()]
+            rows = [r for r in rd if r[args.csv_column].strip()]
+            col = lambda name: [(r[name] or "").strip() for r in rows] if name in rd.fieldnames else None
+            return ([r[args.csv_column].strip().replace("T", "U") for r in rows],
+                    col(getattr(args, "known_column", "struct")), col(getattr(args, "name_column", "name")))
     fasta = any(l.startswith(">") for l in lines)
     for l in lines:
         if fasta:
@@ -81,7 +106,40 @@ def read_sequences(args):
             seqs.append(l)
     if cur:
         seqs.append("".join(cur))
-    return [s.replace("T", "U") for s in seqs]
+    return [s.replace("T", "U") for s in seqs], None, None
+
+
+def read_sequences(args):
+    return read_records(args)[0]
+
+
+def write_scores(path, seqs, names, results, table, select="ppv", traj=False):
+    """The reference's score table (benchmark_results/scoring.py:120-128): header `seq,len_seq,struct,nrj,nbp,pvv,sens,name`, one
+    line per sequence - the last structure of the final beam that reaches the highest PPV (select="ppv", scoring.py:90-91) or the
+    first one (select="energy", `--one`).  `table`: what scoring.score_batch_gpu returns."""
+    import numpy as np
+    from .utils import energies_from_dcal
+    pick = np.asarray(table["pick_ppv" if select == "ppv" else "pick_first"])
+    row0, n_known = np.asarray(table["row0"]), np.asarray(table["n_known"])
+    with open(path, "w") as out:
+        out.write("seq,len_seq,struct,nrj,nbp,pvv,sens,name\n")
+        for k, s in enumerate(seqs):
+            status = int(table["seq_status"][k])
+            if status or pick[k] < 0:
+                raise SystemExit(f"--scores: sequence {k} ({names[k]}): no scored structure (status {status})")
+            raw = results.raw(k) if hasattr(results, "raw") else None
+            if raw is not None:
+                L, sizes, rows, dcal = raw
+                at = len(rows) - sizes[-1] + int(pick[k])
+                struct, nrj = rows[at].tobytes().decode("ascii"), float(energies_from_dcal(dcal[at:at + 1])[0])
+            else:
+                st = (results[k][0] if traj else results[k])[int(pick[k])]
+                struct, nrj = st.str_struct, st.energy
+            r = int(row0[k] + pick[k])
+            n_pred, hit_pred, hit_known = int(table["n_pred"][r]), int(table["hit_pred"][r]), int(table["hit_known"][r])
+            ppv = 100.0 * hit_pred / n_pred if n_pred else 0.0
+            sens = 100.0 * hit_known / int(n_known[k]) if n_known[k] else 0.0
+            out.write(f"{s},{len(s)},{struct},{nrj},{struct.count('(')},{round(ppv, 2)},{round(sens, 2)},{names[k]}\n")
 
 
 def format_result(sequence, result, args):
@@ -118,13 +176,27 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None):
+def main(argv=None, fold_batch=None, scorer=None):
+    """`fold_batch` / `scorer`: injection points for tests (the fold, and the callable (results, known) -> score table that
+    stands in for scoring.score_batch_gpu)."""
     args = parse_arguments(argv)
-    seqs = read_sequences(args)
+    seqs, known, names = read_records(args)
+    if args.scores:
+        if not args.batch or known is None:
+            raise SystemExit("--scores needs -sf CSV --batch with a known structure per sequence "
+                             f"(column {args.known_column!r}, or the headerless seq,struct,name file)")
+        names = names if names is not None else [""] * len(seqs)
     if fold_batch is None:
         from .rafft import fold_batch
     results = fold_batch(seqs, args.n_mode, args.max_stack, args.max_branch, args.min_hp, args.min_nrj, args.traj,
                          args.temp, args.gc_wei, args.au_wei, args.gu_wei)
+    if args.scores:
+        if scorer is None:
+            from .scoring import score_batch_gpu as scorer
+        write_scores(args.scores, seqs, names, results, scorer(results, known), args.select, args.traj)
+        if not args.output:          # the table is the output; the structures are written as well when -o names a file
+            _table_note()
+            return
     out = open(args.output, "wb") if args.output else sys.stdout.buffer if hasattr(sys.stdout, "buffer") else None
     try:
         for k, s in enumerate(seqs):

@@ -31,6 +31,7 @@
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
 #include "rafft_landscape.hip"
+#include "rafft_score.hip"
 
 namespace {
 
@@ -2380,6 +2381,221 @@ int rafft_landscape_counters(long long out[4])
     if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
     for (int k = 0; k < 4; k++) out[k] = g_landscape_counters[k];
     return 0;
+}
+
+// ---- accuracy scoring (kernels in rafft_score.hip)
+
+// device buffers of the scoring calls: grow-only and kept for the life of the process (a call on a warm library allocates nothing).
+// Unlike the workspaces they are not trimmed when the library idles: after the biggest call so far they hold its rows, its row
+// records and, for sequences beyond the LDS plans, up to 1024 workgroups' scratch (tens of MB at the benchmark's sizes).
+static struct { Buf rows, known, seqs, items, row_out, seq_out, scratch; } g_score;
+
+// the known structure's table as rafft/utils.py:53-67 pairs it: ( and < share a stack, [ has its own; 1-based partners, 0 = unpaired
+static bool score_known_table(const char *db, int L, uint16_t *t, int *n_known, std::string &err)
+{
+    const size_t n = strlen(db);
+    if (n != (size_t)L) { err = "known structure of length " + std::to_string(n) + " for a sequence of length " + std::to_string(L); return false; }
+    std::vector<int> reg, pk;
+    int pairs = 0;
+    for (int i = 0; i < L; i++) {
+        const char c = db[i];
+        t[i] = 0;
+        if (c == '(' || c == '<') reg.push_back(i);
+        else if (c == '[') pk.push_back(i);
+        else if (c == ')' || c == '>' || c == ']') {
+            std::vector<int> &stk = c == ']' ? pk : reg;
+            if (stk.empty()) { err = std::string("known structure: unmatched '") + c + "' at position " + std::to_string(i); return false; }
+            const int j = stk.back(); stk.pop_back();
+            t[i] = (uint16_t)(j + 1); t[j] = (uint16_t)(i + 1);
+            pairs++;
+        } else if (c != '.') { err = std::string("known structure: character '") + c + "' at position " + std::to_string(i); return false; }
+    }
+    if (!reg.empty() || !pk.empty()) { err = "known structure: unclosed bracket at position " + std::to_string(!reg.empty() ? reg.back() : pk.back()); return false; }
+    *n_known = pairs;
+    return true;
+}
+
+struct ScoreSrc { const char *base; size_t bytes; size_t dev_off; };      // a host range of rows that goes to the device as it lies
+
+// rows_off[s]: where sequence s's first row lies in the device copy of `src`; pre_status[s] != 0: the sequence is not scored
+static int score_impl(int n_seq, const int *lens, const int *n_rows, const int *stride, const unsigned long long *rows_off, const int *pre_status,
+                      const std::vector<ScoreSrc> &src, size_t rows_bytes, const char *const *known, rafft_score_row *row_out, rafft_score_seq *seq_out)
+{
+    std::lock_guard<std::mutex> ws_lk(g.ws_mu);
+    if (int rc = init_ws(g.ws[0])) return rc;
+    hipStream_t st = g.ws[0].stream;
+    std::vector<ScoreSeq> seqs(n_seq);
+    std::vector<uint16_t> ktab;
+    std::vector<ScoreItem> items[3];
+    int Lc[3] = {2, 2, 2};
+    long long total_rows = 0;
+    std::string first_err;
+    for (int s = 0; s < n_seq; s++) {
+        ScoreSeq &q = seqs[s];
+        q = ScoreSeq{};
+        q.rows_off = rows_off[s]; q.L = lens[s]; q.n_rows = n_rows[s]; q.stride = stride[s]; q.row0 = (int)total_rows;
+        q.status = pre_status ? pre_status[s] : 0;
+        total_rows += n_rows[s];
+        if (total_rows > 0x7fffffff) return fail(RAFFT_ERR_PARAM, "too many rows");
+        if (q.status) continue;
+        const size_t o = ktab.size();
+        if (o + (size_t)q.L > 0xffffffffull) return fail(RAFFT_ERR_PARAM, "known structures too long in total");
+        ktab.resize(o + (size_t)q.L);
+        std::string err;
+        if (!score_known_table(known[s], q.L, ktab.data() + o, &q.n_known, err)) {
+            ktab.resize(o);
+            q.status = RAFFT_ERR_STRUCT; q.n_known = 0;
+            if (first_err.empty()) first_err = "sequence " + std::to_string(s) + ": " + err;
+            continue;
+        }
+        q.known_off = (unsigned)o;
+        const int cls = q.L <= SC_L_SMALL ? 0 : q.L <= SC_L_LDS ? 1 : 2;
+        Lc[cls] = std::max(Lc[cls], (q.L + 1) & ~1);
+        for (int r0 = 0; r0 < q.n_rows; r0 += SC_ROWS) items[cls].push_back(ScoreItem{s, r0, std::min(r0 + SC_ROWS, q.n_rows)});
+    }
+    if (n_seq == 0) return 0;
+    std::vector<ScoreItem> all;
+    size_t item0[3];
+    for (int c = 0; c < 3; c++) { item0[c] = all.size(); all.insert(all.end(), items[c].begin(), items[c].end()); }
+    const unsigned grid2 = (unsigned)std::min<size_t>(items[2].size(), 1024);
+    const size_t scratch_bytes = (size_t)grid2 * SC_WAVES * (size_t)(Lc[2] + Lc[2] / 2) * 2;
+    if (int rc = ensure(g_score.rows, rows_bytes + 64)) return rc;
+    if (int rc = ensure(g_score.known, ktab.size() * 2 + 64)) return rc;
+    if (int rc = ensure(g_score.seqs, seqs.size() * sizeof(ScoreSeq))) return rc;
+    if (int rc = ensure(g_score.items, all.size() * sizeof(ScoreItem) + 64)) return rc;
+    if (int rc = ensure(g_score.row_out, (size_t)total_rows * sizeof(rafft_score_row) + 64)) return rc;
+    if (int rc = ensure(g_score.seq_out, seqs.size() * sizeof(rafft_score_seq))) return rc;
+    if (int rc = ensure(g_score.scratch, scratch_bytes + 64)) return rc;
+    for (const ScoreSrc &x : src)
+        if (x.bytes) HIPCHK(hipMemcpyAsync((char *)g_score.rows.p + x.dev_off, x.base, x.bytes, hipMemcpyHostToDevice, st));
+    if (!ktab.empty()) HIPCHK(hipMemcpyAsync(g_score.known.p, ktab.data(), ktab.size() * 2, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(g_score.seqs.p, seqs.data(), seqs.size() * sizeof(ScoreSeq), hipMemcpyHostToDevice, st));
+    if (!all.empty()) HIPCHK(hipMemcpyAsync(g_score.items.p, all.data(), all.size() * sizeof(ScoreItem), hipMemcpyHostToDevice, st));
+    if (total_rows) HIPCHK(hipMemsetAsync(g_score.row_out.p, 0, (size_t)total_rows * sizeof(rafft_score_row), st));
+    for (int c = 0; c < 3; c++) {
+        if (items[c].empty()) continue;
+        const ScoreItem *it = (const ScoreItem *)g_score.items.p + item0[c];
+        if (c < 2)
+            hipLaunchKernelGGL(score_rows_kernel<true>, dim3((unsigned)std::min<size_t>(items[c].size(), (size_t)1 << 20)), dim3(SC_NT), (size_t)14 * Lc[c], st,
+                               (int)items[c].size(), it, (const ScoreSeq *)g_score.seqs.p, (const char *)g_score.rows.p, (const uint16_t *)g_score.known.p, Lc[c],
+                               (uint16_t *)nullptr, (rafft_score_row *)g_score.row_out.p);
+        else
+            hipLaunchKernelGGL(score_rows_kernel<false>, dim3(grid2), dim3(SC_NT), 0, st,
+                               (int)items[c].size(), it, (const ScoreSeq *)g_score.seqs.p, (const char *)g_score.rows.p, (const uint16_t *)g_score.known.p, Lc[c],
+                               (uint16_t *)g_score.scratch.p, (rafft_score_row *)g_score.row_out.p);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(score_pick_kernel, dim3((unsigned)((n_seq + SC_WAVES - 1) / SC_WAVES)), dim3(SC_NT), 0, st, n_seq, (const ScoreSeq *)g_score.seqs.p,
+                       (const rafft_score_row *)g_score.row_out.p, (rafft_score_seq *)g_score.seq_out.p);
+    HIPCHK(hipGetLastError());
+    if (row_out && total_rows) HIPCHK(hipMemcpyAsync(row_out, g_score.row_out.p, (size_t)total_rows * sizeof(rafft_score_row), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(seq_out, g_score.seq_out.p, seqs.size() * sizeof(rafft_score_seq), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (row_out)
+        for (int s = 0; s < n_seq; s++)
+            if (seqs[s].status)
+                for (int r = 0; r < seqs[s].n_rows; r++) row_out[(size_t)seqs[s].row0 + r].status = seqs[s].status;
+    g_err = first_err;
+    return 0;
+}
+
+// rows of every sequence packed into one host buffer (strides kept): rows that lie anywhere in pageable memory
+static void score_pack(int n_seq, const int *lens, const int *n_rows, const char *const *rows, const int *stride, const int *pre_status,
+                       std::vector<char> &pack, std::vector<unsigned long long> &rows_off)
+{
+    size_t tot = 0;
+    for (int s = 0; s < n_seq; s++) {
+        rows_off[s] = tot;
+        if (n_rows[s] && !(pre_status && pre_status[s])) tot += (size_t)(n_rows[s] - 1) * stride[s] + lens[s];
+    }
+    pack.resize(tot);
+    for (int s = 0; s < n_seq; s++) {
+        const size_t end = s + 1 < n_seq ? rows_off[s + 1] : tot;
+        if (end > rows_off[s]) memcpy(pack.data() + rows_off[s], rows[s], end - rows_off[s]);
+    }
+}
+
+int rafft_score_rows(int n_seq, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                     const char *const *known, rafft_score_row *row_out, rafft_score_seq *seq_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || (n_seq > 0 && (!lens || !n_rows || !rows || !row_stride || !known || !seq_out))) return fail(RAFFT_ERR_PARAM, "bad argument");
+    for (int s = 0; s < n_seq; s++) {
+        if (lens[s] < 0 || lens[s] > 32767) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": length outside 0..32767");
+        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": negative number of rows");
+        if (row_stride[s] < lens[s]) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": row stride below the length");
+        if (!known[s] || (n_rows[s] && !rows[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    }
+    if (int rc = init_ctx(-1)) return rc;
+    drain();
+    std::vector<char> pack;
+    std::vector<unsigned long long> rows_off(n_seq);
+    score_pack(n_seq, lens, n_rows, rows, row_stride, nullptr, pack, rows_off);
+    std::vector<ScoreSrc> src{ScoreSrc{pack.data(), pack.size(), 0}};
+    return score_impl(n_seq, lens, n_rows, row_stride, rows_off.data(), nullptr, src, pack.size(), known, row_out, seq_out);
+}
+
+int rafft_score_result(const rafft_result *r, const char *const *known, rafft_score_row *row_out, rafft_score_seq *seq_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!r || r->n_seq < 0 || (r->n_seq > 0 && (!r->seq || !known || !seq_out))) return fail(RAFFT_ERR_PARAM, "bad argument");
+    const int n_seq = r->n_seq;
+    std::vector<int> lens(n_seq), n_rows(n_seq), stride(n_seq), pre(n_seq);
+    std::vector<const char *> rows(n_seq);
+    for (int s = 0; s < n_seq; s++) {
+        const rafft_seq_result &sr = r->seq[s];
+        pre[s] = sr.status;
+        if (sr.status) { lens[s] = n_rows[s] = stride[s] = 0; rows[s] = nullptr; continue; }
+        if (sr.length < 0 || sr.length > 32767) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": length outside 0..32767");
+        if (!known[s]) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+        const int last = sr.n_steps - 1;
+        lens[s] = sr.length; stride[s] = sr.length + 1;
+        n_rows[s] = last >= 0 ? sr.step_size[last] : 0;
+        rows[s] = n_rows[s] ? sr.db + (size_t)sr.step_off[last] * (size_t)(sr.length + 1) : nullptr;
+    }
+    if (int rc = init_ctx(-1)) return rc;
+    drain();
+    // the rows lie in the pinned chunks the fold's copies landed in: per chunk, the range the final beams span goes up as one copy
+    const HostOut *ho = (const HostOut *)r->_owner;
+    std::vector<unsigned long long> rows_off(n_seq, 0);
+    std::vector<ScoreSrc> src;
+    std::vector<char> pack;
+    size_t rows_bytes = 0;
+    bool in_chunks = ho != nullptr;
+    if (in_chunks) {
+        const size_t nc = ho->chunks.size();
+        std::vector<const char *> lo(nc, nullptr), hi(nc, nullptr);
+        std::vector<int> chunk_of(n_seq, -1);
+        for (int s = 0; s < n_seq && in_chunks; s++) {
+            if (!n_rows[s]) continue;
+            const char *a = rows[s], *b = a + (size_t)(n_rows[s] - 1) * stride[s] + lens[s];
+            for (size_t c = 0; c < nc; c++) {
+                const char *cb = (const char *)ho->chunks[c]->b.p;
+                if (a >= cb && b <= cb + ho->chunks[c]->b.cap) { chunk_of[s] = (int)c; break; }
+            }
+            if (chunk_of[s] < 0) { in_chunks = false; break; }
+            const int c = chunk_of[s];
+            if (!lo[c] || a < lo[c]) lo[c] = a;
+            if (!hi[c] || b > hi[c]) hi[c] = b;
+        }
+        if (in_chunks) {
+            std::vector<size_t> dev_off(nc, 0);
+            for (size_t c = 0; c < nc; c++) {
+                if (!lo[c]) continue;
+                dev_off[c] = rows_bytes;
+                src.push_back(ScoreSrc{lo[c], (size_t)(hi[c] - lo[c]), rows_bytes});
+                rows_bytes += ((size_t)(hi[c] - lo[c]) + 255) & ~(size_t)255;
+            }
+            for (int s = 0; s < n_seq; s++)
+                if (chunk_of[s] >= 0) rows_off[s] = dev_off[chunk_of[s]] + (size_t)(rows[s] - lo[chunk_of[s]]);
+        }
+    }
+    if (!in_chunks) {       // a result that was not made by this library's fold
+        score_pack(n_seq, lens.data(), n_rows.data(), rows.data(), stride.data(), pre.data(), pack, rows_off);
+        src.assign(1, ScoreSrc{pack.data(), pack.size(), 0});
+        rows_bytes = pack.size();
+    }
+    return score_impl(n_seq, lens.data(), n_rows.data(), stride.data(), rows_off.data(), pre.data(), src, rows_bytes, known, row_out, seq_out);
 }
 
 } // extern "C"
