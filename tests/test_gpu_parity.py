@@ -378,7 +378,7 @@ def test_gpu_long_stems_vs_oracle():
 
 
 def test_gpu_seen_tables_sized_from_the_length_and_grown(monkeypatch):
-    """round 5: a sequence's `seen` set starts in a table sized from its length (seen_slots0, rafft_api.hip) so that the benchmark set
+    """round 5: a sequence's `seen` set starts in a table sized from its length (seen_slots0, rafft_plan.h) so that the benchmark set
     folds without a rehash; a set that outgrows its table is still rehashed into one of twice the size inside beam_step_kernel.  Both
     sides: random sequences of 60-900 nt with the default tables, with fixed 8192-slot tables (RAFFT_SEEN_FIXED=1: everything beyond
     ~200 nt grows once or twice) and at max_stack 150 (three times the children per step the sizing was measured at) - same beams, and
