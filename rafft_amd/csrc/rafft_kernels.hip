@@ -652,7 +652,11 @@ __global__ __launch_bounds__(NT * WPB, (NT == 64 ? (WPB == 16 ? 4 : RAFFT_EXPAND
                     double nGU = 2.0 * (double)rintf(z2[k].x * invP);
                     double raw = nAU * d.au + nGC * d.gc + nGU * d.gu;
                     int nk = k < m - 1 - k ? k : m - 1 - k;
-                    v = raw / ((double)nk + 1.0);
+                    // (+ 0.0: a lag without a pair comes out of the FFT as +-1e-7 and rintf keeps the sign - three counts of -0.0f made
+                    //  the value -0.0, which the bit-pattern keys of the ranking put BELOW the +0.0 of the other empty lags, where the
+                    //  reference's exact 0.0 ties with them and the larger lag wins.  Seen on a 65-nt CUG repeat, whose top 100 reach into
+                    //  the empty lags: tests/test_gpu_ties.py.  -0.0 + 0.0 = +0.0; every other value is unchanged.)
+                    v = raw / ((double)nk + 1.0) + 0.0;
                 }
                 keyv[k] = v;
                 tally(v, k < m);

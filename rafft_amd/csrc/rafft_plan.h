@@ -48,7 +48,12 @@ int class_cfg(const Config &cfg, int K, int maxL, ClsCfg out[NGEN + 1], bool nof
         ExpandLds l = expand_lds(P[c], LM[c], nmax, BR[c], Kmax, TAB[c], WPB[c], nf, NT[c], c != 0);      // (class 0: no LDS copy of the base codes - expand_kernel's CODE_LDS)
         // region A is time-shared: behind the fp64 lag values (8 P bytes) it must still hold the branch prefix sums
         // (10 bytes per branch), the select histogram and the window_slide scratch of this class
-        if (c == 0 && longseq && (8 * MASK_WORDS * (big_n / 64) + 24 * 8 * std::max(Kmax, 1) + 4096 > 16 * P[c] || 10 * (BR[c] + 1) + 16 + 24 * Kmax + 2048 > 16 * P[c]))
+        // (the partial results of chunked diagonals: C chunks per ranked lag, C = min(8, NT / lags) - 512 records of 24 bytes
+        //  at the most until there are more lags than threads, not 8 per lag: that bound refused nb_mode 214-399 on sequences
+        //  of 4097-16384 nt, which the message below and DESIGN.md 5 promise - tests/test_gpu_ties.py asks for 399 at 4097 nt.
+        //  The plan for 32 768 positions keeps the bound of 8 per lag it has been tested with: nb_mode <= 106.)
+        const int ws_parts = maxL > 16384 ? 8 * std::max(Kmax, 1) : std::max(std::min(8 * std::max(Kmax, 1), NT[c]), Kmax);
+        if (c == 0 && longseq && (8 * MASK_WORDS * (big_n / 64) + 24 * ws_parts + 4096 > 16 * P[c] || 10 * (BR[c] + 1) + 16 + 24 * Kmax + 2048 > 16 * P[c]))
             return fail(RAFFT_ERR_PARAM, std::string("nb_mode too large for the LDS scratch of the class for regions beyond 4096 positions: with a sequence of ") +
                                          (maxL > 16384 ? "more than 16384 nt it must stay at or below 106" : "more than 4096 nt it must stay below ~400") +
                                          " (this wave: nb_mode " + std::to_string(K) + ", longest sequence " + std::to_string(maxL) + " nt)");

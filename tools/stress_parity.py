@@ -1,5 +1,9 @@
 """One-off stress run: random sequences (incl. low-complexity ones with many ties) x random parameters, GPU
-trajectories against the CPU oracle.  Both expand routings (RAFFT_MERGE_*)."""
+trajectories against the CPU oracle.  Both expand routings (RAFFT_MERGE_*).
+
+The low-complexity cases now live in the suite: tests/test_ties.py and tests/test_gpu_ties.py run repeat families (GC, AU, GU,
+CUG, tandem hairpins) through every expand class and the beam step, against fixtures made by the reference's own Python
+(tools/make_golden_ties.py).  This script remains for random parameter mixes by hand."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
