@@ -29,8 +29,9 @@
 #include <vector>
 #include <pthread.h>
 
-// kernels (rafft_kernels.hip is compiled into the same translation unit so the
-// templates and the Dev struct are shared without a device-link step)
+// kernels (rafft_kernels.hip - the shared device helpers, which in turn includes one file per fold kernel: rafft_expand.hip,
+// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip - is compiled into the same translation
+// unit so the templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
 #include "rafft_landscape.hip"

@@ -368,22 +368,7 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
                         } else
                             rank += ky < kx ? 1 : 0;
                     }
-                    const int mi = w_mi[s], mj = w_mj[s], nb = w_nb[s];
-                    const int a0 = pos[mi], b0 = pos[mj], ao = pos[mi - nb + 1], bo = pos[mj + nb - 1];
-                    uint64_t h1 = 0, h2 = 0;
-                    if (a0 - ao == nb - 1 && bo - b0 == nb - 1) stem_hash(a0, b0, ao, bo, &h1, &h2);      // contiguous: the pair hashes telescope
-                    else
-                        for (int t = 0; t < nb; t++) {
-                            uint64_t a, b;
-                            pair_hash(pos[mi - t], pos[mj + t], &a, &b);
-                            h1 += a; h2 += b;
-                        }
-                    Cand cd;
-                    cd.ddcal = w_dd[s]; cd.mi = (uint16_t)mi; cd.mj = (uint16_t)mj; cd.nb = (uint16_t)nb;
-                    { int c0, c1, c2, c3; br_lower4(brl, nbr, a0, b0, ao, bo, c0, c1, c2, c3); cd.set_cuts(c0, c1, c2, c3); }
-                    cd.h1 = h1; cd.h2 = h2;
-                    d.cand[cbase + toff + rank] = cd;
-                    d.cslot[cbase + toff + rank] = 0ULL;      // (both child slots: nobody has asked yet)
+                    emit_cand(d, brl, nbr, pos, w_mi[s], w_mj[s], w_nb[s], w_dd[s], cbase + toff + rank);
                     if (dbg && d.dbg.kept) d.dbg.kept[rank] = w_rank[s];
                 }
         }
@@ -403,14 +388,7 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
     }
     if (lane == 0 && st_items) {
         Counters::StatLine *sl = &d.c->xstat[cls][gw & (NSHARD - 1)];
-        atomicAdd(&sl->items, st_items);
-        atomicAdd(&sl->n, st_n);
-        atomicAdd(&sl->lags, st_lags);
-        atomicAdd(&sl->nbr, st_nbr);
-        if (T->lsb && st_eval) {          // (built-in tables: stem energies evaluated / involving a rule or model value / kept ones that do)
-            atomicAdd(&sl->evals, (unsigned long long)st_eval);
-            if (st_guess) atomicAdd(&sl->guessed, (unsigned long long)st_guess);
-            if (st_kguess) atomicAdd(&sl->kept_guessed, (unsigned long long)st_kguess);
-        }
+        flush_stats(sl, st_items, st_n, st_lags, st_nbr);
+        if (T->lsb && st_eval) flush_guess_stats(sl, st_eval, st_guess, st_kguess);      // (built-in tables)
     }
 }
