@@ -306,7 +306,7 @@ static int eval_structures_impl(int n, const char *const *seqs, const char *cons
     HIPCHK(hipMemcpy(dcal_out, dout, n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(st2.data(), dst, n * 4, hipMemcpyDeviceToHost));
     if (guessed_out) HIPCHK(hipMemcpy(guessed_out, dg, n * 4, hipMemcpyDeviceToHost));
-    if (guessed_out) for (int i = 0; i < n; i++) if (status[i]) guessed_out[i] = 0;
+    if (guessed_out) for (int i = 0; i < n; i++) if (status[i] || st2[i]) guessed_out[i] = 0;      // (a row with an error has no energy to qualify)
     int worst = 0;
     for (int i = 0; i < n; i++) {
         int s = status[i] ? status[i] : st2[i];
