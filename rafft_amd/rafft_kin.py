@@ -43,9 +43,9 @@ def _pair_table(db):
     return pt
 
 
-def get_transition_mat(fast_paths, nb_struct, struct_map):
+def get_transition_mat(fast_paths, nb_struct, struct_map, kt=KT):
     """rafft_kin.py:68-91.  Note the reference's quirk: step 0 is compared with the LAST step
-    (`fast_paths[step_i - 1]` with step_i == 0)."""
+    (`fast_paths[step_i - 1]` with step_i == 0).  `kt`: the reference's constant 0.61 unless given."""
     transition_mat = zeros((nb_struct, nb_struct), dtype=np.longdouble)
     tables = [np.stack([_pair_table(s.str_struct) for s in step]) if step else None for step in fast_paths]
     for step_i, fold_step in enumerate(fast_paths):
@@ -60,8 +60,8 @@ def get_transition_mat(fast_paths, nb_struct, struct_map):
                 map_prev, prev_nrj = struct_map[prev[si].str_struct]
                 delta_nrj = cur_nrj - prev_nrj
                 if map_cur != map_prev:
-                    transition_mat[map_prev, map_cur] = min(1.0, exp(-delta_nrj / KT))
-                    transition_mat[map_cur, map_prev] = min(1.0, exp(delta_nrj / KT))
+                    transition_mat[map_prev, map_cur] = min(1.0, exp(-delta_nrj / kt))
+                    transition_mat[map_cur, map_prev] = min(1.0, exp(delta_nrj / kt))
     for si in range(nb_struct):
         transition_mat[si, si] = -transition_mat[si, :].sum()
     return transition_mat
@@ -114,6 +114,9 @@ def graph_arrays(fast_paths):
     """The graph as flat arrays for the C-ABI: step sizes, all dot-bracket rows back to back, row -> unique index,
     energy of every unique structure (of its first appearance, rafft_kin.py:115), the unique structures."""
     struct_list, index = unique_structures(fast_paths)
+    lengths = {len(st.str_struct) for st in struct_list}
+    if len(lengths) > 1:
+        raise ValueError(f"the structures of a graph must have one length, got {sorted(lengths)}")
     sizes = np.array([len(step) for step in fast_paths], dtype=np.int32)
     rows = "".join(st.str_struct for step in fast_paths for st in step).encode("ascii")
     uid = np.array([index[st.str_struct] for step in fast_paths for st in step], dtype=np.int32)
@@ -138,20 +141,21 @@ def rate_matrix_gpu(fast_paths, kt=KT):
 SPECTRAL_MAX_SPAN_KT = 30.0     # sqrt(pi_max / pi_min) = e^15 = 3e6: the spectral formula keeps ~9 digits
 
 
-def solve_master_equation(rate, energy, p0, sample_times, method="auto", substeps=32):
+def solve_master_equation(rate, energy, p0, sample_times, method="auto", substeps=32, kt=KT):
     """p(t) at `sample_times` for dp/dt = rate^T p (torch float64 tensors on any device; on the GPU the dense
-    factorisations are rocSOLVER's).  Returns an (n_times, S) numpy array of populations normalised to 1."""
+    factorisations are rocSOLVER's).  Returns an (n_times, S) numpy array of populations normalised to 1.
+    `kt` must be the one the rate matrix was built with: the spectral symmetrisation and the choice "auto" makes use it."""
     import torch
     dev = rate.device
     S = rate.shape[0]
     A = rate.T.contiguous()                           # M_ij = k(i -> j), rafft_kin.py:83-85
     energy = np.asarray(energy, dtype=np.float64)
-    span = float(energy.max() - energy.min()) / KT
+    span = float(energy.max() - energy.min()) / kt
     if method == "auto":
         method = "spectral" if span <= SPECTRAL_MAX_SPAN_KT else "implicit"
     if method == "spectral":
         e = torch.as_tensor(energy, device=dev)
-        d = torch.exp(-0.5 * (e - e.min()) / KT)     # sqrt(pi), <= 1
+        d = torch.exp(-0.5 * (e - e.min()) / kt)     # sqrt(pi), <= 1
         B = A * (d[None, :] / d[:, None])            # B[j,i] = A[j,i] * sqrt(pi_i / pi_j): symmetric by detailed balance
         B = 0.5 * (B + B.T)
         lam, Q = torch.linalg.eigh(B)                # rocSOLVER syevd on the GPU
@@ -217,13 +221,14 @@ def solve_master_equation(rate, energy, p0, sample_times, method="auto", substep
     return np.stack(out)
 
 
-def kinetics_gpu(fast_paths, max_time, n_steps, initial_pop=None, method="auto", substeps=32):
+def kinetics_gpu(fast_paths, max_time, n_steps, initial_pop=None, method="auto", substeps=32, kt=KT):
     """Same contract as `kinetics` (rafft_kin.py:94-150).  The rate matrix (inclusion search + Metropolis rates) is computed on
     the MI355X; the master equation is solved on the device (spectral, implicit-dense) or - the sparse TR-BDF2 integrator that
     `implicit` and, beyond 30 KT of energy span, `auto` use - on the host from the non-zeros (see solve_master_equation).  Returns
-    (trajectory, times, struct_list, str_equi_pop); trajectory rows are float64 numpy arrays."""
+    (trajectory, times, struct_list, str_equi_pop); trajectory rows are float64 numpy arrays.  `kt` goes to the rate matrix and
+    to the solver alike."""
     import torch
-    rate, struct_list, energy = rate_matrix_gpu(fast_paths)
+    rate, struct_list, energy = rate_matrix_gpu(fast_paths, kt)
     S = len(struct_list)
     p0 = torch.zeros(S, dtype=torch.float64, device=rate.device)
     if initial_pop is None:
@@ -233,7 +238,7 @@ def kinetics_gpu(fast_paths, max_time, n_steps, initial_pop=None, method="auto",
             p0[where] = weight
     sample_times = np.exp(np.arange(n_steps) * (max_time / n_steps) - 4)
     times = [exp(-4)] + [t for t in sample_times]
-    pops = solve_master_equation(rate, energy, p0, sample_times, method, substeps)
+    pops = solve_master_equation(rate, energy, p0, sample_times, method, substeps, kt)
     trajectory = [p0.cpu().numpy().copy()] + [row for row in pops]
     final = trajectory[-1]
     str_equi_pop = [(st.str_struct, st.energy, float(final[k]), k) for k, st in enumerate(struct_list)]
