@@ -96,6 +96,26 @@ inline void builtin_unpinned_counts(int out[3])
     }
 }
 
+// one table of a set by its ViennaRNA name (w: 0 the 37 C values, 1 the enthalpies), flat and row-major in ViennaRNA's own array
+// shape (pairs 0..7, bases 0..4), with its number of entries; null: no table of that name
+inline const int *table_by_name(const ParamSet &P, const char *table, int w, long *count)
+{
+    struct Ent { const char *n; const int *p; long cnt; };
+    const Ent ents[] = {
+        {"stack", &P.stack[w][0][0], 64}, {"hairpin", P.hairpin[w], 31}, {"bulge", P.bulge[w], 31}, {"interior", P.interior[w], 31},
+        {"mismatch_hairpin", &P.mmH[w][0][0][0], 200}, {"mismatch_interior", &P.mmI[w][0][0][0], 200},
+        {"mismatch_interior_1n", &P.mm1n[w][0][0][0], 200}, {"mismatch_interior_23", &P.mm23[w][0][0][0], 200},
+        {"mismatch_multi", &P.mmM[w][0][0][0], 200}, {"mismatch_exterior", &P.mmE[w][0][0][0], 200},
+        {"dangle5", &P.d5[w][0][0], 40}, {"dangle3", &P.d3[w][0][0], 40},
+        {"int11", &P.int11[w][0][0][0][0], 8 * 8 * 25}, {"int21", &P.int21[w][0][0][0][0][0], 8 * 8 * 125},
+        {"int22", &P.int22[w][0][0][0][0][0][0], 8 * 8 * 625},
+        {"ninio", &P.ninio[w], 1}, {"ml_base", &P.ml_base[w], 1}, {"ml_closing", &P.ml_closing[w], 1}, {"ml_intern", &P.ml_intern[w], 1},
+        {"terminal_au", &P.term_au[w], 1}, {"max_ninio", &P.max_ninio, 1}};
+    for (const Ent &e : ents)
+        if (!strcmp(e.n, table)) { *count = e.cnt; return e.p; }
+    return nullptr;
+}
+
 // ---------------------------------------------------------------- reader
 
 struct Section { std::vector<std::string> tok; std::vector<int> line; int head_line = 0; };   // tokens with the line each came from; line of the '# name' header

@@ -263,8 +263,6 @@ static size_t merge_cap()
     return (size_t)std::max(1, g.sched_cfg.merge_seqs);
 }
 
-struct SeqIn { const char *s; int len; int idx; int bi; const uint8_t *c = nullptr; };   // bi: which member batch of the job the sequence belongs to; c: the bases as codes (encoded at submit, on the caller's thread), or null
-
 // The HBM plan of a job: the initial `seen` tables of its sequences and the arenas sized from them.  Wave::setup allocates by it, the
 // scheduler's admission test asks it whether the job fits.
 struct JobPlan { Caps caps; std::vector<uint32_t> seen_cap0; size_t seen0_total; double seen0_avg; };

@@ -25,14 +25,6 @@ static int g_span_level = 1;
 static inline bool span_on(int kind) { return g_span_level >= 2 || (g_span_level == 1 && kind == 11); }
 #define SPAN_REC(ev, st, kind) do { if (span_on(kind)) HIPCHK(hipEventRecord((ev), (st))); } while (0)
 
-// base codes of rafft/utils.py:73-80 (N=0 A=1 C=2 G=3 U=4); bit 3 marks a character outside "AGCUN"
-struct BaseCodeTable {
-    uint8_t v[256];
-    BaseCodeTable() { for (int i = 0; i < 256; i++) v[i] = 8; v['N'] = 0; v['A'] = 1; v['C'] = 2; v['G'] = 3; v['U'] = 4; }
-    uint8_t operator[](unsigned char c) const { return v[c]; }
-};
-static const BaseCodeTable kBaseCode;
-
 struct HostOut {   // owner of a rafft_result
     std::vector<rafft_seq_result> seq;
     std::vector<std::vector<int>> step_size, step_off;
@@ -41,6 +33,7 @@ struct HostOut {   // owner of a rafft_result
     std::vector<const int *> dcal_ptr;      // directly in the memory the caller reads
     std::vector<std::shared_ptr<struct PinChunk>> chunks;   // a chunk may hold rows of several batches folded as one wave
     rafft_result res;
+    void resize(int n) { seq.resize(n); step_size.resize(n); step_off.resize(n); one_size.assign(n, 0); one_off.assign(n, 0); dcal_ptr.assign(n, nullptr); db_ptr.assign(n, nullptr); }
 };
 void free_out(HostOut *o) { delete o; }      // (its pinned chunks go back to the pool with their last reference)
 
@@ -51,7 +44,7 @@ struct Job { std::vector<SeqIn> seqs; double est; int depth; std::vector<std::sh
              bool big_prod = false; };    // re-run after a structure had more productive regions than the short lists hold
 
 // One rafft_fold_submit(): its sequences (copied), its result under construction, its jobs (lane 0: the long tail of
-// the batch, lane 1: the bulk - see rafft_fold_submit) and what the scheduler needs to finish it.
+// the batch, lane 1: the bulk - see cut_lanes, rafft_hostpure.h) and what the scheduler needs to finish it.
 struct Batch {
     rafft_params p;
     Config cfg;                               // the environment switches as they were when the batch was submitted (rafft_config.h)

@@ -349,3 +349,15 @@ def test_config_struct_is_the_only_reader_of_the_environment(tmp_path):
         subprocess.check_call(["g++", "-std=c++17", "-O1"] + flags + [os.path.join(ROOT, "tests", "hostcheck", "config_check.cpp"), "-o", exe])
         r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
         assert r.returncode == 0 and "0 failures" in r.stdout, r.stdout + r.stderr
+
+
+def test_hostpure_helpers_against_hand_derived_values(tmp_path):
+    """rafft_hostpure.h - the lane cut of a batch (RAFFT_SPLIT rule, lanes, estimate), the two host dot-bracket parsers, the base codes, the
+    enclosing-loop walk of rafft_expand_node and the row layout of the scoring calls - compiled alone with g++ (no HIP, no GPU) and checked
+    against values derived by hand from the rules; then the same program under AddressSanitizer + UBSan, run directly"""
+    src = os.path.join(ROOT, "tests", "hostcheck", "hostpure_check.cpp")
+    for tag, flags in (("plain", ["-O1"]), ("san", ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = str(tmp_path / ("hostpure_check_" + tag))
+        subprocess.check_call(["g++", "-std=c++17", "-Wall"] + flags + [src, "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and "0 failures" in r.stdout and not r.stderr, r.stdout + r.stderr
