@@ -213,6 +213,45 @@ int rafft_get_stats(rafft_stats *out);
 int rafft_kin_rate_matrix(int n_steps, const int *step_size, int L, const char *rows, const int *uid, int n_unique,
                           const double *energy, double kt, double *rate_device);
 
+/* The kinetics of a whole batch of fast-folding graphs in one call.  Replaces, per graph: get_connected_prev +
+ * get_transition_mat + kinetics, rafft/rafft_kin.py:48-56,68-150 - which rows are the same structure (rafft_kin.py:106-112), the
+ * Metropolis rate matrix, and the populations p(t) of dp/dt = rate^T p with everything on unique structure 0 at t = 0 (the
+ * reference's default initial population).  Where the reference solves with eig/inv - numerically wrong on its own example - this
+ * integrates with TR-BDF2, `m[k]` sub-steps of `h[k]` from times[k-1] (0 for k = 0) to times[k]; the caller computes the schedule
+ * (rafft_amd.rafft_kin.kinetics_schedule), so m[k] * h[k] = times[k] - times[k-1].  The generator has non-negative off-diagonals and
+ * zero column sums, so every stage matrix is strictly column-diagonally dominant and is inverted without pivoting.
+ * Built for many small graphs: one with more than RAFFT_KIN_BATCH_MAX_STATES unique structures gets RAFFT_ERR_CAPACITY and goes
+ * through rafft_kin_rate_matrix and a solver of the caller's instead (its matrix and the inverse would no longer stay in the L2:
+ * 2 x 8 MB at 1024 states).
+ * Per graph g, in the shape of rafft_score_rows: lens[g] positions; n_steps[g] beams of step_size[g][i] rows; rows[g] = the rows
+ * of all its steps, row_stride[g] bytes apart (lens[g] back to back, lens[g] + 1 for rafft_seq_result.db, taken from where the fold left
+ * them: the host packs them once for the upload); energy[g][row] = the energy the caller chose for each row (the first appearance of a structure counts, rafft_kin.py:115).
+ * kt = 0.61 in the reference.  times: n_times ascending positive sample times.  workspace_bytes: device memory for the matrices of
+ * the graphs solved together (0: the default, 512 MiB); graphs are processed in chunks that fit, one graph at least.
+ * Outputs (host): graph_out[g]; uid_out[row0 + r] = index of row r in the list of the graph's unique structures in order of first
+ * appearance; first_row_out[row0 + u] = row (numbered inside the graph) where unique structure u first appears, -1 beyond
+ * n_unique; pop_out + n_times * row0 = n_times rows of n_unique doubles, each normalised to sum 1 (the caller sizes uid_out and
+ * first_row_out for the rows of all graphs, pop_out for n_times times as many); rate_out (may be NULL, and so may rate_out[g]) =
+ * per graph a host buffer for the n_unique x n_unique row-major rate matrix, diagonal = -row sum.
+ * Same input, same bits: every sum has a fixed order, and a graph's results do not depend on the rest of the batch.
+ * A malformed row (RAFFT_ERR_STRUCT) or too many unique structures (RAFFT_ERR_CAPACITY) is an error of that graph only - the call
+ * returns RAFFT_OK, rafft_last_error() names the first such graph, the graph's uid_out / first_row_out are -1 and its populations 0.
+ * RAFFT_ERR_PARAM, before anything is launched: a null argument, a negative count, a length above 32767, a stride below the
+ * length, times that do not ascend from above 0, kt, m[k] or h[k] not positive. */
+#define RAFFT_KIN_BATCH_MAX_STATES 1024
+typedef struct {
+    int32_t status;
+    int32_t n_rows;      /* rows over all steps */
+    int32_t row0;        /* index of the graph's first row in uid_out / first_row_out; its populations start at n_times * row0 */
+    int32_t n_unique;    /* unique structures (also set with RAFFT_ERR_CAPACITY) */
+    int32_t n_edges;     /* non-zero off-diagonal rates */
+    int32_t _pad;
+} rafft_kin_graph;       /* 24 bytes */
+int rafft_kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows,
+                    const int *row_stride, const double *const *energy, double kt, int n_times, const double *times, const int *m,
+                    const double *h, long long workspace_bytes, rafft_kin_graph *graph_out, int *uid_out, int *first_row_out,
+                    double *pop_out, double *const *rate_out);
+
 /* Folding landscape of a fast-folding graph.  Replaces the arithmetic of utility/surface.py; the drawing
  * stays in Python.  All matrices live in DEVICE memory of the caller (HIP pointers, e.g. a torch tensor's data_ptr); the
  * caller's own stream must be done with them.  Same input, same bits: every floating-point sum has a fixed order.

@@ -42,12 +42,20 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KinGraph(C.Structure):
+    """rafft_kin_graph: one record per graph of rafft_kin_batch"""
+    _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("row0", C.c_int32), ("n_unique", C.c_int32), ("n_edges", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+KIN_BATCH_MAX_STATES = 1024      # RAFFT_KIN_BATCH_MAX_STATES
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
            "rafft_param_value", "rafft_kin_rate_matrix", "rafft_shutdown", "rafft_alloc_counters", "rafft_eval_structures_info", "rafft_params_unpinned",
            "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
-           "rafft_score_rows", "rafft_score_result"]
+           "rafft_score_rows", "rafft_score_result", "rafft_kin_batch"]
 
 _lib = None
 
@@ -131,6 +139,10 @@ def lib():
     L.rafft_score_rows.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_int),
                                    C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
     L.rafft_score_result.argtypes = [C.POINTER(Result), C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
+    L.rafft_kin_batch.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_void_p), C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                  C.c_longlong, C.POINTER(KinGraph), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_void_p)]
     _lib = L
     return L
 

@@ -47,6 +47,11 @@ _OPTIONS = [
                                                                         "highest PPV (scoring.py), or the first one (scoring.py --one)")),
     (("--known_column",), dict(default="struct", help="known-structure column of a CSV with a header (default: struct)")),
     (("--name_column",), dict(default="name", help="name column of a CSV with a header (default: name)")),
+    (("--kin",), dict(metavar="OUT", help="with -sf FILE --batch: fold with trajectories and solve the folding kinetics of every sequence's\n"
+                                          "fast-folding graph on the GPU, all in one call (rafft_kin.kinetics_batch).  OUT gets, per sequence,\n"
+                                          "a `> index sequence` line and the table `rafft_kin` prints, sorted by final population")),
+    (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
+    (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
     (("--output", "-o"), dict(help="write the result there instead of stdout")),
     (("--sidecar",), dict(help="with --traj: also write the fast-folding graph as a binary side-car (exact dcal energies,\n"
                                "no strings to re-parse) that `rafft_kin --sidecar` reads; with several sequences the\n"
@@ -142,6 +147,18 @@ def write_scores(path, seqs, names, results, table, select="ppv", traj=False):
             out.write(f"{s},{len(s)},{struct},{nrj},{struct.count('(')},{round(ppv, 2)},{round(sens, 2)},{names[k]}\n")
 
 
+def write_kinetics(path, seqs, tables):
+    """--kin: per sequence `> index sequence` and the lines of rafft_kin (structure, final population, energy, index), sorted by
+    final population.  `tables`: what rafft_kin.kinetics_batch returns; a sequence whose fold failed has a header line only."""
+    with open(path, "w") as out:
+        for k, s in enumerate(seqs):
+            out.write(f"> {k} {s}\n")
+            if tables[k] is None:
+                continue
+            for st, nrj, fp, si in sorted(tables[k][3], key=lambda el: el[2]):
+                out.write("{} {:6.3f} {:5.1f} {:d}\n".format(st, fp, nrj, si))
+
+
 def format_result(sequence, result, args):
     out = []
     if args.traj:
@@ -176,11 +193,16 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None):
-    """`fold_batch` / `scorer`: injection points for tests (the fold, and the callable (results, known) -> score table that
-    stands in for scoring.score_batch_gpu)."""
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None):
+    """`fold_batch` / `scorer` / `kinetics`: injection points for tests (the fold, the callable (results, known) -> score table that
+    stands in for scoring.score_batch_gpu, and the callable (results, max_time, n_steps) that stands in for
+    rafft_kin.kinetics_batch)."""
     args = parse_arguments(argv)
     seqs, known, names = read_records(args)
+    if args.kin:
+        if not args.batch or args.seq_file is None:
+            raise SystemExit("--kin needs -sf FILE --batch")
+        args.traj = True
     if args.scores:
         if not args.batch or known is None:
             raise SystemExit("--scores needs -sf CSV --batch with a known structure per sequence "
@@ -195,6 +217,13 @@ def main(argv=None, fold_batch=None, scorer=None):
             from .scoring import score_batch_gpu as scorer
         write_scores(args.scores, seqs, names, results, scorer(results, known), args.select, args.traj)
         if not args.output:          # the table is the output; the structures are written as well when -o names a file
+            _table_note()
+            return
+    if args.kin:
+        if kinetics is None:
+            from .rafft_kin import kinetics_batch as kinetics
+        write_kinetics(args.kin, seqs, kinetics(results if hasattr(results, "raw") else [r[1] for r in results], args.max_time, args.n_steps))
+        if not args.output:          # the tables are the output; the graphs are written as well when -o names a file
             _table_note()
             return
     out = open(args.output, "wb") if args.output else sys.stdout.buffer if hasattr(sys.stdout, "buffer") else None

@@ -35,6 +35,7 @@
 // unit so the templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
+#include "rafft_kin_batch.hip"
 #include "rafft_landscape.hip"
 #include "rafft_score.hip"
 
@@ -249,6 +250,34 @@ int rafft_kin_rate_matrix(int n_steps, const int *step_size, int L, const char *
     if (!step_size || !rows || !uid || !energy || !rate_device || n_steps < 1 || L < 1 || L > 32767 || n_unique < 1 || !(kt > 0))
         return fail(RAFFT_ERR_PARAM, "bad argument");
     return kin_rate_matrix(n_steps, step_size, L, rows, uid, n_unique, energy, kt, rate_device);
+}
+
+int rafft_kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows, const int *row_stride,
+                    const double *const *energy, double kt, int n_times, const double *times, const int *m, const double *h, long long workspace_bytes,
+                    rafft_kin_graph *graph_out, int *uid_out, int *first_row_out, double *pop_out, double *const *rate_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_graphs < 0 || n_times < 1 || !times || !m || !h || !(kt > 0) || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_graphs > 0 && (!lens || !n_steps || !step_size || !rows || !row_stride || !energy || !graph_out || !uid_out || !first_row_out || !pop_out))
+        return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < n_times; k++) {
+        if (!(times[k] > (k ? times[k - 1] : 0.0)) || !(times[k] < INFINITY)) return fail(RAFFT_ERR_PARAM, "times must be positive and ascend");
+        if (m[k] < 1 || !(h[k] > 0) || !(h[k] < INFINITY)) return fail(RAFFT_ERR_PARAM, "interval " + std::to_string(k) + ": non-positive sub-step count or step");
+    }
+    for (int i = 0; i < n_graphs; i++) {
+        const std::string who = "graph " + std::to_string(i);
+        if (lens[i] < 0 || lens[i] > 32767) return fail(RAFFT_ERR_PARAM, who + ": length outside 0..32767");
+        if (row_stride[i] < lens[i]) return fail(RAFFT_ERR_PARAM, who + ": row stride below the length");
+        if (n_steps[i] < 0 || (n_steps[i] && !step_size[i])) return fail(RAFFT_ERR_PARAM, who + ": negative number of steps or no step sizes");
+        long long nr = 0;
+        for (int s = 0; s < n_steps[i]; s++) {
+            if (step_size[i][s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative step size");
+            nr += step_size[i][s];
+        }
+        if (nr && (!rows[i] || !energy[i])) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+    }
+    return kin_batch(n_graphs, lens, n_steps, step_size, rows, row_stride, energy, kt, n_times, m, h, workspace_bytes, graph_out, uid_out, first_row_out,
+                     pop_out, rate_out);
 }
 
 int rafft_landscape_distances(int n, int L, const char *rows, uint16_t *dist_device)

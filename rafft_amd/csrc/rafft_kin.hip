@@ -13,44 +13,46 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// pair tables from dot-bracket rows: one thread per row, explicit stack in a global scratch row
-__global__ void kin_pair_table_kernel(int n, int L, const char *rows, int16_t *pt, int16_t *stack, int *bad)
+// pair table of one dot-bracket row, explicit stack in a scratch row of its own; false: the row is malformed
+__device__ __forceinline__ bool kin_pair_table_row(int L, const char *row, int16_t *p, int16_t *st)
 {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const char *row = rows + (size_t)r * L;
-    int16_t *p = pt + (size_t)r * L, *st = stack + (size_t)r * L;
     int sp = 0;
     for (int x = 0; x < L; x++) {
         const char c = row[x];
         p[x] = -1;
         if (c == '(') st[sp++] = (int16_t)x;
         else if (c == ')') {
-            if (sp == 0) { *bad = 1; return; }
+            if (sp == 0) return false;
             const int j = st[--sp];
             p[x] = (int16_t)j; p[j] = (int16_t)x;
-        } else if (c != '.') { *bad = 1; return; }
+        } else if (c != '.') return false;
     }
-    if (sp) *bad = 1;
+    return sp == 0;
+}
+
+// pair tables from dot-bracket rows: one thread per row, explicit stack in a global scratch row
+__global__ void kin_pair_table_kernel(int n, int L, const char *rows, int16_t *pt, int16_t *stack, int *bad)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    if (!kin_pair_table_row(L, rows + (size_t)r * L, pt + (size_t)r * L, stack + (size_t)r * L)) *bad = 1;
 }
 
 // rates between connected structures.  cur_row0/prev_row0: first rows of the two steps; uid: row -> unique structure;
 // energy: per unique structure (the energy of its first appearance, rafft_kin.py:115); rate: S x S row-major, zeroed.
 // Several (step, pair) occurrences of the same two structures write the same values (benign).
 #define KIN_NT 256
-__global__ __launch_bounds__(KIN_NT) void kin_rates_kernel(int L, const int16_t *pt, int cur_row0, int n_prev, int prev_row0,
-                                                           const int *uid, const double *energy, double kt, int S, double *rate)
+// one workgroup of KIN_NT threads: the structure with pair table `pc` (unique index uc) against the n_prev structures whose tables
+// start at `pp0` and whose unique indices start at `uid_prev`; cur: L entries of LDS
+__device__ __forceinline__ void kin_rates_row(int L, const int16_t *pc, const int16_t *pp0, int n_prev, int uc, const int *uid_prev,
+                                              const double *energy, double kt, int S, double *rate, int16_t *cur)
 {
-    extern __shared__ int16_t cur[];
-    const int c = cur_row0 + blockIdx.x;
-    const int16_t *pc = pt + (size_t)c * L;
     for (int x = threadIdx.x; x < L; x += KIN_NT) cur[x] = pc[x];
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int uc = uid[c];
     const double ec = energy[uc];
     for (int p = wv; p < n_prev; p += KIN_NT / 64) {
-        const int16_t *pp = pt + (size_t)(prev_row0 + p) * L;
+        const int16_t *pp = pp0 + (size_t)p * L;
         bool ok = true;
         for (int x0 = 0; x0 < L && ok; x0 += 64) {
             const int x = x0 + lane;
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(KIN_NT) void kin_rates_kernel(int L, const int16_t 
             if (__ballot(viol)) ok = false;
         }
         if (ok && lane == 0) {
-            const int up = uid[prev_row0 + p];
+            const int up = uid_prev[p];
             if (up != uc) {
                 const double d = ec - energy[up];       // delta_nrj = cur_nrj - prev_nrj
                 rate[(size_t)up * S + uc] = fmin(1.0, exp(-d / kt));
@@ -69,18 +71,33 @@ __global__ __launch_bounds__(KIN_NT) void kin_rates_kernel(int L, const int16_t 
     }
 }
 
-// transition_mat[si, si] = -transition_mat[si, :].sum()   (rafft_kin.py:87-88); one workgroup per row
-__global__ __launch_bounds__(256) void kin_diag_kernel(int S, double *rate)
+__global__ __launch_bounds__(KIN_NT) void kin_rates_kernel(int L, const int16_t *pt, int cur_row0, int n_prev, int prev_row0,
+                                                           const int *uid, const double *energy, double kt, int S, double *rate)
 {
-    __shared__ double part[256];
-    const int r = blockIdx.x;
+    extern __shared__ int16_t cur[];
+    const int c = cur_row0 + blockIdx.x;
+    kin_rates_row(L, pt + (size_t)c * L, pt + (size_t)prev_row0 * L, n_prev, uid[c], uid + prev_row0, energy, kt, S, rate, cur);
+}
+
+// sum of a matrix row in a fixed order, by one workgroup of 256 threads (part: 256 doubles of LDS); every thread gets it
+__device__ __forceinline__ double kin_row_sum(int S, const double *row, double *part)
+{
     double s = 0.0;
-    for (int c = threadIdx.x; c < S; c += 256) s += rate[(size_t)r * S + c];
+    for (int c = threadIdx.x; c < S; c += 256) s += row[c];
     part[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) rate[(size_t)r * S + r] = -part[0];
+    return part[0];
+}
+
+// transition_mat[si, si] = -transition_mat[si, :].sum()   (rafft_kin.py:87-88); one workgroup per row
+__global__ __launch_bounds__(256) void kin_diag_kernel(int S, double *rate)
+{
+    __shared__ double part[256];
+    const int r = blockIdx.x;
+    const double s = kin_row_sum(S, rate + (size_t)r * S, part);
+    if (threadIdx.x == 0) rate[(size_t)r * S + r] = -s;
 }

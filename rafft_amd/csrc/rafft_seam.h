@@ -201,6 +201,190 @@ int kin_rate_matrix(int n_steps, const int *step_size, int L, const char *rows, 
     return 0;
 }
 
+// rafft_kin_batch (arguments validated by the entry point).  Two passes over the device: structure identity for every graph, then -
+// the numbers of unique structures being known - rates and integration for chunks of graphs whose matrices fit the workspace budget.
+constexpr size_t KIN_BATCH_WORKSPACE = (size_t)512 << 20;
+
+int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows, const int *row_stride,
+              const double *const *energy, double kt, int n_times, const int *m, const double *h, long long workspace_bytes,
+              rafft_kin_graph *rec, int *uid_out, int *first_row_out, double *pop_out, double *const *rate_out)
+{
+    std::vector<KinGraph> gs(n_graphs);
+    long long n = 0;
+    unsigned long long bytes = 0;
+    int Lmax = 0;
+    for (int g = 0; g < n_graphs; g++) {
+        long long nr = 0;
+        for (int i = 0; i < n_steps[g]; i++) nr += step_size[g][i];
+        if (n + nr > 0x7fffffff) return fail(RAFFT_ERR_PARAM, "too many rows");
+        gs[g] = KinGraph{bytes, 0, lens[g], (int)nr, (int)n, 0};
+        rec[g] = rafft_kin_graph{0, (int)nr, (int)n, 0, 0, 0};
+        n += nr;
+        bytes += (unsigned long long)nr * (unsigned long long)lens[g];
+        if (nr) Lmax = std::max(Lmax, lens[g]);
+    }
+    if (n == 0) return 0;
+    // rows packed back to back; per row: its graph, the step it is compared with, its energy
+    std::vector<char> pack(bytes + 1);
+    std::vector<int> row_graph(n), row_prev0(n), row_nprev(n);
+    std::vector<double> en(n);
+    for (int g = 0; g < n_graphs; g++) {
+        const KinGraph &G = gs[g];
+        if (!G.n_rows) continue;
+        if (row_stride[g] == G.L) memcpy(pack.data() + G.off, rows[g], (size_t)G.n_rows * G.L);
+        else for (int r = 0; r < G.n_rows; r++) memcpy(pack.data() + G.off + (size_t)r * G.L, rows[g] + (size_t)r * row_stride[g], (size_t)G.L);
+        memcpy(en.data() + G.row0, energy[g], (size_t)G.n_rows * sizeof(double));
+        std::vector<int> s0(n_steps[g]);
+        int at = G.row0;
+        for (int i = 0; i < n_steps[g]; i++) { s0[i] = at; at += step_size[g][i]; }
+        for (int i = 0; i < n_steps[g]; i++) {
+            const int pi = i == 0 ? n_steps[g] - 1 : i - 1;   // the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)
+            for (int r = s0[i]; r < s0[i] + step_size[g][i]; r++) { row_graph[r] = g; row_prev0[r] = s0[pi]; row_nprev[r] = step_size[g][pi]; }
+        }
+    }
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    KinGraph *d_gs; char *d_rows; int16_t *d_pt, *d_stack; unsigned long long *d_hash; double *d_en, *d_enu, *d_h;
+    int *d_rg, *d_p0, *d_np, *d_bad, *d_first, *d_rank, *d_frow, *d_nu, *d_uid, *d_ne, *d_m;
+    const size_t n4 = (size_t)n * 4, g4 = (size_t)n_graphs * 4;
+    if (int rc = mem.alloc(d_gs, gs.size() * sizeof(KinGraph))) return rc;
+    if (int rc = mem.alloc(d_rows, bytes + 1)) return rc;
+    if (int rc = mem.alloc(d_pt, (bytes + 1) * 2)) return rc;
+    if (int rc = mem.alloc(d_stack, (bytes + 1) * 2)) return rc;
+    if (int rc = mem.alloc(d_hash, n4 * 2)) return rc;
+    if (int rc = mem.alloc(d_en, n4 * 2)) return rc;
+    if (int rc = mem.alloc(d_enu, n4 * 2)) return rc;
+    if (int rc = mem.alloc(d_rg, n4)) return rc;
+    if (int rc = mem.alloc(d_p0, n4)) return rc;
+    if (int rc = mem.alloc(d_np, n4)) return rc;
+    if (int rc = mem.alloc(d_first, n4)) return rc;
+    if (int rc = mem.alloc(d_rank, n4)) return rc;
+    if (int rc = mem.alloc(d_frow, n4)) return rc;
+    if (int rc = mem.alloc(d_uid, n4)) return rc;
+    if (int rc = mem.alloc(d_bad, g4)) return rc;
+    if (int rc = mem.alloc(d_nu, g4)) return rc;
+    if (int rc = mem.alloc(d_ne, g4)) return rc;
+    if (int rc = mem.alloc(d_m, (size_t)n_times * 4)) return rc;
+    if (int rc = mem.alloc(d_h, (size_t)n_times * 8)) return rc;
+    HIPCHK(hipMemcpyAsync(d_gs, gs.data(), gs.size() * sizeof(KinGraph), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rows, pack.data(), bytes + 1, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_en, en.data(), n4 * 2, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rg, row_graph.data(), n4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_p0, row_prev0.data(), n4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_np, row_nprev.data(), n4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_m, m, (size_t)n_times * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_h, h, (size_t)n_times * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_bad, 0, g4, st));
+    HIPCHK(hipMemsetAsync(d_ne, 0, g4, st));
+    HIPCHK(hipMemsetAsync(d_frow, 0xff, n4, st));            // -1: no such unique structure
+    HIPCHK(hipMemsetAsync(d_rank, 0, n4, st));
+    const unsigned nb64 = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(kin_batch_pair_table_kernel, dim3(nb64), dim3(64), 0, st, (int)n, d_gs, d_rg, d_rows, d_pt, d_stack, d_hash, d_bad);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kin_batch_identity_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (int)n, d_gs, d_rg, d_rows, d_hash, d_first);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kin_batch_rank_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, d_gs, d_first, d_en, d_rank, d_frow, d_enu, d_nu);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kin_batch_uid_kernel, dim3(nb64), dim3(64), 0, st, (int)n, d_gs, d_rg, d_first, d_rank, d_uid);
+    HIPCHK(hipGetLastError());
+    std::vector<int> bad(n_graphs), nu(n_graphs);
+    HIPCHK(hipMemcpyAsync(bad.data(), d_bad, g4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(nu.data(), d_nu, g4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(uid_out, d_uid, n4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(first_row_out, d_frow, n4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::string first_err;
+    for (int g = 0; g < n_graphs; g++) {
+        KinGraph &G = gs[g];
+        if (bad[g]) {
+            rec[g].status = RAFFT_ERR_STRUCT;
+            if (first_err.empty()) first_err = "graph " + std::to_string(g) + ": malformed dot-bracket row";
+        } else if (nu[g] > RAFFT_KIN_BATCH_MAX_STATES) {
+            rec[g].status = RAFFT_ERR_CAPACITY;
+            rec[g].n_unique = nu[g];
+            if (first_err.empty())
+                first_err = "graph " + std::to_string(g) + ": " + std::to_string(nu[g]) + " unique structures, the batch path takes up to " +
+                            std::to_string(RAFFT_KIN_BATCH_MAX_STATES) + " - use the single-graph path (rafft_kin_rate_matrix and a dense or sparse solver)";
+        } else {
+            rec[g].n_unique = G.S = nu[g];
+            continue;
+        }
+        for (int r = 0; r < G.n_rows; r++) uid_out[G.row0 + r] = first_row_out[G.row0 + r] = -1;
+    }
+    // chunks of consecutive graphs: three S x S blocks per graph and the populations of the chunk within the budget (one graph at least)
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : KIN_BATCH_WORKSPACE;
+    struct Chunk { int ga, gb; };
+    std::vector<Chunk> chunks;
+    size_t ws_max = 0, pop_max = 0;
+    for (int ga = 0; ga < n_graphs; ) {
+        size_t w = 0, pp = 0;
+        int gb = ga;
+        while (gb < n_graphs) {
+            const size_t dw = 3 * (size_t)gs[gb].S * gs[gb].S * 8, dp = (size_t)n_times * gs[gb].n_rows * 8;
+            if (gb > ga && (w + dw > budget || pp + dp > budget)) break;
+            gs[gb].mat = w / 8;
+            w += dw; pp += dp; gb++;
+        }
+        chunks.push_back(Chunk{ga, gb});
+        ws_max = std::max(ws_max, w); pop_max = std::max(pop_max, pp);
+        ga = gb;
+    }
+    double *d_ws, *d_pop;
+    if (int rc = mem.alloc(d_ws, ws_max + 8)) return rc;
+    if (int rc = mem.alloc(d_pop, pop_max + 8)) return rc;
+    HIPCHK(hipMemcpyAsync(d_gs, gs.data(), gs.size() * sizeof(KinGraph), hipMemcpyHostToDevice, st));
+    constexpr size_t lds_small = (size_t)(4 * KIN_BATCH_LDS_STATES + 1 + KIN_BATCH_LDS_STATES * KIN_BATCH_LDS_STATES) * 8;
+    constexpr size_t lds_big = (size_t)(4 * RAFFT_KIN_BATCH_MAX_STATES + 1) * 8;
+    HIPCHK(hipFuncSetAttribute((const void *)kin_batch_integrate_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
+    // per chunk the graphs that are solved: those whose inverse fits LDS first, then the others
+    std::vector<int> order(n_graphs), n_small(chunks.size()), n_big(chunks.size());
+    for (size_t ci = 0; ci < chunks.size(); ci++) {
+        int at = chunks[ci].ga;
+        for (int g = chunks[ci].ga; g < chunks[ci].gb; g++) if (gs[g].S && gs[g].S <= KIN_BATCH_LDS_STATES) order[at++] = g;
+        n_small[ci] = at - chunks[ci].ga;
+        for (int g = chunks[ci].ga; g < chunks[ci].gb; g++) if (gs[g].S > KIN_BATCH_LDS_STATES) order[at++] = g;
+        n_big[ci] = at - chunks[ci].ga - n_small[ci];
+    }
+    int *d_order;
+    if (int rc = mem.alloc(d_order, g4)) return rc;
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), g4, hipMemcpyHostToDevice, st));
+    for (size_t ci = 0; ci < chunks.size(); ci++) {
+        const Chunk &c = chunks[ci];
+        const int ra = gs[c.ga].row0, rb = c.gb < n_graphs ? gs[c.gb].row0 : (int)n;
+        const int small = n_small[ci], big = n_big[ci];
+        size_t w = 0;
+        for (int g = c.ga; g < c.gb; g++) w += 3 * (size_t)gs[g].S * gs[g].S * 8;
+        if (rb == ra) continue;
+        if (!small && !big) { memset(pop_out + (size_t)n_times * ra, 0, (size_t)n_times * (rb - ra) * 8); continue; }
+        HIPCHK(hipMemsetAsync(d_ws, 0, w, st));
+        HIPCHK(hipMemsetAsync(d_pop, 0, (size_t)n_times * (rb - ra) * 8, st));
+        hipLaunchKernelGGL(kin_batch_rates_kernel, dim3((unsigned)(rb - ra)), dim3(KIN_NT), (size_t)Lmax * 2, st, ra, d_gs, d_rg, d_p0, d_np, d_pt, d_uid, d_enu, kt, d_ws);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(kin_batch_diag_kernel, dim3((unsigned)(rb - ra)), dim3(256), 0, st, ra, d_gs, d_rg, d_ws, d_ne);
+        HIPCHK(hipGetLastError());
+        if (small) {
+            hipLaunchKernelGGL(kin_batch_integrate_kernel<true>, dim3((unsigned)small), dim3(KINB_NT), lds_small, st, d_order + c.ga, ra, d_gs, d_ws, n_times, d_m, d_h, d_pop);
+            HIPCHK(hipGetLastError());
+        }
+        if (big) {
+            hipLaunchKernelGGL(kin_batch_integrate_kernel<false>, dim3((unsigned)big), dim3(KINB_NT), lds_big, st, d_order + c.ga + small, ra, d_gs, d_ws, n_times, d_m, d_h, d_pop);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(pop_out + (size_t)n_times * ra, d_pop, (size_t)n_times * (rb - ra) * 8, hipMemcpyDeviceToHost, st));
+        if (rate_out)
+            for (int g = c.ga; g < c.gb; g++)
+                if (rate_out[g] && gs[g].S) HIPCHK(hipMemcpyAsync(rate_out[g], d_ws + gs[g].mat, (size_t)gs[g].S * gs[g].S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    std::vector<int> ne(n_graphs);
+    HIPCHK(hipMemcpy(ne.data(), d_ne, g4, hipMemcpyDeviceToHost));
+    for (int g = 0; g < n_graphs; g++) rec[g].n_edges = ne[g];
+    g_err = first_err;
+    return 0;
+}
+
 // ---- folding landscape
 
 long long g_landscape_counters[4];      // MDS calls, SMACOF passes enqueued, host read-backs of the `done` words, passes of the last call

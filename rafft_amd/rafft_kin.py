@@ -138,6 +138,22 @@ def rate_matrix_gpu(fast_paths, kt=KT):
     return rate, struct_list, energy
 
 
+def kinetics_schedule(max_time=None, n_steps=None, substeps=32, sample_times=None):
+    """-> (sample_times, m, h): the output times and the TR-BDF2 schedule between them, the one place both come from
+    (solve_master_equation, kinetics_gpu, kinetics_batch).  sample_times: exp(k * max_time / n_steps - 4), k < n_steps
+    (rafft_kin.py:128-131) unless given.  From each output time to the next - from 0 to the first - m[k] sub-steps of h[k]:
+    `substeps` per factor e^0.3 of time (the reference's default spacing), so the relative step stays constant."""
+    if sample_times is None:
+        sample_times = np.exp(np.arange(n_steps) * (max_time / n_steps) - 4)
+    ms, hs, t_now = [], [], 0.0
+    for t in sample_times:
+        m = max(1, int(np.ceil(substeps * (np.log(float(t) / t_now) / 0.3 if t_now > 0 else 1.0))))
+        ms.append(m)
+        hs.append((float(t) - t_now) / m)
+        t_now = float(t)
+    return sample_times, ms, hs
+
+
 SPECTRAL_MAX_SPAN_KT = 30.0     # sqrt(pi_max / pi_min) = e^15 = 3e6: the spectral formula keeps ~9 digits
 
 
@@ -188,35 +204,26 @@ def solve_master_equation(rate, energy, p0, sample_times, method="auto", substep
         As = sp.csc_matrix((vals, (idx[:, 0], idx[:, 1])), shape=(S, S))
         eye_s = sp.identity(S, dtype=np.float64, format="csc")
         y = p0.cpu().numpy().astype(np.float64)
-        t_now = 0.0
         out = []
-        for t in sample_times:
-            m = max(1, int(np.ceil(substeps * (np.log(float(t) / t_now) / 0.3 if t_now > 0 else 1.0))))
-            h = (float(t) - t_now) / m
+        for m, h in zip(*kinetics_schedule(sample_times=sample_times, substeps=substeps)[1:]):
             # (minimum degree on the pattern of A + A^T: the graph is close to a forest of folding paths - 76 k non-zeros in
             #  L + U on the configs[4] graph against 1.0 M with the default COLAMD and 15 M unordered)
             lu = splu((eye_s - (c * h) * As).tocsc(), permc_spec="MMD_AT_PLUS_A")
             for _ in range(m):
                 yg = lu.solve(y + (0.5 * g * h) * (As @ y))
                 y = lu.solve(yg / (g * (2.0 - g)) - ((1.0 - g) ** 2 / (g * (2.0 - g))) * y)
-            t_now = float(t)
             out.append(y / y.sum())
         return np.stack(out)
     eye = torch.eye(S, dtype=torch.float64, device=dev)
     y = p0.clone()
-    t_now = 0.0
     out = []
-    for t in sample_times:
-        # `substeps` per factor e^0.3 of time (the reference's default spacing): the relative step stays constant
-        m = max(1, int(np.ceil(substeps * (np.log(float(t) / t_now) / 0.3 if t_now > 0 else 1.0))))
-        h = (float(t) - t_now) / m
+    for m, h in zip(*kinetics_schedule(sample_times=sample_times, substeps=substeps)[1:]):
         LU, piv = torch.linalg.lu_factor(eye - (c * h) * A)                  # rocSOLVER getrf, one per output interval
         for _ in range(m):
             rhs = y + (0.5 * g * h) * (A @ y)
             yg = torch.linalg.lu_solve(LU, piv, rhs[:, None])[:, 0]
             rhs = yg / (g * (2.0 - g)) - ((1.0 - g) ** 2 / (g * (2.0 - g))) * y
             y = torch.linalg.lu_solve(LU, piv, rhs[:, None])[:, 0]
-        t_now = float(t)
         out.append((y / y.sum()).cpu().numpy().copy())
     return np.stack(out)
 
@@ -236,13 +243,156 @@ def kinetics_gpu(fast_paths, max_time, n_steps, initial_pop=None, method="auto",
     else:
         for where, weight in initial_pop:
             p0[where] = weight
-    sample_times = np.exp(np.arange(n_steps) * (max_time / n_steps) - 4)
+    sample_times = kinetics_schedule(max_time, n_steps)[0]
     times = [exp(-4)] + [t for t in sample_times]
     pops = solve_master_equation(rate, energy, p0, sample_times, method, substeps, kt)
     trajectory = [p0.cpu().numpy().copy()] + [row for row in pops]
     final = trajectory[-1]
     str_equi_pop = [(st.str_struct, st.energy, float(final[k]), k) for k, st in enumerate(struct_list)]
     return trajectory, times, struct_list, str_equi_pop
+
+
+def _batch_graph(graph):
+    """one fast_paths as the arrays of rafft_kin_batch: (L, step sizes, rows back to back, stride, energy per row, flat rows)"""
+    flat = [st for step in graph for st in step]
+    lengths = {len(st.str_struct) for st in flat}
+    if len(lengths) > 1:
+        raise ValueError(f"the structures of a graph must have one length, got {sorted(lengths)}")
+    L = lengths.pop() if lengths else 0
+    return (L, np.array([len(step) for step in graph], dtype=np.int32), "".join(st.str_struct for st in flat).encode("ascii"), L,
+            np.array([float(st.energy) for st in flat], dtype=np.float64), flat)
+
+
+def kin_batch_call(graphs, sample_times, kt=KT, substeps=32, rates=False, workspace_bytes=0, schedule=None):
+    """rafft_kin_batch (include/rafft_hip.h) on `graphs`: a list of (L, step sizes int32, rows, row stride, energy per row float64)
+    with `rows` a bytes object or an address.  -> dict of per-graph lists: status, n_rows, row0, n_unique, n_edges, uid (int32 per
+    row), first_row (int32 per unique structure), pop ((n_times, n_unique) float64; None for a graph with an error), rate (with
+    rates=True) - and `error`, the library's message about the first graph with an error.  Raises on a bad argument."""
+    import ctypes as C
+    from . import _native as N
+    n = len(graphs)
+    sample_times = np.ascontiguousarray(sample_times, dtype=np.float64)
+    _, ms, hs = schedule if schedule is not None else kinetics_schedule(sample_times=sample_times, substeps=substeps)
+    ms, hs = np.ascontiguousarray(ms, dtype=np.int32), np.ascontiguousarray(hs, dtype=np.float64)
+    nt = len(sample_times)
+    sizes = [np.ascontiguousarray(g[1], dtype=np.int32) for g in graphs]
+    energy = [np.ascontiguousarray(g[4], dtype=np.float64) for g in graphs]
+    keep = [g[2] for g in graphs]
+    addr = lambda x: x if isinstance(x, int) else C.cast(C.c_char_p(x), C.c_void_p).value
+    lens = (C.c_int * n)(*[int(g[0]) for g in graphs])
+    nst = (C.c_int * n)(*[len(s) for s in sizes])
+    stride = (C.c_int * n)(*[int(g[3]) for g in graphs])
+    p_sizes = (C.c_void_p * n)(*[s.ctypes.data for s in sizes])
+    p_rows = (C.c_void_p * n)(*[addr(r) for r in keep])
+    p_en = (C.c_void_p * n)(*[e.ctypes.data for e in energy])
+    n_rows = [int(s.sum()) for s in sizes]
+    for e, k in zip(energy, n_rows):
+        if len(e) != k:
+            raise ValueError("one energy per row")
+    total = sum(n_rows)
+    rec = (N.KinGraph * n)()
+    uid = np.full(total + 1, -1, dtype=np.int32)
+    first_row = np.full(total + 1, -1, dtype=np.int32)
+    pop = np.zeros(nt * total + 1, dtype=np.float64)
+    rate_bufs = [np.zeros(min(k, N.KIN_BATCH_MAX_STATES) ** 2, dtype=np.float64) for k in n_rows] if rates else None
+    p_rate = (C.c_void_p * n)(*[b.ctypes.data for b in rate_bufs]) if rates else None
+    D, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    N.check(N.lib().rafft_kin_batch(n, lens, nst, p_sizes, p_rows, stride, p_en, float(kt), nt, sample_times.ctypes.data_as(D), ms.ctypes.data_as(I),
+                                    hs.ctypes.data_as(D), int(workspace_bytes), rec, uid.ctypes.data_as(I), first_row.ctypes.data_as(I),
+                                    pop.ctypes.data_as(D), p_rate))
+    out = dict(status=[], n_rows=[], row0=[], n_unique=[], n_edges=[], uid=[], first_row=[], pop=[], rate=[] if rates else None,
+               error=N.lib().rafft_last_error().decode() if any(r.status for r in rec) else "")
+    for g, r in enumerate(rec):
+        S, ok = r.n_unique, r.status == N.OK
+        for key in ("status", "n_rows", "row0", "n_unique", "n_edges"):
+            out[key].append(getattr(r, key))
+        out["uid"].append(uid[r.row0:r.row0 + r.n_rows].copy())
+        out["first_row"].append(first_row[r.row0:r.row0 + S].copy() if ok else np.zeros(0, np.int32))
+        out["pop"].append(pop[nt * r.row0:nt * r.row0 + nt * S].reshape(nt, S).copy() if ok else None)
+        if rates:
+            out["rate"].append(rate_bufs[g][:S * S].reshape(S, S) if ok else None)
+    return out
+
+
+def kinetics_batch(graphs, max_time, n_steps, kt=KT, substeps=32, text_energies=True, workspace_bytes=0):
+    """`kinetics_gpu` for many graphs in ONE call, everything on the MI355X (rafft_kin_batch: structure identity, rate matrices and
+    the TR-BDF2 integration of solve_master_equation(method="implicit"), the stage matrices inverted without pivoting - DESIGN.md
+    section 6).  graphs: a list of fast_paths (as parse_rafft_output / read_sidecar / fold(traj=True) give them; `.energy` as it
+    stands), or the BatchResult of fold_batch(..., traj=True): its rows are taken from where the fold left them (no strings are
+    built; the C call packs them once for the upload), with the one-decimal energies of the `--traj` text (what the reference's rafft_kin sees) or, text_energies=False, the exact ones.
+    Returns one (trajectory, times, struct_list, str_equi_pop) per graph as kinetics_gpu does, everything starting on structure 0;
+    None for a sequence whose fold failed.  An error stays with its graph, as in the C call: a graph with more than 1024 unique
+    structures (RAFFT_ERR_CAPACITY) is solved by kinetics_gpu(method="implicit") instead, a graph with a malformed row gives None;
+    either way a RuntimeWarning carries the library's message and every other graph keeps its result."""
+    import ctypes as C
+    from . import _native as N
+    from .rafft import BatchResult
+    from .utils import Structure, energies_from_dcal, text_energy
+    sched = kinetics_schedule(max_time, n_steps, substeps)
+    arrays, flats, where = [], [], []
+    if isinstance(graphs, BatchResult):
+        if not graphs._traj:
+            raise ValueError("kinetics_batch needs the BatchResult of a fold with traj=True")
+        for i in range(len(graphs)):
+            sr = graphs._res.seq[i]
+            if sr.status != N.OK:
+                continue
+            dcal = np.ctypeslib.as_array(sr.dcal, shape=(sr.n_structs,)) if sr.n_structs else np.zeros(0, np.int32)
+            en = energies_from_dcal(dcal)
+            if text_energies:
+                uniq, inv = np.unique(en, return_inverse=True)
+                en = np.array([text_energy(e) for e in uniq.tolist()], dtype=np.float64)[inv]
+            sizes = np.ctypeslib.as_array(sr.step_size, shape=(sr.n_steps,)) if sr.n_steps else np.zeros(0, np.int32)
+            arrays.append((sr.length, sizes, C.addressof(sr.db.contents) if sr.n_structs else 0, sr.length + 1, en))
+            flats.append((sr, dcal, en))
+            where.append(i)
+        n_out = len(graphs)
+    else:
+        for i, graph in enumerate(graphs):
+            *arr, flat = _batch_graph(graph)
+            arrays.append(tuple(arr))
+            flats.append(flat)
+            where.append(i)
+        n_out = len(graphs)
+    res = kin_batch_call(arrays, sched[0], kt, substeps, workspace_bytes=workspace_bytes, schedule=sched)
+    times = [exp(-4)] + [t for t in sched[0]]
+    out = [None] * n_out
+    failed = [k for k, s in enumerate(res["status"]) if s]
+    if failed:
+        import warnings
+        over = [where[k] for k in failed if res["status"][k] == N.ERR_CAPACITY]
+        warnings.warn(f"kinetics_batch: {len(failed)} of {len(where)} graphs not solved by the batch call ({res['error']}); "
+                      f"graphs {over} go through kinetics_gpu(method='implicit'), the others give None", RuntimeWarning, stacklevel=2)
+    for k, i in enumerate(where):
+        if res["status"][k] == N.ERR_CAPACITY:
+            if isinstance(flats[k], list):
+                graph = graphs[i]
+            else:
+                sr, dcal, en = flats[k]
+                w, at, graph = sr.length + 1, 0, []
+                for size in arrays[k][1].tolist():
+                    graph.append([Structure(C.string_at(C.addressof(sr.db.contents) + r * w, sr.length).decode("ascii"), int(dcal[r]), float(en[r]))
+                                  for r in range(at, at + size)])
+                    at += size
+            out[i] = kinetics_gpu(graph, max_time, n_steps, None, "implicit", substeps, kt)
+            continue
+        if res["status"][k]:
+            continue
+        S, rows = res["n_unique"][k], res["first_row"][k]
+        if isinstance(flats[k], list):
+            struct_list = [flats[k][r] for r in rows]
+        else:
+            sr, dcal, en = flats[k]
+            w = sr.length + 1
+            struct_list = [Structure(C.string_at(C.addressof(sr.db.contents) + int(r) * w, sr.length).decode("ascii"), int(dcal[r]), float(en[r]))
+                           for r in rows]
+        p0 = np.zeros(S, dtype=np.float64)
+        if S:
+            p0[0] = 1.0
+        trajectory = [p0] + [row for row in res["pop"][k]]
+        final = trajectory[-1]
+        out[i] = (trajectory, times, struct_list, [(st.str_struct, st.energy, float(final[u]), u) for u, st in enumerate(struct_list)])
+    return out
 
 
 def main(argv=None):

@@ -181,6 +181,11 @@ def write_sidecar(path, sequence, trajectory):
             fh.write(row)
 
 
+def text_energy(energy):
+    """an energy as a reader of the `--traj` text sees it: the one decimal of `{:6.1f}` (bin/rafft:77-78)"""
+    return float(f"{energy:6.1f}")
+
+
 def read_sidecar(path, text_energies=False):
     """-> (fast_paths, sequence), the same shape parse_rafft_output returns, with exact dcal energies.
     text_energies=True rounds `.energy` to the one decimal the `--traj` text carries (bin/rafft:77-78), which is
@@ -205,7 +210,7 @@ def read_sidecar(path, text_energies=False):
         for _ in range(int(n)):
             st = Structure(buf[o + k * L:o + (k + 1) * L].decode("ascii"), int(dcal[k]))
             if text_energies:
-                st.energy = float(f"{st.energy:6.1f}")
+                st.energy = text_energy(st.energy)
             step.append(st)
             k += 1
         fast_paths.append(step)
