@@ -319,6 +319,35 @@ int rafft_score_rows(int n_seq, const int *lens, const int *n_rows, const char *
  * that status and has no rows.  row_out (may be NULL) holds the sum of the final beams' sizes. */
 int rafft_score_result(const rafft_result *r, const char *const *known, rafft_score_row *row_out, rafft_score_seq *seq_out);
 
+/* Minimum-free-energy structures of a batch.  Replaces: RNA.fold(seq), benchmark_results/src/vrna_mfe.py:25,
+ * which benchmark_results/bench_mfe.py:11-15 runs with one process per sequence to make the comparison column mfe_scores.csv.
+ * RNA.fold's defaults are dangles=2, lonely pairs allowed and interior loops of up to 30 unpaired positions; so is this: Zuker's
+ * recurrences in integer dcal over the loop energies rafft_eval_structure uses, hence dcal = the minimum of rafft_eval_structure
+ * over all structures with canonical pairs, hairpins of at least 3 and interior loops of at most 30, and rafft_eval_structure of
+ * the returned row gives dcal again.  Among structures of equal energy the traceback's fixed candidate order decides: the row is a
+ * function of the sequence and the energy tables alone - not of the batch, its order, the size class or the workspace.
+ * Sequences of up to rafft_mfe_lds_len() nt keep their tables in LDS, one workgroup each; longer ones (up to RAFFT_MFE_MAX_LEN)
+ * have 3 x L x L int32 tables in device memory and are processed in chunks that fit workspace_bytes (0: 512 MiB; one sequence at
+ * least - 192 MiB at 4096 nt).  max_lds_len: 0 for the library's bound; a lower value sends shorter sequences through the
+ * device-memory class as well (tests, measurements).  temp as in rafft_params.
+ * Outputs (host): seq_out[s]; db_out[s] = lens[s] + 1 bytes for the NUL-terminated dot-bracket row.
+ * RAFFT_ERR_BAD_CHAR, RAFFT_ERR_EMPTY and RAFFT_ERR_TOO_LONG (above RAFFT_MFE_MAX_LEN) are errors of that sequence only: its row
+ * is all dots, the call returns RAFFT_OK and rafft_last_error() names the first such sequence.  RAFFT_ERR_PARAM, before anything
+ * is launched: a null argument, a negative count, max_lds_len above rafft_mfe_lds_len().  RAFFT_ERR_TEMP as for the fold. */
+#define RAFFT_MFE_MAX_LEN 4096
+typedef struct {
+    int32_t status;
+    int32_t length;
+    int32_t dcal;        /* minimum free energy in dcal/mol (<= 0: the open chain has 0) */
+    int32_t n_pairs;     /* pairs of the row */
+} rafft_mfe_seq;         /* 16 bytes */
+int rafft_mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                    int max_lds_len,            /* 0: the library's bound; lower values route shorter sequences through the HBM class (tests, measurements) */
+                    long long workspace_bytes,  /* 0: 512 MiB */
+                    rafft_mfe_seq *seq_out, char *const *db_out /* db_out[s]: lens[s] + 1 bytes, NUL terminated */);
+/* the longest sequence whose tables fit the LDS class */
+int rafft_mfe_lds_len(void);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

@@ -50,6 +50,10 @@ _OPTIONS = [
     (("--kin",), dict(metavar="OUT", help="with -sf FILE --batch: fold with trajectories and solve the folding kinetics of every sequence's\n"
                                           "fast-folding graph on the GPU, all in one call (rafft_kin.kinetics_batch).  OUT gets, per sequence,\n"
                                           "a `> index sequence` line and the table `rafft_kin` prints, sorted by final population")),
+    (("--mfe",), dict(action="store_true", help="no RAFFT fold: the minimum-free-energy structure of every sequence on the GPU (rafft_amd.mfe_batch;\n"
+                                                "dangles=2, lonely pairs allowed, interior loops up to 30 - RNA.fold's defaults), one line per sequence as\n"
+                                                "benchmark_results/src/vrna_mfe.py prints it: seq len structure energy #pairs.  With --scores the table of\n"
+                                                "mfe_scores.csv.  Works with -s SEQ and with -sf FILE --batch")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
     (("--output", "-o"), dict(help="write the result there instead of stdout")),
@@ -179,6 +183,34 @@ def format_result(sequence, result, args):
     return "\n".join(out)
 
 
+def format_mfe_line(sequence, struct):
+    """the line of benchmark_results/src/vrna_mfe.py:26"""
+    return f"{sequence} {len(sequence)} {struct.str_struct} {struct.energy} {struct.str_struct.count('(')}"
+
+
+def main_mfe(args, seqs, known, names, mfe_batch=None, scorer=None):
+    """--mfe: the MFE structures instead of the fold.  `scorer`: the callable (rows per sequence, known) -> score table that stands
+    in for scoring.score_rows_gpu."""
+    if args.kin or args.traj:
+        raise SystemExit("--mfe gives one structure per sequence: no --kin, no --traj")
+    if mfe_batch is None:
+        from .zuker import mfe_batch
+    structs = mfe_batch(seqs, args.temp)
+    if args.scores:
+        if scorer is None:
+            from .scoring import score_rows_gpu as scorer
+        beams = [[st] for st in structs]
+        write_scores(args.scores, seqs, names, beams, scorer(beams, known), "energy")
+        if not args.output:
+            return
+    text = "".join(format_mfe_line(s, st) + "\n" for s, st in zip(seqs, structs))
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def _table_note():
     """one line on stderr when the fold used rule / model values of the built-in tables (never with ViennaRNA's own tables loaded)"""
     try:
@@ -193,10 +225,10 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None, kinetics=None):
-    """`fold_batch` / `scorer` / `kinetics`: injection points for tests (the fold, the callable (results, known) -> score table that
-    stands in for scoring.score_batch_gpu, and the callable (results, max_time, n_steps) that stands in for
-    rafft_kin.kinetics_batch)."""
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None):
+    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch`: injection points for tests (the fold, the callable (results, known) -> score
+    table that stands in for scoring.score_batch_gpu - with --mfe for scoring.score_rows_gpu -, the callable (results, max_time,
+    n_steps) that stands in for rafft_kin.kinetics_batch, and the callable (sequences, temp) that stands in for zuker.mfe_batch)."""
     args = parse_arguments(argv)
     seqs, known, names = read_records(args)
     if args.kin:
@@ -208,6 +240,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None):
             raise SystemExit("--scores needs -sf CSV --batch with a known structure per sequence "
                              f"(column {args.known_column!r}, or the headerless seq,struct,name file)")
         names = names if names is not None else [""] * len(seqs)
+    if args.mfe:
+        return main_mfe(args, seqs, known, names, mfe_batch, scorer)
     if fold_batch is None:
         from .rafft import fold_batch
     results = fold_batch(seqs, args.n_mode, args.max_stack, args.max_branch, args.min_hp, args.min_nrj, args.traj,

@@ -38,6 +38,7 @@
 #include "rafft_kin_batch.hip"
 #include "rafft_landscape.hip"
 #include "rafft_score.hip"
+#include "rafft_mfe.hip"
 
 // host side, one responsibility per file (each in its own anonymous namespace)
 #include "rafft_host_ctx.h"     // errors, workspaces and their buffers, the global context, memory pools, initialisation
@@ -327,5 +328,18 @@ int rafft_score_result(const rafft_result *r, const char *const *known, rafft_sc
     if (!r || r->n_seq < 0 || (r->n_seq > 0 && (!r->seq || !known || !seq_out))) return fail(RAFFT_ERR_PARAM, "bad argument");
     return score_result(r, known, row_out, seq_out);
 }
+
+int rafft_mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int max_lds_len, long long workspace_bytes,
+                    rafft_mfe_seq *seq_out, char *const *db_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || max_lds_len < 0 || max_lds_len > RAFFT_MFE_LDS_LEN || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_seq > 0 && (!seqs || !lens || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int s = 0; s < n_seq; s++)
+        if (!db_out[s] || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    return mfe_batch(n_seq, seqs, lens, temp, max_lds_len ? max_lds_len : RAFFT_MFE_LDS_LEN, workspace_bytes, seq_out, db_out);
+}
+
+int rafft_mfe_lds_len(void) { return RAFFT_MFE_LDS_LEN; }
 
 } // extern "C"

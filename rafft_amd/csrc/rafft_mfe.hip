@@ -1,0 +1,332 @@
+// rafft_mfe.hip - minimum-free-energy folds of a batch (gfx950): Zuker's recurrences in integer dcal over the device functions of
+// rafft_device.h (e_hairpin, e_intloop, e_stem - the energy model is stated there and nowhere else), and the traceback.
+// DESIGN.md section 9.  Included by rafft_api.hip, after rafft_kernels.hip (wave_sync).
+//
+//   C[i][j]   (i,j) pair: hairpin | interior loop with inner pair (p,q), n1 + n2 <= 30 | multiloop closed by (i,j)
+//   M1[i][j]  exactly one stem, starting at i, ending at or before j: min(C[i][j] + stem(i,j), M1[i][j-1] + ml_base)
+//   M[i][j]   at least one stem in i..j: min(M1[i][j], M[i+1][j] + ml_base, min_k M[i][k-1] + M1[k][j])
+//   F[j]      exterior loop of 0..j: min(F[j-1], min_i F[i-1] + C[i][j] + stem_ext(i,j))
+// The value of a cell is the minimum over its candidates, whatever their order.  The traceback visits the candidates of a cell in ONE
+// fixed order and takes the first that reproduces the stored value, so the structure is a function of the sequence and the tables:
+//   C:  hairpin; interior loops, p ascending then q descending; multiloop splits, k ascending
+//   M1: the stem (i,j); j unpaired
+//   M:  M1[i][j]; i unpaired; splits, k ascending
+//   F:  j unpaired; stems (i,j), i ascending
+// Two size classes share mfe_cell and mfe_traceback through a table view: triangular tables in LDS (mfe_lds_kernel, one workgroup per
+// sequence, a barrier per anti-diagonal) and full L x L tables in HBM (mfe_diag_kernel, one launch per anti-diagonal: stream order
+// is the synchronisation; mfe_traceback_kernel).
+#pragma once
+
+#define MFE_INF 1000000000          // "no structure"; two of them still add up inside an int
+#define MFE_INFH 500000000          // every real energy lies below, every sum with an MFE_INF above
+#define MFE_MAXLOOP 30              // unpaired positions of an interior loop (RNA.fold's default)
+#define MFE_NIL 496                 // pairs (n1, n2) with n1 + n2 <= 30
+#define MFE_LDS_NT 512
+#define MFE_HBM_NT 256
+#define MFE_LDS_BYTES (128 << 10)
+// LDS class: three triangular int32 tables of L (L + 1) / 2 cells, F (L + 1 ints) and the bases (L bytes, padded to 16) in 128 KiB
+#define RAFFT_MFE_LDS_LEN 146
+__host__ __device__ constexpr int mfe_lds_bytes(int L) { return (3 * (L * (L + 1) / 2) + L + 1) * 4 + ((L + 15) & ~15); }
+static_assert(mfe_lds_bytes(RAFFT_MFE_LDS_LEN) <= MFE_LDS_BYTES && mfe_lds_bytes(RAFFT_MFE_LDS_LEN + 1) > MFE_LDS_BYTES, "RAFFT_MFE_LDS_LEN is what 128 KiB hold");
+
+// (n1 << 8 | n2) of interior-loop candidate x: n1 ascending, then n2 ascending - p ascending, then q descending
+struct MfeIlTable {
+    unsigned short v[MFE_NIL];
+    constexpr MfeIlTable() : v()
+    {
+        int x = 0;
+        for (int n1 = 0; n1 <= MFE_MAXLOOP; n1++)
+            for (int n2 = 0; n1 + n2 <= MFE_MAXLOOP; n2++) v[x++] = (unsigned short)(n1 << 8 | n2);
+    }
+};
+__constant__ MfeIlTable mfe_il = MfeIlTable();
+
+struct MfeSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long tab_off;     // HBM class: first int of the sequence's three L x L tables in the workspace
+    unsigned long long stack_off;   // first word of its traceback stack (L + 8 words)
+    unsigned long long db_off;      // its row in the output (L + 1 bytes)
+    int L, pad;
+};
+
+// table views: c / m / m1 are cell (i, j), i <= j.  The split loops read M along a row (k - 1 varies) and M1 along a column
+// (k varies), so M is stored by rows and M1 by columns: the 64 lanes of a split read 64 consecutive words of each.
+struct MfeTabLds {
+    int *C, *M, *M1;
+    int L;
+    __device__ __forceinline__ int row(int i, int j) const { return i * L - ((i * (i - 1)) >> 1) + (j - i); }
+    __device__ __forceinline__ int col(int i, int j) const { return ((j * (j + 1)) >> 1) + i; }
+    __device__ __forceinline__ int &c(int i, int j) const { return C[row(i, j)]; }
+    __device__ __forceinline__ int &m(int i, int j) const { return M[row(i, j)]; }
+    __device__ __forceinline__ int &m1(int i, int j) const { return M1[col(i, j)]; }
+};
+struct MfeTabHbm {
+    int *C, *M, *M1T;
+    int L;
+    __device__ __forceinline__ int &c(int i, int j) const { return C[(size_t)i * L + j]; }
+    __device__ __forceinline__ int &m(int i, int j) const { return M[(size_t)i * L + j]; }
+    __device__ __forceinline__ int &m1(int i, int j) const { return M1T[(size_t)j * L + i]; }
+};
+
+// minimum over the 64 lanes of a wavefront (all of them active), the same in every lane: the DPP steps of wave_incl_scan with min
+__device__ __forceinline__ int mfe_wave_min(int x)
+{
+    x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x111, 0xF, 0xF, false));
+    x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x112, 0xF, 0xF, false));
+    x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x114, 0xF, 0xF, false));
+    x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x118, 0xF, 0xF, false));
+    x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x142, 0xA, 0xF, false));
+    x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x143, 0xC, 0xF, false));
+    return __builtin_amdgcn_readlane(x, 63);
+}
+
+// a stem (i,j) as a branch of a multiloop.  Inside a multiloop both neighbours exist; cells on the sequence's border are filled
+// too (nothing reads them) and must not read outside the sequence
+__device__ __forceinline__ int mfe_stem_ml(const SmallT *T, const uint8_t *S, int L, int i, int j)
+{
+    return e_stem(T, pair_type(S[i], S[j]), i > 0 ? (int)S[i - 1] : -1, j < L - 1 ? (int)S[j + 1] : -1, false);
+}
+__device__ __forceinline__ int mfe_stem_ext(const SmallT *T, const uint8_t *S, int L, int i, int j)
+{
+    return e_stem(T, pair_type(S[i], S[j]), i > 0 ? (int)S[i - 1] : -1, j < L - 1 ? (int)S[j + 1] : -1, true);
+}
+// interior-loop candidate x of the pair (i,j) of type t: its energy with C[p][q], MFE_INF when there is no such loop
+template <class Tab>
+__device__ __forceinline__ int mfe_interior(const Tab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int i, int j, int t, int x, int &p, int &q)
+{
+    const int n12 = mfe_il.v[x], n1 = n12 >> 8, n2 = n12 & 255;
+    p = i + 1 + n1; q = j - 1 - n2;
+    if (q - p < 4) return MFE_INF;
+    const int t2 = pair_type(S[p], S[q]);
+    if (!t2) return MFE_INF;
+    const int cc = tb.c(p, q);
+    if (cc >= MFE_INFH) return MFE_INF;
+    int g = 0;
+    return e_intloop(T, B, n1, n2, t, rtype(t2), S[i + 1], S[j - 1], S[p - 1], S[q + 1], g) + cc;
+}
+// what closing a multiloop with (i,j) of type t adds to its inside M[i+1][k-1] + M1[k][j-1]
+__device__ __forceinline__ int mfe_ml_close(const SmallT *T, const uint8_t *S, int i, int j, int t)
+{
+    return T->ml_closing + e_stem(T, rtype(t), S[j - 1], S[i + 1], false);
+}
+
+// one wavefront fills cell (i,j) of the three tables; every cell of a smaller j - i is there
+template <class Tab>
+__device__ inline void mfe_cell(const Tab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, int i, int j, int lane)
+{
+    const int d = j - i;
+    int c = MFE_INF, m1 = MFE_INF, m = MFE_INF;
+    if (d >= 4) {
+        const int t = pair_type(S[i], S[j]);
+        if (t) {
+            int best = MFE_INF;
+            if (lane == 0) best = e_hairpin(T, B, d - 1, t, S, i, j);
+            for (int x = lane; x < MFE_NIL; x += 64) {
+                int p, q;
+                best = min(best, mfe_interior(tb, T, B, S, i, j, t, x, p, q));
+            }
+            int ml = MFE_INF;                       // a stem takes five positions: k - 1 >= i + 5, k <= j - 5
+            for (int k = i + 6 + lane; k <= j - 5; k += 64) {
+                const int a = tb.m(i + 1, k - 1), b = tb.m1(k, j - 1);
+                if (a < MFE_INFH && b < MFE_INFH) ml = min(ml, a + b);
+            }
+            if (ml < MFE_INFH) best = min(best, ml + mfe_ml_close(T, S, i, j, t));
+            c = mfe_wave_min(best);
+            if (c < MFE_INFH) m1 = c + mfe_stem_ml(T, S, L, i, j);
+        }
+        const int mlb = T->ml_base;
+        const int prev = tb.m1(i, j - 1);
+        if (prev < MFE_INFH) m1 = min(m1, prev + mlb);
+        m = m1;
+        const int nx = tb.m(i + 1, j);
+        if (nx < MFE_INFH) m = min(m, nx + mlb);
+        int sp = MFE_INF;
+        for (int k = i + 5 + lane; k <= j - 4; k += 64) {
+            const int a = tb.m(i, k - 1), b = tb.m1(k, j);
+            if (a < MFE_INFH && b < MFE_INFH) sp = min(sp, a + b);
+        }
+        m = min(m, mfe_wave_min(sp));
+    }
+    if (lane == 0) { tb.c(i, j) = c; tb.m1(i, j) = m1; tb.m(i, j) = m; }
+}
+
+// One wavefront: the exterior loop, then the traceback with an explicit stack of (i, j, table) words.  F: L + 1 ints of LDS (F[j + 1]
+// = exterior energy of 0..j; the pair table once the exterior loop is traced).  `stack`: `cap` words only lane 0 touches.
+// rec = (dcal, pairs, 1 when no candidate reproduced a cell - an internal error, 0)
+enum { MFE_K_C = 0, MFE_K_M = 1, MFE_K_M1 = 2 };
+template <class Tab>
+__device__ inline void mfe_traceback(const Tab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, int *F, uint32_t *stack, int cap,
+                                     char *db, int4 *rec, int lane)
+{
+    if (lane == 0) F[0] = 0;
+    wave_sync();
+    for (int j = 0; j < L; j++) {
+        int best = MFE_INF;
+        for (int i = lane; i <= j - 4; i += 64) {
+            const int c = tb.c(i, j);
+            if (c < MFE_INFH) best = min(best, F[i] + c + mfe_stem_ext(T, S, L, i, j));
+        }
+        best = mfe_wave_min(best);
+        const int prev = F[j];
+        if (lane == 0) F[j + 1] = min(prev, best);
+        wave_sync();
+    }
+    const int mfe = F[L];
+    int sp = 0, npairs = 0, bad = 0;
+    auto push = [&](int i, int j, int kind) {
+        if (sp >= cap) { bad = 1; return; }
+        if (lane == 0) stack[sp] = (uint32_t)i | (uint32_t)j << 12 | (uint32_t)kind << 24;
+        sp++;
+    };
+    for (int j = L - 1; j >= 4 && !bad;) {
+        const int v = F[j + 1];
+        if (v == F[j]) { j--; continue; }
+        int found = -1;
+        for (int i0 = 0; i0 <= j - 4 && found < 0; i0 += 64) {
+            const int i = i0 + lane;
+            bool hit = false;
+            if (i <= j - 4) {
+                const int c = tb.c(i, j);
+                hit = c < MFE_INFH && F[i] + c + mfe_stem_ext(T, S, L, i, j) == v;
+            }
+            const unsigned long long bal = __ballot(hit);
+            if (bal) found = i0 + __ffsll((long long)bal) - 1;
+        }
+        if (found < 0) { bad = 1; break; }
+        push(found, j, MFE_K_C);
+        j = found - 1;
+    }
+    wave_sync();
+    int *pt = F;
+    for (int x = lane; x < L; x += 64) pt[x] = -1;
+    wave_sync();
+    const int mlb = T->ml_base;
+    while (sp > 0 && !bad) {
+        sp--;
+        uint32_t w = 0;
+        if (lane == 0) w = stack[sp];
+        w = (uint32_t)__shfl((int)w, 0, 64);
+        int i = (int)(w & 4095u), j = (int)((w >> 12) & 4095u), kind = (int)(w >> 24);
+        if (kind == MFE_K_M) {
+            for (;;) {
+                const int v = tb.m(i, j);
+                if (tb.m1(i, j) == v) { kind = MFE_K_M1; break; }
+                if (j > i) {
+                    const int nx = tb.m(i + 1, j);
+                    if (nx < MFE_INFH && nx + mlb == v) { i++; continue; }
+                }
+                int found = -1;
+                for (int k0 = i + 5; k0 <= j - 4 && found < 0; k0 += 64) {
+                    const int k = k0 + lane;
+                    bool hit = false;
+                    if (k <= j - 4) {
+                        const int a = tb.m(i, k - 1), b = tb.m1(k, j);
+                        hit = a < MFE_INFH && b < MFE_INFH && a + b == v;
+                    }
+                    const unsigned long long bal = __ballot(hit);
+                    if (bal) found = k0 + __ffsll((long long)bal) - 1;
+                }
+                if (found < 0) { bad = 1; break; }
+                push(i, found - 1, MFE_K_M);
+                i = found; kind = MFE_K_M1;
+                break;
+            }
+        }
+        if (!bad && kind == MFE_K_M1) {
+            for (;;) {
+                const int v = tb.m1(i, j), c = tb.c(i, j);
+                if (c < MFE_INFH && c + mfe_stem_ml(T, S, L, i, j) == v) { kind = MFE_K_C; break; }
+                if (j > i) {
+                    const int prev = tb.m1(i, j - 1);
+                    if (prev < MFE_INFH && prev + mlb == v) { j--; continue; }
+                }
+                bad = 1;
+                break;
+            }
+        }
+        if (bad || kind != MFE_K_C) continue;
+        if (lane == 0) { pt[i] = j; pt[j] = i; }
+        npairs++;
+        const int v = tb.c(i, j), t = pair_type(S[i], S[j]);
+        if (!t || v >= MFE_INFH) { bad = 1; continue; }
+        if (e_hairpin(T, B, j - i - 1, t, S, i, j) == v) continue;
+        int found = -1;
+        for (int x0 = 0; x0 < MFE_NIL && found < 0; x0 += 64) {
+            const int x = x0 + lane;
+            int p, q;
+            const bool hit = x < MFE_NIL && mfe_interior(tb, T, B, S, i, j, t, x, p, q) == v;
+            const unsigned long long bal = __ballot(hit);
+            if (bal) found = x0 + __ffsll((long long)bal) - 1;
+        }
+        if (found >= 0) {
+            const int n12 = mfe_il.v[found];
+            push(i + 1 + (n12 >> 8), j - 1 - (n12 & 255), MFE_K_C);
+            continue;
+        }
+        const int close = mfe_ml_close(T, S, i, j, t);
+        for (int k0 = i + 6; k0 <= j - 5 && found < 0; k0 += 64) {
+            const int k = k0 + lane;
+            bool hit = false;
+            if (k <= j - 5) {
+                const int a = tb.m(i + 1, k - 1), b = tb.m1(k, j - 1);
+                hit = a < MFE_INFH && b < MFE_INFH && a + b + close == v;
+            }
+            const unsigned long long bal = __ballot(hit);
+            if (bal) found = k0 + __ffsll((long long)bal) - 1;
+        }
+        if (found < 0) { bad = 1; continue; }
+        push(i + 1, found - 1, MFE_K_M);
+        push(found, j - 1, MFE_K_M1);
+    }
+    wave_sync();
+    for (int x = lane; x < L; x += 64) { const int y = pt[x]; db[x] = y < 0 ? '.' : y > x ? '(' : ')'; }
+    if (lane == 0) { db[L] = 0; *rec = make_int4(mfe, npairs, bad, 0); }
+}
+
+// LDS class: workgroup b folds sequence order[b]
+__global__ __launch_bounds__(MFE_LDS_NT) void mfe_lds_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes,
+                                                            uint32_t *stacks, char *db, int4 *rec)
+{
+    extern __shared__ __align__(16) int mfe_lds[];
+    const int s = order[blockIdx.x];
+    const MfeSeq q = seqs[s];
+    const int L = q.L, N = L * (L + 1) / 2, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const MfeTabLds tb{mfe_lds, mfe_lds + N, mfe_lds + 2 * N, L};
+    int *F = mfe_lds + 3 * N;
+    uint8_t *S = (uint8_t *)(F + L + 1);
+    for (int x = tid; x < L; x += MFE_LDS_NT) S[x] = codes[q.code_off + x];
+    __syncthreads();
+    const SmallT *T = &ET->s;
+    const BigT *B = &ET->b;
+    for (int d = 0; d < L; d++) {
+        for (int i = wave; i + d < L; i += MFE_LDS_NT / 64) mfe_cell(tb, T, B, S, L, i, i + d, lane);
+        __syncthreads();
+    }
+    if (wave == 0) mfe_traceback(tb, T, B, S, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, lane);
+}
+
+// HBM class: anti-diagonal d of the sequences order[0 .. gridDim.y), four cells per workgroup and round
+__global__ __launch_bounds__(MFE_HBM_NT) void mfe_diag_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes, int *tabs, int d)
+{
+    const MfeSeq q = seqs[order[blockIdx.y]];
+    const int L = q.L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (d >= L) return;
+    int *t0 = tabs + q.tab_off;
+    const size_t LL = (size_t)L * L;
+    const MfeTabHbm tb{t0, t0 + LL, t0 + 2 * LL, L};
+    const uint8_t *S = codes + q.code_off;
+    for (int i = blockIdx.x * (MFE_HBM_NT / 64) + wave; i + d < L; i += gridDim.x * (MFE_HBM_NT / 64)) mfe_cell(tb, &ET->s, &ET->b, S, L, i, i + d, lane);
+}
+
+__global__ __launch_bounds__(64) void mfe_traceback_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes, int *tabs,
+                                                          uint32_t *stacks, char *db, int4 *rec)
+{
+    __shared__ int F[RAFFT_MFE_MAX_LEN + 1];
+    const int s = order[blockIdx.x];
+    const MfeSeq q = seqs[s];
+    const int L = q.L;
+    int *t0 = tabs + q.tab_off;
+    const size_t LL = (size_t)L * L;
+    const MfeTabHbm tb{t0, t0 + LL, t0 + 2 * LL, L};
+    mfe_traceback(tb, &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, (int)threadIdx.x);
+}

@@ -1,7 +1,7 @@
 // rafft_seam.h - the seam calls: entry points that drain the folds in flight and borrow workspace 0 on the caller's thread.
 // What they share is written once here - how such a call enters (SeamGuard) and who owns its device buffers (DevScratch) -
 // followed by the calls themselves: structure evaluation, rafft_expand_node, and the drivers of the feature kernels (the kinetics
-// rate matrix, the folding landscape, accuracy scoring).
+// rate matrix, the folding landscape, accuracy scoring, minimum-free-energy folds).
 // Part of the single translation unit of rafft_api.hip (included there, after rafft_submit.h).
 #pragma once
 
@@ -636,6 +636,120 @@ int score_result(const rafft_result *r, const char *const *known, rafft_score_ro
         rows_bytes = pack.size();
     }
     return score_held(sg.stream, n_seq, lens.data(), n_rows.data(), stride.data(), rows_off.data(), pre.data(), src, rows_bytes, known, row_out, seq_out);
+}
+
+// ---- minimum-free-energy folds
+
+constexpr size_t MFE_WORKSPACE = (size_t)512 << 20;
+
+// rafft_mfe_batch (arguments validated by the entry point).  Sequences up to `lds_len` go through mfe_lds_kernel in one launch, the
+// others through the HBM class in chunks whose tables fit the workspace budget (one sequence at least): per chunk one launch per
+// anti-diagonal, then the traceback.  One synchronise at the end.
+int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int lds_len, long long workspace_bytes, rafft_mfe_seq *seq_out,
+              char *const *db_out)
+{
+    // as the fold's entry (validate_params): before any sequence is looked at, so a batch of nothing but erroneous sequences fails too
+    if (!(temp > -273.15 && temp < 1000.0)) return fail(RAFFT_ERR_TEMP, "temp out of range");
+    if (temp != 37.0 && !param_set().has_dH)
+        return fail(RAFFT_ERR_TEMP, "temp != 37 needs the enthalpy tables of a ViennaRNA parameter file (rafft_load_params); the built-in tables are 37 C only");
+    if (n_seq == 0) return 0;
+    std::vector<MfeSeq> qs(n_seq);
+    std::vector<int> lds_order, hbm_order;
+    unsigned long long n_codes = 0, n_stack = 0, n_db = 0;
+    std::string first_err;
+    for (int s = 0; s < n_seq; s++) {
+        int st = 0;
+        if (lens[s] <= 0) st = RAFFT_ERR_EMPTY;
+        else if (lens[s] > RAFFT_MFE_MAX_LEN) st = RAFFT_ERR_TOO_LONG;
+        else for (int x = 0; x < lens[s] && !st; x++) if (kBaseCode[(unsigned char)seqs[s][x]] & 8) st = RAFFT_ERR_BAD_CHAR;
+        const int len = lens[s] > 0 ? lens[s] : 0;
+        seq_out[s] = rafft_mfe_seq{st, len, 0, 0};
+        memset(db_out[s], '.', (size_t)len);
+        db_out[s][len] = 0;
+        qs[s] = MfeSeq{n_codes, 0, n_stack, n_db, st ? 0 : len, 0};
+        if (st) {
+            if (first_err.empty())
+                first_err = "sequence " + std::to_string(s) + (st == RAFFT_ERR_EMPTY ? ": empty" : st == RAFFT_ERR_TOO_LONG ? ": longer than RAFFT_MFE_MAX_LEN" : ": character outside ACGUN");
+            continue;
+        }
+        n_codes += (unsigned long long)len; n_stack += (unsigned long long)len + 8; n_db += (unsigned long long)len + 1;
+        (len <= lds_len ? lds_order : hbm_order).push_back(s);
+    }
+    g_err = first_err;
+    if (lds_order.empty() && hbm_order.empty()) return 0;
+    std::vector<uint8_t> codes(n_codes + 16, 0);
+    for (int s = 0; s < n_seq; s++)
+        for (int x = 0; x < qs[s].L; x++) codes[qs[s].code_off + x] = (uint8_t)(kBaseCode[(unsigned char)seqs[s][x]] & 7);
+    // the longest first: the workgroups of a launch that run last are the short ones
+    std::stable_sort(lds_order.begin(), lds_order.end(), [&](int a, int b) { return qs[a].L > qs[b].L; });
+    // chunks of the HBM class, in input order
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE;
+    struct Chunk { size_t a, b; int Lmax; };
+    std::vector<Chunk> chunks;
+    size_t ws_max = 0;
+    for (size_t a = 0; a < hbm_order.size();) {
+        size_t w = 0, b = a;
+        int Lmax = 0;
+        while (b < hbm_order.size() && b - a < 65535) {
+            MfeSeq &q = qs[hbm_order[b]];
+            const size_t dw = 3 * (size_t)q.L * q.L * 4;
+            if (b > a && w + dw > budget) break;
+            q.tab_off = w / 4;
+            w += dw; Lmax = std::max(Lmax, q.L); b++;
+        }
+        chunks.push_back(Chunk{a, b, Lmax});
+        ws_max = std::max(ws_max, w);
+        a = b;
+    }
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    if (int rc = ensure_tables(temp)) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    MfeSeq *d_qs; uint8_t *d_codes; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr;
+    std::vector<int> order(lds_order);
+    order.insert(order.end(), hbm_order.begin(), hbm_order.end());
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSeq))) return rc;
+    if (int rc = mem.alloc(d_codes, codes.size())) return rc;
+    if (int rc = mem.alloc(d_stack, n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (ws_max) if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
+    if (!lds_order.empty()) {
+        HIPCHK(hipFuncSetAttribute((const void *)mfe_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MFE_LDS_BYTES));
+        hipLaunchKernelGGL(mfe_lds_kernel, dim3((unsigned)lds_order.size()), dim3(MFE_LDS_NT), (size_t)mfe_lds_bytes(qs[lds_order[0]].L), st, g.T, d_qs, d_order,
+                           d_codes, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    for (const Chunk &c : chunks) {
+        const int *ord = d_order + lds_order.size() + c.a;
+        const unsigned ny = (unsigned)(c.b - c.a);
+        for (int d = 0; d < c.Lmax; d++) {
+            const unsigned nx = (unsigned)std::min((c.Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
+            hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d);
+        }
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mfe_traceback_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<int4> rec(n_seq);
+    std::vector<char> db(n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
+        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
+        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    g_err = first_err;
+    return 0;
 }
 
 } // namespace

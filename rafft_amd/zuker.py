@@ -1,0 +1,48 @@
+"""Minimum-free-energy structures on the GPU (rafft_mfe_batch): what the reference gets from ViennaRNA's
+RNA.fold for the comparison column of its benchmark (benchmark_results/src/vrna_mfe.py:25, bench_mfe.py:11-15)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from . import params as _params_mod
+from .rafft import _raise_like_reference
+from .utils import Structure, energies_from_dcal
+
+
+def mfe_batch_raw(sequences, temp=37.0, max_lds_len=0, workspace_bytes=0):
+    """(rows, dcal, n_pairs, status) of rafft_mfe_batch: dot-bracket strings and three int lists, one entry per sequence; nothing is
+    raised for a sequence's own error (its row is all dots).  max_lds_len / workspace_bytes as in include/rafft_hip.h."""
+    L = N.lib()
+    _params_mod.ensure_default_params()
+    n = len(sequences)
+    enc = [s.encode("ascii", "replace") for s in sequences]
+    arr = (C.c_char_p * n)(*enc)
+    lens = (C.c_int * n)(*map(len, enc))
+    bufs = [C.create_string_buffer(len(e) + 1) for e in enc]
+    out = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+    rec = (N.MfeSeq * n)()
+    N.check(L.rafft_mfe_batch(n, arr, lens, float(temp), int(max_lds_len), int(workspace_bytes), rec, out))
+    return ([b.value.decode("ascii") for b in bufs], [r.dcal for r in rec], [r.n_pairs for r in rec], [r.status for r in rec])
+
+
+def mfe_batch(sequences, temp=37.0, raise_errors=True):
+    """The MFE structure of every sequence, as a list of utils.Structure.  A sequence with an error raises what fold_batch raises
+    for it (raise_errors=False: its entry is None)."""
+    rows, dcal, _, status = mfe_batch_raw(sequences, temp)
+    en = energies_from_dcal(np.asarray(dcal, dtype=np.int32)).tolist() if rows else []
+    out = []
+    for k, s in enumerate(sequences):
+        if status[k] != N.OK:
+            if raise_errors:
+                if status[k] == N.ERR_TOO_LONG:
+                    raise ValueError(f"sequence of {len(s)} nt: mfe_batch takes up to {N.MFE_MAX_LEN} nt (RAFFT_MFE_MAX_LEN)")
+                _raise_like_reference(status[k], s)
+            out.append(None)
+        else:
+            out.append(Structure(rows[k], dcal[k], en[k]))
+    return out
+
+
+def mfe(sequence, temp=37.0):
+    return mfe_batch([sequence], temp)[0]
