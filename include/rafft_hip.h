@@ -348,6 +348,43 @@ int rafft_mfe_batch(int n_seq, const char *const *seqs, const int *lens, double 
 /* the longest sequence whose tables fit the LDS class */
 int rafft_mfe_lds_len(void);
 
+/* Partition function, base-pair probabilities and centroid structures of a batch (McCaskill).  Replaces:
+ * RNA.fold_compound(seq, md).pf() / bpp(), the calls beside the RNA.fold of benchmark_results/src/vrna_mfe.py:25.
+ * The ensemble is the one rafft_mfe_batch minimises over: canonical pairs, hairpins of at least 3, interior loops of at most 30
+ * unpaired positions, lonely pairs allowed, dangles=2.  The weight of a structure is exp(-dcal / (100 kT)), dcal the integer
+ * rafft_eval_structure returns for it, kT = (temp + 273.15) * 1.98717e-3 kcal/mol.  Z is the sum of these weights over every
+ * structure of the ensemble, P(i,j) the weight share of the structures that hold the pair (i,j), and the centroid row holds every
+ * pair with P > 0.5 (such pairs cannot cross or share a base).
+ * The sums are scaled fp64: the call first runs the MFE path on the same sequences and divides every table cell by
+ * scale^(positions it covers), scale = exp(-scale_factor * (mfe_dcal / 100) / (kT * length)), as ViennaRNA's pf_scale with sfact
+ * 1.07.  The results do not depend on scale_factor beyond rounding; a sequence's bits depend on the sequence, the energy tables,
+ * temp and scale_factor only - not on the batch, its order or the workspace.
+ * Every sequence has six L x L fp64 tables in device memory; the batch is processed in chunks of whole sequences, in input order,
+ * that fit workspace_bytes (0: 512 MiB; one sequence at least - 768 MiB at 4096 nt).
+ * Outputs (host): seq_out[s]; db_out[s] = lens[s] + 1 bytes for the NUL-terminated centroid row; prob_out may be NULL and so may
+ * prob_out[s], else lens[s] x lens[s] doubles, row-major, P(i pairs j) at [i][j] for i < j and 0 elsewhere.
+ * RAFFT_ERR_BAD_CHAR, RAFFT_ERR_EMPTY and RAFFT_ERR_TOO_LONG (above RAFFT_PF_MAX_LEN) are errors of that sequence only: its row is
+ * all dots, its energy and its probabilities are 0, the call returns RAFFT_OK and rafft_last_error() names the first such sequence.
+ * So is RAFFT_ERR_CAPACITY: the scaled tables of that sequence left the fp64 range (its exterior sum is zero or not finite, or a
+ * probability is not finite) - never a silent inf or nan.  RAFFT_ERR_PARAM, before anything is launched: a null argument, a
+ * negative count, a scale_factor that is negative or not finite.  RAFFT_ERR_TEMP as for the fold. */
+#define RAFFT_PF_MAX_LEN RAFFT_MFE_MAX_LEN
+typedef struct {
+    int32_t status;
+    int32_t length;
+    int32_t mfe_dcal;      /* the MFE the scale was taken from (what rafft_mfe_batch returns) */
+    int32_t n_pairs;       /* pairs of the centroid row */
+    double  energy;        /* ensemble free energy -kT ln Z, kcal/mol */
+    double  mfe_frequency; /* exp((energy - mfe_dcal/100) / kT): share of the MFE structure in the ensemble */
+} rafft_pf_seq;            /* 32 bytes */
+int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                   double scale_factor,        /* 0: 1.07; tests pass other values */
+                   long long workspace_bytes,  /* 0: 512 MiB; one sequence at least */
+                   rafft_pf_seq *seq_out,
+                   char *const *db_out,        /* db_out[s]: lens[s]+1 bytes, the centroid row, NUL terminated */
+                   double *const *prob_out     /* may be NULL, and so may prob_out[s]: lens[s] x lens[s] doubles, row-major,
+                                                  P(i pairs j) at [i][j] for i < j, 0 elsewhere */);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

@@ -54,6 +54,10 @@ _OPTIONS = [
                                                 "dangles=2, lonely pairs allowed, interior loops up to 30 - RNA.fold's defaults), one line per sequence as\n"
                                                 "benchmark_results/src/vrna_mfe.py prints it: seq len structure energy #pairs.  With --scores the table of\n"
                                                 "mfe_scores.csv.  Works with -s SEQ and with -sf FILE --batch")),
+    (("--pf",), dict(action="store_true", help="no RAFFT fold: the partition function of every sequence on the GPU (rafft_amd.pf_batch; the ensemble of --mfe),\n"
+                                               "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
+                                               "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
+                                               "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --kin or --traj")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
     (("--output", "-o"), dict(help="write the result there instead of stdout")),
@@ -211,6 +215,33 @@ def main_mfe(args, seqs, known, names, mfe_batch=None, scorer=None):
         sys.stdout.write(text)
 
 
+def format_pf_line(sequence, res):
+    return f"{sequence} {len(sequence)} {res.centroid} {res.energy:.2f} {res.centroid.count('(')} {res.mfe_frequency:.4g}"
+
+
+def main_pf(args, seqs, known, names, pf_batch=None, scorer=None):
+    """--pf: centroid, ensemble free energy and MFE share instead of the fold.  `scorer` as for main_mfe."""
+    if args.mfe or args.kin or args.traj:
+        raise SystemExit("--pf gives the ensemble of every sequence: no --mfe, no --kin, no --traj")
+    if pf_batch is None:
+        from .mccaskill import pf_batch as _pf
+        pf_batch = lambda sequences, temp: _pf(sequences, temp, probs=False)
+    results = pf_batch(seqs, args.temp)
+    if args.scores:
+        if scorer is None:
+            from .scoring import score_rows_gpu as scorer
+        beams = [[r] for r in results]
+        write_scores(args.scores, seqs, names, beams, scorer(beams, known), "energy")
+        if not args.output:
+            return
+    text = "".join(format_pf_line(s, r) + "\n" for s, r in zip(seqs, results))
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def _table_note():
     """one line on stderr when the fold used rule / model values of the built-in tables (never with ViennaRNA's own tables loaded)"""
     try:
@@ -225,12 +256,15 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None):
-    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch`: injection points for tests (the fold, the callable (results, known) -> score
-    table that stands in for scoring.score_batch_gpu - with --mfe for scoring.score_rows_gpu -, the callable (results, max_time,
-    n_steps) that stands in for rafft_kin.kinetics_batch, and the callable (sequences, temp) that stands in for zuker.mfe_batch)."""
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None):
+    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch`: injection points for tests (the fold, the callable (results,
+    known) -> score table that stands in for scoring.score_batch_gpu - with --mfe and --pf for scoring.score_rows_gpu -, the
+    callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable (sequences, temp) that stands
+    in for zuker.mfe_batch, and the callable (sequences, temp) that stands in for mccaskill.pf_batch)."""
     args = parse_arguments(argv)
     seqs, known, names = read_records(args)
+    if args.pf and (args.mfe or args.kin or args.traj):
+        raise SystemExit("--pf gives the ensemble of every sequence: no --mfe, no --kin, no --traj")
     if args.kin:
         if not args.batch or args.seq_file is None:
             raise SystemExit("--kin needs -sf FILE --batch")
@@ -240,6 +274,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None)
             raise SystemExit("--scores needs -sf CSV --batch with a known structure per sequence "
                              f"(column {args.known_column!r}, or the headerless seq,struct,name file)")
         names = names if names is not None else [""] * len(seqs)
+    if args.pf:
+        return main_pf(args, seqs, known, names, pf_batch, scorer)
     if args.mfe:
         return main_mfe(args, seqs, known, names, mfe_batch, scorer)
     if fold_batch is None:

@@ -39,6 +39,7 @@
 #include "rafft_landscape.hip"
 #include "rafft_score.hip"
 #include "rafft_mfe.hip"
+#include "rafft_pf.hip"
 
 // host side, one responsibility per file (each in its own anonymous namespace)
 #include "rafft_host_ctx.h"     // errors, workspaces and their buffers, the global context, memory pools, initialisation
@@ -341,5 +342,16 @@ int rafft_mfe_batch(int n_seq, const char *const *seqs, const int *lens, double 
 }
 
 int rafft_mfe_lds_len(void) { return RAFFT_MFE_LDS_LEN; }
+
+int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes,
+                   rafft_pf_seq *seq_out, char *const *db_out, double *const *prob_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || workspace_bytes < 0 || !std::isfinite(scale_factor) || scale_factor < 0.0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_seq > 0 && (!seqs || !lens || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int s = 0; s < n_seq; s++)
+        if (!db_out[s] || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    return pf_batch(n_seq, seqs, lens, temp, scale_factor, workspace_bytes, seq_out, db_out, prob_out);
+}
 
 } // extern "C"

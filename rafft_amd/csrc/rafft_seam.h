@@ -752,4 +752,123 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
     return 0;
 }
 
+// ---- partition function and pair probabilities
+
+constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
+
+// rafft_pf_batch (arguments validated by the entry point).  The MFE of every sequence first (mfe_batch: its errors are this call's,
+// its energy gives the scale), then chunks of whole sequences in input order whose six L x L fp64 tables fit the workspace budget
+// (one sequence at least): per chunk one launch per anti-diagonal upwards, the exterior sums, one launch per anti-diagonal downwards,
+// the probabilities.  One synchronise at the end.
+int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, rafft_pf_seq *seq_out,
+             char *const *db_out, double *const *prob_out)
+{
+    std::vector<rafft_mfe_seq> mfe(std::max(n_seq, 1));
+    if (int rc = mfe_batch(n_seq, seqs, lens, temp, RAFFT_MFE_LDS_LEN, workspace_bytes, mfe.data(), db_out)) return rc;
+    if (n_seq == 0) return 0;
+    const std::string first_err = g_err;
+    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
+    std::vector<PfSeq> qs(n_seq);
+    std::vector<int> order;
+    unsigned long long n_codes = 0, n_aux = 0, n_db = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const int len = mfe[s].length;
+        seq_out[s] = rafft_pf_seq{mfe[s].status, len, mfe[s].dcal, 0, 0.0, 0.0};
+        memset(db_out[s], '.', (size_t)len);
+        db_out[s][len] = 0;
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)len * len * sizeof(double));
+        const int L = mfe[s].status ? 0 : len;
+        const double ln_scale = L ? -sf * ((double)mfe[s].dcal / 100.0) / (kt * (double)L) : 0.0;
+        const double scale = std::exp(ln_scale);
+        qs[s] = PfSeq{n_codes, 0, n_aux, n_db, L, mfe[s].dcal, scale, std::log(scale)};
+        if (!L) continue;
+        n_codes += (unsigned long long)L; n_aux += 4 * ((unsigned long long)L + 1); n_db += (unsigned long long)L + 1;
+        order.push_back(s);
+    }
+    if (order.empty()) return 0;
+    std::vector<uint8_t> codes(n_codes + 16, 0);
+    for (int s = 0; s < n_seq; s++)
+        for (int x = 0; x < qs[s].L; x++) codes[qs[s].code_off + x] = (uint8_t)(kBaseCode[(unsigned char)seqs[s][x]] & 7);
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE;
+    struct Chunk { size_t a, b; int Lmax; };
+    std::vector<Chunk> chunks;
+    size_t ws_max = 0;
+    for (size_t a = 0; a < order.size();) {
+        size_t w = 0, b = a;
+        int Lmax = 0;
+        while (b < order.size() && b - a < 65535) {
+            PfSeq &q = qs[order[b]];
+            const size_t dw = 6 * (size_t)q.L * q.L * sizeof(double);
+            if (b > a && w + dw > budget) break;
+            q.tab_off = w / sizeof(double);
+            w += dw; Lmax = std::max(Lmax, q.L); b++;
+        }
+        chunks.push_back(Chunk{a, b, Lmax});
+        ws_max = std::max(ws_max, w);
+        a = b;
+    }
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    if (int rc = ensure_tables(temp)) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    PfSeq *d_qs; uint8_t *d_codes; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(PfSeq))) return rc;
+    if (int rc = mem.alloc(d_codes, codes.size())) return rc;
+    if (int rc = mem.alloc(d_aux, n_aux * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(PfRec))) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(PfSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(PfRec), st));
+    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, d_qs, n_seq, d_aux, beta);
+    HIPCHK(hipGetLastError());
+    for (const Chunk &c : chunks) {
+        const int *ord = d_order + c.a;
+        const unsigned ny = (unsigned)(c.b - c.a);
+        const auto nx = [&](int d) { return (unsigned)std::min((c.Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); };
+        for (int d = 0; d < c.Lmax; d++)
+            hipLaunchKernelGGL(pf_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pf_exterior_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, kt, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+        for (int d = c.Lmax - 1; d >= 4; d--)
+            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pf_prob_kernel, dim3(nx(0), ny), dim3(PF_NT), 0, st, d_qs, ord, d_ws, d_aux, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+        if (prob_out)
+            for (size_t k = c.a; k < c.b; k++) {
+                const PfSeq &q = qs[order[k]];
+                if (prob_out[order[k]])
+                    HIPCHK(hipMemcpyAsync(prob_out[order[k]], d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+    }
+    std::vector<PfRec> rec(n_seq);
+    std::vector<char> db(n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::string err = first_err;
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].status || rec[s].bad) {
+            // the scaled tables left the fp64 range: no number of this sequence is reported
+            seq_out[s].status = RAFFT_ERR_CAPACITY;
+            if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)qs[s].L * qs[s].L * sizeof(double));
+            if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
+            continue;
+        }
+        seq_out[s].n_pairs = rec[s].n_pairs;
+        seq_out[s].energy = rec[s].energy;
+        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
+        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    g_err = err;
+    return 0;
+}
+
 } // namespace
