@@ -169,6 +169,21 @@ def lib():
     return L
 
 
+def seq_arrays(sequences, rows=False):
+    """The ctypes arguments of a list of sequences: (enc, arr, lens) - the encoded strings (a character outside ASCII becomes '?',
+    which the library reports as that sequence's bad character), the array of their pointers and the array of their lengths.
+    rows=True adds (bufs, out): one output row of len + 1 bytes per sequence and the array of the rows' addresses."""
+    n = len(sequences)
+    enc = [s.encode("ascii", "replace") for s in sequences]
+    arr = (C.c_char_p * n)(*enc)
+    lens = (C.c_int * n)(*map(len, enc))
+    if not rows:
+        return enc, arr, lens
+    bufs = [C.create_string_buffer(len(e) + 1) for e in enc]
+    out = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+    return enc, arr, lens, bufs, out
+
+
 def check(rc):
     if rc:
         raise RafftError(rc, lib().rafft_last_error().decode())

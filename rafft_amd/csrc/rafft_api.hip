@@ -48,6 +48,16 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch
+
+// the arguments rafft_mfe_batch and rafft_pf_batch share
+static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
+{
+    if (n_seq > 0 && (!seqs || !lens || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int s = 0; s < n_seq; s++)
+        if (!db_out[s] || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    return 0;
+}
 
 extern "C" {
 
@@ -335,9 +345,7 @@ int rafft_mfe_batch(int n_seq, const char *const *seqs, const int *lens, double 
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (n_seq < 0 || max_lds_len < 0 || max_lds_len > RAFFT_MFE_LDS_LEN || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
-    if (n_seq > 0 && (!seqs || !lens || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
-    for (int s = 0; s < n_seq; s++)
-        if (!db_out[s] || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
     return mfe_batch(n_seq, seqs, lens, temp, max_lds_len ? max_lds_len : RAFFT_MFE_LDS_LEN, workspace_bytes, seq_out, db_out);
 }
 
@@ -348,9 +356,7 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (n_seq < 0 || workspace_bytes < 0 || !std::isfinite(scale_factor) || scale_factor < 0.0) return fail(RAFFT_ERR_PARAM, "bad argument");
-    if (n_seq > 0 && (!seqs || !lens || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
-    for (int s = 0; s < n_seq; s++)
-        if (!db_out[s] || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
     return pf_batch(n_seq, seqs, lens, temp, scale_factor, workspace_bytes, seq_out, db_out, prob_out);
 }
 

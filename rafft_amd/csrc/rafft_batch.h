@@ -1,0 +1,392 @@
+// rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
+// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds) and pf_batch (partition
+// function and pair probabilities), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence
+// pack, the graph pack, the solve order of a chunk - is in rafft_hostpure.h, where the CPU suite checks it.
+// Part of the single translation unit of rafft_api.hip (included there, after rafft_seam.h, whose SeamGuard and DevScratch they use).
+#pragma once
+
+namespace {
+
+// ---- kinetics of a batch of graphs
+
+// rafft_kin_batch (arguments validated by the entry point).  Two passes over the device: structure identity for every graph, then -
+// the numbers of unique structures being known - rates and integration for chunks of graphs whose matrices fit the workspace budget.
+constexpr size_t KIN_BATCH_WORKSPACE = (size_t)512 << 20;
+
+int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows, const int *row_stride,
+              const double *const *energy, double kt, int n_times, const int *m, const double *h, long long workspace_bytes,
+              rafft_kin_graph *rec, int *uid_out, int *first_row_out, double *pop_out, double *const *rate_out)
+{
+    KinPack pk;
+    if (!kin_pack(n_graphs, lens, n_steps, step_size, rows, row_stride, energy, pk)) return fail(RAFFT_ERR_PARAM, "too many rows");
+    const long long n = pk.n;
+    const unsigned long long bytes = pk.bytes;
+    std::vector<KinGraph> gs(n_graphs);
+    int Lmax = 0;
+    for (int g = 0; g < n_graphs; g++) {
+        gs[g] = KinGraph{pk.off[g], 0, lens[g], pk.n_rows[g], pk.row0[g], 0};
+        rec[g] = rafft_kin_graph{0, pk.n_rows[g], pk.row0[g], 0, 0, 0};
+        if (pk.n_rows[g]) Lmax = std::max(Lmax, lens[g]);
+    }
+    if (n == 0) return 0;
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    KinGraph *d_gs; char *d_rows; int16_t *d_pt, *d_stack; unsigned long long *d_hash; double *d_en, *d_enu, *d_h;
+    int *d_rg, *d_p0, *d_np, *d_bad, *d_first, *d_rank, *d_frow, *d_nu, *d_uid, *d_ne, *d_m;
+    const size_t n4 = (size_t)n * 4, g4 = (size_t)n_graphs * 4;
+    if (int rc = mem.alloc(d_gs, gs.size() * sizeof(KinGraph))) return rc;
+    if (int rc = mem.alloc(d_rows, bytes + 1)) return rc;
+    if (int rc = mem.alloc(d_pt, (bytes + 1) * 2)) return rc;
+    if (int rc = mem.alloc(d_stack, (bytes + 1) * 2)) return rc;
+    if (int rc = mem.alloc(d_hash, n4 * 2)) return rc;
+    if (int rc = mem.alloc(d_en, n4 * 2)) return rc;
+    if (int rc = mem.alloc(d_enu, n4 * 2)) return rc;
+    if (int rc = mem.alloc(d_rg, n4)) return rc;
+    if (int rc = mem.alloc(d_p0, n4)) return rc;
+    if (int rc = mem.alloc(d_np, n4)) return rc;
+    if (int rc = mem.alloc(d_first, n4)) return rc;
+    if (int rc = mem.alloc(d_rank, n4)) return rc;
+    if (int rc = mem.alloc(d_frow, n4)) return rc;
+    if (int rc = mem.alloc(d_uid, n4)) return rc;
+    if (int rc = mem.alloc(d_bad, g4)) return rc;
+    if (int rc = mem.alloc(d_nu, g4)) return rc;
+    if (int rc = mem.alloc(d_ne, g4)) return rc;
+    if (int rc = mem.alloc(d_m, (size_t)n_times * 4)) return rc;
+    if (int rc = mem.alloc(d_h, (size_t)n_times * 8)) return rc;
+    HIPCHK(hipMemcpyAsync(d_gs, gs.data(), gs.size() * sizeof(KinGraph), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rows, pk.rows.data(), bytes + 1, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_en, pk.energy.data(), n4 * 2, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rg, pk.row_graph.data(), n4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_p0, pk.row_prev0.data(), n4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_np, pk.row_nprev.data(), n4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_m, m, (size_t)n_times * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_h, h, (size_t)n_times * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_bad, 0, g4, st));
+    HIPCHK(hipMemsetAsync(d_ne, 0, g4, st));
+    HIPCHK(hipMemsetAsync(d_frow, 0xff, n4, st));            // -1: no such unique structure
+    HIPCHK(hipMemsetAsync(d_rank, 0, n4, st));
+    const unsigned nb64 = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(kin_batch_pair_table_kernel, dim3(nb64), dim3(64), 0, st, (int)n, d_gs, d_rg, d_rows, d_pt, d_stack, d_hash, d_bad);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kin_batch_identity_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (int)n, d_gs, d_rg, d_rows, d_hash, d_first);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kin_batch_rank_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, d_gs, d_first, d_en, d_rank, d_frow, d_enu, d_nu);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kin_batch_uid_kernel, dim3(nb64), dim3(64), 0, st, (int)n, d_gs, d_rg, d_first, d_rank, d_uid);
+    HIPCHK(hipGetLastError());
+    std::vector<int> bad(n_graphs), nu(n_graphs);
+    HIPCHK(hipMemcpyAsync(bad.data(), d_bad, g4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(nu.data(), d_nu, g4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(uid_out, d_uid, n4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(first_row_out, d_frow, n4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::string first_err;
+    for (int g = 0; g < n_graphs; g++) {
+        KinGraph &G = gs[g];
+        if (bad[g]) {
+            rec[g].status = RAFFT_ERR_STRUCT;
+            if (first_err.empty()) first_err = "graph " + std::to_string(g) + ": malformed dot-bracket row";
+        } else if (nu[g] > RAFFT_KIN_BATCH_MAX_STATES) {
+            rec[g].status = RAFFT_ERR_CAPACITY;
+            rec[g].n_unique = nu[g];
+            if (first_err.empty())
+                first_err = "graph " + std::to_string(g) + ": " + std::to_string(nu[g]) + " unique structures, the batch path takes up to " +
+                            std::to_string(RAFFT_KIN_BATCH_MAX_STATES) + " - use the single-graph path (rafft_kin_rate_matrix and a dense or sparse solver)";
+        } else {
+            rec[g].n_unique = G.S = nu[g];
+            continue;
+        }
+        for (int r = 0; r < G.n_rows; r++) uid_out[G.row0 + r] = first_row_out[G.row0 + r] = -1;
+    }
+    // chunks of consecutive graphs: three S x S blocks per graph and the populations of the chunk within the budget (one graph at least)
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : KIN_BATCH_WORKSPACE;
+    std::vector<int> S(n_graphs);
+    std::vector<size_t> mat_bytes(n_graphs), pop_bytes(n_graphs);
+    for (int g = 0; g < n_graphs; g++) {
+        S[g] = gs[g].S;
+        mat_bytes[g] = 3 * (size_t)S[g] * S[g] * 8;
+        pop_bytes[g] = (size_t)n_times * gs[g].n_rows * 8;
+    }
+    const ChunkPlan plan = plan_chunks((size_t)n_graphs, mat_bytes.data(), pop_bytes.data(), budget, 0);
+    for (int g = 0; g < n_graphs; g++) gs[g].mat = plan.off[g] / 8;
+    double *d_ws, *d_pop;
+    if (int rc = mem.alloc(d_ws, plan.max_cost + 8)) return rc;
+    if (int rc = mem.alloc(d_pop, plan.max_cost2 + 8)) return rc;
+    HIPCHK(hipMemcpyAsync(d_gs, gs.data(), gs.size() * sizeof(KinGraph), hipMemcpyHostToDevice, st));
+    constexpr size_t lds_small = (size_t)(4 * KIN_BATCH_LDS_STATES + 1 + KIN_BATCH_LDS_STATES * KIN_BATCH_LDS_STATES) * 8;
+    constexpr size_t lds_big = (size_t)(4 * RAFFT_KIN_BATCH_MAX_STATES + 1) * 8;
+    HIPCHK(hipFuncSetAttribute((const void *)kin_batch_integrate_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
+    // per chunk the graphs that are solved: those whose inverse fits LDS first, then the others
+    std::vector<int> order(n_graphs);
+    std::vector<SolveCounts> solved(plan.chunks.size());
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++)
+        solved[ci] = kin_solve_order(S.data(), plan.chunks[ci].a, plan.chunks[ci].b, KIN_BATCH_LDS_STATES, order.data());
+    int *d_order;
+    if (int rc = mem.alloc(d_order, g4)) return rc;
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), g4, hipMemcpyHostToDevice, st));
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
+        const ChunkPlan::Range &c = plan.chunks[ci];
+        const int ra = gs[c.a].row0, rb = c.b < (size_t)n_graphs ? gs[c.b].row0 : (int)n;
+        const int small = solved[ci].n_small, big = solved[ci].n_big;
+        size_t w = 0;
+        for (size_t g = c.a; g < c.b; g++) w += mat_bytes[g];
+        if (rb == ra) continue;
+        if (!small && !big) { memset(pop_out + (size_t)n_times * ra, 0, (size_t)n_times * (rb - ra) * 8); continue; }
+        HIPCHK(hipMemsetAsync(d_ws, 0, w, st));
+        HIPCHK(hipMemsetAsync(d_pop, 0, (size_t)n_times * (rb - ra) * 8, st));
+        hipLaunchKernelGGL(kin_batch_rates_kernel, dim3((unsigned)(rb - ra)), dim3(KIN_NT), (size_t)Lmax * 2, st, ra, d_gs, d_rg, d_p0, d_np, d_pt, d_uid, d_enu, kt, d_ws);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(kin_batch_diag_kernel, dim3((unsigned)(rb - ra)), dim3(256), 0, st, ra, d_gs, d_rg, d_ws, d_ne);
+        HIPCHK(hipGetLastError());
+        if (small) {
+            hipLaunchKernelGGL(kin_batch_integrate_kernel<true>, dim3((unsigned)small), dim3(KINB_NT), lds_small, st, d_order + c.a, ra, d_gs, d_ws, n_times, d_m, d_h, d_pop);
+            HIPCHK(hipGetLastError());
+        }
+        if (big) {
+            hipLaunchKernelGGL(kin_batch_integrate_kernel<false>, dim3((unsigned)big), dim3(KINB_NT), lds_big, st, d_order + c.a + small, ra, d_gs, d_ws, n_times, d_m, d_h, d_pop);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(pop_out + (size_t)n_times * ra, d_pop, (size_t)n_times * (rb - ra) * 8, hipMemcpyDeviceToHost, st));
+        if (rate_out)
+            for (size_t g = c.a; g < c.b; g++)
+                if (rate_out[g] && gs[g].S) HIPCHK(hipMemcpyAsync(rate_out[g], d_ws + gs[g].mat, (size_t)gs[g].S * gs[g].S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    std::vector<int> ne(n_graphs);
+    HIPCHK(hipMemcpy(ne.data(), d_ne, g4, hipMemcpyDeviceToHost));
+    for (int g = 0; g < n_graphs; g++) rec[g].n_edges = ne[g];
+    g_err = first_err;
+    return 0;
+}
+
+// ---- minimum-free-energy folds
+
+constexpr size_t MFE_WORKSPACE = (size_t)512 << 20;
+
+// as the fold's entry (validate_params): before any sequence is looked at, so a batch of nothing but erroneous sequences fails too
+int check_temp(double temp)
+{
+    if (!(temp > -273.15 && temp < 1000.0)) return fail(RAFFT_ERR_TEMP, "temp out of range");
+    if (temp != 37.0 && !param_set().has_dH)
+        return fail(RAFFT_ERR_TEMP, "temp != 37 needs the enthalpy tables of a ViennaRNA parameter file (rafft_load_params); the built-in tables are 37 C only");
+    return 0;
+}
+
+// a row of dots for a sequence of `len` (what a sequence with an error keeps)
+void dot_row(char *db, int len)
+{
+    memset(db, '.', (size_t)len);
+    db[len] = 0;
+}
+
+// The MFE folds of a pack, under the caller's guard: the device tables are scaled for the call's temp, d_codes is the device copy
+// of pk.codes, seq_out[s].status is set.  Sequences up to `lds_len` go through mfe_lds_kernel in one launch, the others through
+// the HBM class in chunks whose tables fit the workspace budget (one sequence at least): per chunk one launch per anti-diagonal,
+// then the traceback.  One synchronise at the end; its device buffers are freed on return.  db_out may be null (no rows wanted).
+int mfe_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, int lds_len, long long workspace_bytes, rafft_mfe_seq *seq_out, char *const *db_out)
+{
+    const int n_seq = (int)pk.L.size();
+    std::vector<MfeSeq> qs(n_seq);
+    std::vector<int> lds_order, hbm_order;
+    unsigned long long n_stack = 0, n_db = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.L[s];
+        qs[s] = MfeSeq{pk.code_off[s], 0, n_stack, n_db, len, 0};
+        if (!len) continue;
+        n_stack += (unsigned long long)len + 8; n_db += (unsigned long long)len + 1;
+        (len <= lds_len ? lds_order : hbm_order).push_back(s);
+    }
+    // the longest first: the workgroups of a launch that run last are the short ones
+    std::stable_sort(lds_order.begin(), lds_order.end(), [&](int a, int b) { return qs[a].L > qs[b].L; });
+    // chunks of the HBM class, in input order; a launch takes up to 65535 sequences (gridDim.y)
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE;
+    std::vector<size_t> tab_bytes(hbm_order.size());
+    for (size_t k = 0; k < hbm_order.size(); k++) tab_bytes[k] = 3 * (size_t)qs[hbm_order[k]].L * qs[hbm_order[k]].L * 4;
+    const ChunkPlan plan = plan_chunks(hbm_order.size(), tab_bytes.data(), nullptr, budget, 65535);
+    for (size_t k = 0; k < hbm_order.size(); k++) qs[hbm_order[k]].tab_off = plan.off[k] / 4;
+    const size_t ws_max = plan.max_cost;
+    DevScratch mem;
+    MfeSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr;
+    std::vector<int> order(lds_order);
+    order.insert(order.end(), hbm_order.begin(), hbm_order.end());
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSeq))) return rc;
+    if (int rc = mem.alloc(d_stack, n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (ws_max) if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
+    if (!lds_order.empty()) {
+        HIPCHK(hipFuncSetAttribute((const void *)mfe_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MFE_LDS_BYTES));
+        hipLaunchKernelGGL(mfe_lds_kernel, dim3((unsigned)lds_order.size()), dim3(MFE_LDS_NT), (size_t)mfe_lds_bytes(qs[lds_order[0]].L), st, g.T, d_qs, d_order,
+                           d_codes, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    for (const ChunkPlan::Range &c : plan.chunks) {
+        const int *ord = d_order + lds_order.size() + c.a;
+        const unsigned ny = (unsigned)(c.b - c.a);
+        int Lmax = 0;
+        for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, qs[hbm_order[k]].L);
+        for (int d = 0; d < Lmax; d++) {
+            const unsigned nx = (unsigned)std::min((Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
+            hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d);
+        }
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mfe_traceback_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<int4> rec(n_seq);
+    std::vector<char> db(n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
+        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
+        if (db_out) memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    return 0;
+}
+
+// rafft_mfe_batch (arguments validated by the entry point)
+int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int lds_len, long long workspace_bytes, rafft_mfe_seq *seq_out,
+              char *const *db_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    for (int s = 0; s < n_seq; s++) {
+        seq_out[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+        dot_row(db_out[s], pk.len[s]);
+    }
+    g_err = pk.first_err;
+    if (pk.fold.empty()) return 0;
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    if (int rc = ensure_tables(temp)) return rc;
+    DevScratch mem;
+    uint8_t *d_codes;
+    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
+    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, sg.stream));
+    if (int rc = mfe_held(sg.stream, pk, d_codes, lds_len, workspace_bytes, seq_out, db_out)) return rc;
+    g_err = pk.first_err;
+    return 0;
+}
+
+// ---- partition function and pair probabilities
+
+constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
+
+// rafft_pf_batch (arguments validated by the entry point).  One pack, one guard, one upload of the bases.  The MFE of every sequence
+// first (mfe_held: its energy gives the scale; its device buffers are freed before the tables here are allocated), then chunks of
+// whole sequences in input order whose six L x L fp64 tables fit the workspace budget (one sequence at least): per chunk one launch
+// per anti-diagonal upwards, the exterior sums, one launch per anti-diagonal downwards, the probabilities.  One synchronise at the end.
+int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, rafft_pf_seq *seq_out,
+             char *const *db_out, double *const *prob_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);     // (RAFFT_PF_MAX_LEN is RAFFT_MFE_MAX_LEN)
+    std::vector<rafft_mfe_seq> mfe(n_seq);
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.len[s];
+        mfe[s] = rafft_mfe_seq{pk.status[s], len, 0, 0};
+        seq_out[s] = rafft_pf_seq{pk.status[s], len, 0, 0, 0.0, 0.0};
+        dot_row(db_out[s], len);
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)len * len * sizeof(double));
+    }
+    g_err = pk.first_err;
+    const std::vector<int> &order = pk.fold;
+    if (order.empty()) return 0;
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    if (int rc = ensure_tables(temp)) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    uint8_t *d_codes;
+    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
+    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
+    if (int rc = mfe_held(st, pk, d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, mfe.data(), nullptr)) return rc;
+    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
+    std::vector<PfSeq> qs(n_seq);
+    unsigned long long n_aux = 0, n_db = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const int L = pk.L[s];
+        seq_out[s].mfe_dcal = mfe[s].dcal;
+        const double ln_scale = L ? -sf * ((double)mfe[s].dcal / 100.0) / (kt * (double)L) : 0.0;
+        const double scale = std::exp(ln_scale);
+        qs[s] = PfSeq{pk.code_off[s], 0, n_aux, n_db, L, mfe[s].dcal, scale, std::log(scale)};
+        if (!L) continue;
+        n_aux += 4 * ((unsigned long long)L + 1); n_db += (unsigned long long)L + 1;
+    }
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE;
+    std::vector<size_t> tab_bytes(order.size());
+    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = 6 * (size_t)qs[order[k]].L * qs[order[k]].L * sizeof(double);
+    const ChunkPlan plan = plan_chunks(order.size(), tab_bytes.data(), nullptr, budget, 65535);      // (gridDim.y, as mfe_held)
+    for (size_t k = 0; k < order.size(); k++) qs[order[k]].tab_off = plan.off[k] / sizeof(double);
+    const size_t ws_max = plan.max_cost;
+    PfSeq *d_qs; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(PfSeq))) return rc;
+    if (int rc = mem.alloc(d_aux, n_aux * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(PfRec))) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(PfSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(PfRec), st));
+    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, d_qs, n_seq, d_aux, beta);
+    HIPCHK(hipGetLastError());
+    for (const ChunkPlan::Range &c : plan.chunks) {
+        const int *ord = d_order + c.a;
+        const unsigned ny = (unsigned)(c.b - c.a);
+        int Lmax = 0;
+        for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, qs[order[k]].L);
+        const auto nx = [&](int d) { return (unsigned)std::min((Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); };
+        for (int d = 0; d < Lmax; d++)
+            hipLaunchKernelGGL(pf_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pf_exterior_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, kt, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+        for (int d = Lmax - 1; d >= 4; d--)
+            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pf_prob_kernel, dim3(nx(0), ny), dim3(PF_NT), 0, st, d_qs, ord, d_ws, d_aux, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+        if (prob_out)
+            for (size_t k = c.a; k < c.b; k++) {
+                const PfSeq &q = qs[order[k]];
+                if (prob_out[order[k]])
+                    HIPCHK(hipMemcpyAsync(prob_out[order[k]], d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+    }
+    std::vector<PfRec> rec(n_seq);
+    std::vector<char> db(n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::string err = pk.first_err;
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].status || rec[s].bad) {
+            // the scaled tables left the fp64 range: no number of this sequence is reported
+            seq_out[s].status = RAFFT_ERR_CAPACITY;
+            if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)qs[s].L * qs[s].L * sizeof(double));
+            if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
+            continue;
+        }
+        seq_out[s].n_pairs = rec[s].n_pairs;
+        seq_out[s].energy = rec[s].energy;
+        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
+        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    g_err = err;
+    return 0;
+}
+
+} // namespace

@@ -1,7 +1,10 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
-// that encloses a region, the lane cut of a batch and the row layout of the scoring calls.  Plain C++ (g++ compiles it alone:
+// that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
+// (chunks within a budget, the sequence pack, the graph pack, the solve order).  Plain C++ (g++ compiles it alone:
 // tests/hostcheck/hostpure_check.cpp).  Part of the single translation unit of rafft_api.hip (included there, before the kernels).
 #pragma once
+
+#include "../../include/rafft_hip.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -170,6 +173,132 @@ static bool score_chunk_layout(int n_seq, const int *lens, const int *n_rows, co
     }
     for (int s = 0; s < n_seq; s++) rows_off[s] = chunk_of[s] >= 0 ? dev_off[chunk_of[s]] + (size_t)(rows[s] - lo[chunk_of[s]]) : 0;
     return true;
+}
+
+// ---- planning of the batch drivers (rafft_batch.h)
+
+// Chunks of consecutive items within a budget.  An item joins the open chunk unless the chunk is non-empty and the item would take
+// the chunk's primary or secondary total over `budget`, or the chunk already holds `cap` items (0: no cap): a chunk holds one item
+// at least, however large.  cost2 may be null.  off[i]: the primary bytes of the items before i in i's chunk.
+struct ChunkPlan {
+    struct Range { size_t a, b; };          // items [a, b)
+    std::vector<Range> chunks;
+    std::vector<size_t> off;
+    size_t max_cost = 0, max_cost2 = 0;     // the largest totals of any chunk
+};
+static ChunkPlan plan_chunks(size_t n, const size_t *cost, const size_t *cost2, size_t budget, size_t cap)
+{
+    ChunkPlan p;
+    p.off.resize(n);
+    for (size_t a = 0; a < n;) {
+        size_t w = 0, w2 = 0, b = a;
+        while (b < n && !(cap && b - a >= cap)) {
+            const size_t d2 = cost2 ? cost2[b] : 0;
+            if (b > a && (w + cost[b] > budget || w2 + d2 > budget)) break;
+            p.off[b] = w;
+            w += cost[b]; w2 += d2; b++;
+        }
+        p.chunks.push_back(ChunkPlan::Range{a, b});
+        p.max_cost = std::max(p.max_cost, w); p.max_cost2 = std::max(p.max_cost2, w2);
+        a = b;
+    }
+    return p;
+}
+
+// The sequences of rafft_mfe_batch / rafft_pf_batch.  Per sequence: status (empty before too long before bad character), the
+// length as reported (max(len, 0)), the folded length (0 for an error) and where its bases lie in `codes` (kBaseCode & 7, back to
+// back, 16 zero bytes behind the last); `fold`: the sequences without an error, in input order; first_err: the first error's text.
+struct SeqPack {
+    std::vector<int> status, len, L, fold;
+    std::vector<unsigned long long> code_off;
+    std::vector<uint8_t> codes;
+    std::string first_err;
+};
+static SeqPack pack_sequences(int n_seq, const char *const *seqs, const int *lens, int max_len)
+{
+    SeqPack p;
+    p.status.resize(n_seq); p.len.resize(n_seq); p.L.resize(n_seq); p.code_off.resize(n_seq);
+    unsigned long long n_codes = 0;
+    for (int s = 0; s < n_seq; s++) {
+        int st = 0;
+        if (lens[s] <= 0) st = RAFFT_ERR_EMPTY;
+        else if (lens[s] > max_len) st = RAFFT_ERR_TOO_LONG;
+        else for (int x = 0; x < lens[s] && !st; x++) if (kBaseCode[(unsigned char)seqs[s][x]] & 8) st = RAFFT_ERR_BAD_CHAR;
+        p.status[s] = st;
+        p.len[s] = lens[s] > 0 ? lens[s] : 0;
+        p.L[s] = st ? 0 : p.len[s];
+        p.code_off[s] = n_codes;
+        if (st) {
+            if (p.first_err.empty())
+                p.first_err = "sequence " + std::to_string(s) + (st == RAFFT_ERR_EMPTY ? ": empty" : st == RAFFT_ERR_TOO_LONG ? ": longer than RAFFT_MFE_MAX_LEN" : ": character outside ACGUN");
+            continue;
+        }
+        n_codes += (unsigned long long)p.L[s];
+        p.fold.push_back(s);
+    }
+    p.codes.assign(n_codes + 16, 0);
+    for (int s : p.fold)
+        for (int x = 0; x < p.L[s]; x++) p.codes[p.code_off[s] + x] = (uint8_t)(kBaseCode[(unsigned char)seqs[s][x]] & 7);
+    return p;
+}
+
+// the step a step of a folding graph is compared with: the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)
+static int kin_prev_step(int i, int n_steps) { return i == 0 ? n_steps - 1 : i - 1; }
+
+// The graphs of rafft_kin_batch, rows packed back to back without their strides.  Per graph: its rows, the number of its first
+// row in the batch and the first byte of its rows; per row: its graph, and first row and size of the step it is compared with;
+// `rows` (one spare byte behind the last) and `energy` in row order.  false: more than 2^31 - 1 rows (nothing is packed then).
+struct KinPack {
+    std::vector<int> n_rows, row0, row_graph, row_prev0, row_nprev;
+    std::vector<unsigned long long> off;
+    std::vector<char> rows;
+    std::vector<double> energy;
+    long long n = 0;                    // rows of the batch
+    unsigned long long bytes = 0;       // of all rows
+};
+static bool kin_pack(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows, const int *row_stride,
+                     const double *const *energy, KinPack &p)
+{
+    p = KinPack{};
+    p.n_rows.resize(n_graphs); p.row0.resize(n_graphs); p.off.resize(n_graphs);
+    for (int g = 0; g < n_graphs; g++) {
+        long long nr = 0;
+        for (int i = 0; i < n_steps[g]; i++) nr += step_size[g][i];
+        if (p.n + nr > 0x7fffffff) return false;
+        p.n_rows[g] = (int)nr; p.row0[g] = (int)p.n; p.off[g] = p.bytes;
+        p.n += nr;
+        p.bytes += (unsigned long long)nr * (unsigned long long)lens[g];
+    }
+    p.rows.resize(p.bytes + 1);
+    p.row_graph.resize(p.n); p.row_prev0.resize(p.n); p.row_nprev.resize(p.n);
+    p.energy.resize(p.n);
+    for (int g = 0; g < n_graphs; g++) {
+        if (!p.n_rows[g]) continue;
+        const size_t L = (size_t)lens[g];
+        if (row_stride[g] == lens[g]) memcpy(p.rows.data() + p.off[g], rows[g], (size_t)p.n_rows[g] * L);
+        else for (int r = 0; r < p.n_rows[g]; r++) memcpy(p.rows.data() + p.off[g] + (size_t)r * L, rows[g] + (size_t)r * row_stride[g], L);
+        memcpy(p.energy.data() + p.row0[g], energy[g], (size_t)p.n_rows[g] * sizeof(double));
+        std::vector<int> s0(n_steps[g]);
+        int at = p.row0[g];
+        for (int i = 0; i < n_steps[g]; i++) { s0[i] = at; at += step_size[g][i]; }
+        for (int i = 0; i < n_steps[g]; i++) {
+            const int pi = kin_prev_step(i, n_steps[g]);
+            for (int r = s0[i]; r < s0[i] + step_size[g][i]; r++) { p.row_graph[r] = g; p.row_prev0[r] = s0[pi]; p.row_nprev[r] = step_size[g][pi]; }
+        }
+    }
+    return true;
+}
+
+// The graphs [a, b) of a chunk in the order they are solved: those with 0 < S <= lds_states (their inverse fits LDS) first, in input
+// order, then those above; S == 0 is not solved.  Written to order[a ...]; returns the two counts.
+struct SolveCounts { int n_small, n_big; };
+static SolveCounts kin_solve_order(const int *S, size_t a, size_t b, int lds_states, int *order)
+{
+    size_t at = a;
+    for (size_t g = a; g < b; g++) if (S[g] && S[g] <= lds_states) order[at++] = (int)g;
+    const int n_small = (int)(at - a);
+    for (size_t g = a; g < b; g++) if (S[g] > lds_states) order[at++] = (int)g;
+    return SolveCounts{n_small, (int)(at - a) - n_small};
 }
 
 } // namespace

@@ -1,7 +1,7 @@
 // rafft_seam.h - the seam calls: entry points that drain the folds in flight and borrow workspace 0 on the caller's thread.
 // What they share is written once here - how such a call enters (SeamGuard) and who owns its device buffers (DevScratch) -
-// followed by the calls themselves: structure evaluation, rafft_expand_node, and the drivers of the feature kernels (the kinetics
-// rate matrix, the folding landscape, accuracy scoring, minimum-free-energy folds).
+// followed by the calls themselves: structure evaluation, rafft_expand_node, and the drivers of the single-item feature kernels
+// (the kinetics rate matrix, the folding landscape, accuracy scoring).  The batch drivers are in rafft_batch.h.
 // Part of the single translation unit of rafft_api.hip (included there, after rafft_submit.h).
 #pragma once
 
@@ -186,7 +186,7 @@ int kin_rate_matrix(int n_steps, const int *step_size, int L, const char *rows, 
     hipLaunchKernelGGL(kin_pair_table_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (int)n, L, d_rows, d_pt, d_stack, d_bad);
     HIPCHK(hipGetLastError());
     for (int i = 0; i < n_steps; i++) {
-        const int pi = i == 0 ? n_steps - 1 : i - 1;      // the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)
+        const int pi = kin_prev_step(i, n_steps);
         if (!step_size[i] || !step_size[pi]) continue;
         hipLaunchKernelGGL(kin_rates_kernel, dim3((unsigned)step_size[i]), dim3(KIN_NT), (size_t)L * 2, st, L, d_pt, row0[i], step_size[pi], row0[pi],
                            d_uid, d_en, kt, n_unique, rate_device);
@@ -198,190 +198,6 @@ int kin_rate_matrix(int n_steps, const int *step_size, int L, const char *rows, 
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (bad) return fail(RAFFT_ERR_STRUCT, "malformed dot-bracket row");
-    return 0;
-}
-
-// rafft_kin_batch (arguments validated by the entry point).  Two passes over the device: structure identity for every graph, then -
-// the numbers of unique structures being known - rates and integration for chunks of graphs whose matrices fit the workspace budget.
-constexpr size_t KIN_BATCH_WORKSPACE = (size_t)512 << 20;
-
-int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows, const int *row_stride,
-              const double *const *energy, double kt, int n_times, const int *m, const double *h, long long workspace_bytes,
-              rafft_kin_graph *rec, int *uid_out, int *first_row_out, double *pop_out, double *const *rate_out)
-{
-    std::vector<KinGraph> gs(n_graphs);
-    long long n = 0;
-    unsigned long long bytes = 0;
-    int Lmax = 0;
-    for (int g = 0; g < n_graphs; g++) {
-        long long nr = 0;
-        for (int i = 0; i < n_steps[g]; i++) nr += step_size[g][i];
-        if (n + nr > 0x7fffffff) return fail(RAFFT_ERR_PARAM, "too many rows");
-        gs[g] = KinGraph{bytes, 0, lens[g], (int)nr, (int)n, 0};
-        rec[g] = rafft_kin_graph{0, (int)nr, (int)n, 0, 0, 0};
-        n += nr;
-        bytes += (unsigned long long)nr * (unsigned long long)lens[g];
-        if (nr) Lmax = std::max(Lmax, lens[g]);
-    }
-    if (n == 0) return 0;
-    // rows packed back to back; per row: its graph, the step it is compared with, its energy
-    std::vector<char> pack(bytes + 1);
-    std::vector<int> row_graph(n), row_prev0(n), row_nprev(n);
-    std::vector<double> en(n);
-    for (int g = 0; g < n_graphs; g++) {
-        const KinGraph &G = gs[g];
-        if (!G.n_rows) continue;
-        if (row_stride[g] == G.L) memcpy(pack.data() + G.off, rows[g], (size_t)G.n_rows * G.L);
-        else for (int r = 0; r < G.n_rows; r++) memcpy(pack.data() + G.off + (size_t)r * G.L, rows[g] + (size_t)r * row_stride[g], (size_t)G.L);
-        memcpy(en.data() + G.row0, energy[g], (size_t)G.n_rows * sizeof(double));
-        std::vector<int> s0(n_steps[g]);
-        int at = G.row0;
-        for (int i = 0; i < n_steps[g]; i++) { s0[i] = at; at += step_size[g][i]; }
-        for (int i = 0; i < n_steps[g]; i++) {
-            const int pi = i == 0 ? n_steps[g] - 1 : i - 1;   // the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)
-            for (int r = s0[i]; r < s0[i] + step_size[g][i]; r++) { row_graph[r] = g; row_prev0[r] = s0[pi]; row_nprev[r] = step_size[g][pi]; }
-        }
-    }
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    hipStream_t st = sg.stream;
-    DevScratch mem;
-    KinGraph *d_gs; char *d_rows; int16_t *d_pt, *d_stack; unsigned long long *d_hash; double *d_en, *d_enu, *d_h;
-    int *d_rg, *d_p0, *d_np, *d_bad, *d_first, *d_rank, *d_frow, *d_nu, *d_uid, *d_ne, *d_m;
-    const size_t n4 = (size_t)n * 4, g4 = (size_t)n_graphs * 4;
-    if (int rc = mem.alloc(d_gs, gs.size() * sizeof(KinGraph))) return rc;
-    if (int rc = mem.alloc(d_rows, bytes + 1)) return rc;
-    if (int rc = mem.alloc(d_pt, (bytes + 1) * 2)) return rc;
-    if (int rc = mem.alloc(d_stack, (bytes + 1) * 2)) return rc;
-    if (int rc = mem.alloc(d_hash, n4 * 2)) return rc;
-    if (int rc = mem.alloc(d_en, n4 * 2)) return rc;
-    if (int rc = mem.alloc(d_enu, n4 * 2)) return rc;
-    if (int rc = mem.alloc(d_rg, n4)) return rc;
-    if (int rc = mem.alloc(d_p0, n4)) return rc;
-    if (int rc = mem.alloc(d_np, n4)) return rc;
-    if (int rc = mem.alloc(d_first, n4)) return rc;
-    if (int rc = mem.alloc(d_rank, n4)) return rc;
-    if (int rc = mem.alloc(d_frow, n4)) return rc;
-    if (int rc = mem.alloc(d_uid, n4)) return rc;
-    if (int rc = mem.alloc(d_bad, g4)) return rc;
-    if (int rc = mem.alloc(d_nu, g4)) return rc;
-    if (int rc = mem.alloc(d_ne, g4)) return rc;
-    if (int rc = mem.alloc(d_m, (size_t)n_times * 4)) return rc;
-    if (int rc = mem.alloc(d_h, (size_t)n_times * 8)) return rc;
-    HIPCHK(hipMemcpyAsync(d_gs, gs.data(), gs.size() * sizeof(KinGraph), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rows, pack.data(), bytes + 1, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_en, en.data(), n4 * 2, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rg, row_graph.data(), n4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_p0, row_prev0.data(), n4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_np, row_nprev.data(), n4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_m, m, (size_t)n_times * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_h, h, (size_t)n_times * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_bad, 0, g4, st));
-    HIPCHK(hipMemsetAsync(d_ne, 0, g4, st));
-    HIPCHK(hipMemsetAsync(d_frow, 0xff, n4, st));            // -1: no such unique structure
-    HIPCHK(hipMemsetAsync(d_rank, 0, n4, st));
-    const unsigned nb64 = (unsigned)((n + 63) / 64);
-    hipLaunchKernelGGL(kin_batch_pair_table_kernel, dim3(nb64), dim3(64), 0, st, (int)n, d_gs, d_rg, d_rows, d_pt, d_stack, d_hash, d_bad);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(kin_batch_identity_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (int)n, d_gs, d_rg, d_rows, d_hash, d_first);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(kin_batch_rank_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, d_gs, d_first, d_en, d_rank, d_frow, d_enu, d_nu);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(kin_batch_uid_kernel, dim3(nb64), dim3(64), 0, st, (int)n, d_gs, d_rg, d_first, d_rank, d_uid);
-    HIPCHK(hipGetLastError());
-    std::vector<int> bad(n_graphs), nu(n_graphs);
-    HIPCHK(hipMemcpyAsync(bad.data(), d_bad, g4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(nu.data(), d_nu, g4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(uid_out, d_uid, n4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(first_row_out, d_frow, n4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::string first_err;
-    for (int g = 0; g < n_graphs; g++) {
-        KinGraph &G = gs[g];
-        if (bad[g]) {
-            rec[g].status = RAFFT_ERR_STRUCT;
-            if (first_err.empty()) first_err = "graph " + std::to_string(g) + ": malformed dot-bracket row";
-        } else if (nu[g] > RAFFT_KIN_BATCH_MAX_STATES) {
-            rec[g].status = RAFFT_ERR_CAPACITY;
-            rec[g].n_unique = nu[g];
-            if (first_err.empty())
-                first_err = "graph " + std::to_string(g) + ": " + std::to_string(nu[g]) + " unique structures, the batch path takes up to " +
-                            std::to_string(RAFFT_KIN_BATCH_MAX_STATES) + " - use the single-graph path (rafft_kin_rate_matrix and a dense or sparse solver)";
-        } else {
-            rec[g].n_unique = G.S = nu[g];
-            continue;
-        }
-        for (int r = 0; r < G.n_rows; r++) uid_out[G.row0 + r] = first_row_out[G.row0 + r] = -1;
-    }
-    // chunks of consecutive graphs: three S x S blocks per graph and the populations of the chunk within the budget (one graph at least)
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : KIN_BATCH_WORKSPACE;
-    struct Chunk { int ga, gb; };
-    std::vector<Chunk> chunks;
-    size_t ws_max = 0, pop_max = 0;
-    for (int ga = 0; ga < n_graphs; ) {
-        size_t w = 0, pp = 0;
-        int gb = ga;
-        while (gb < n_graphs) {
-            const size_t dw = 3 * (size_t)gs[gb].S * gs[gb].S * 8, dp = (size_t)n_times * gs[gb].n_rows * 8;
-            if (gb > ga && (w + dw > budget || pp + dp > budget)) break;
-            gs[gb].mat = w / 8;
-            w += dw; pp += dp; gb++;
-        }
-        chunks.push_back(Chunk{ga, gb});
-        ws_max = std::max(ws_max, w); pop_max = std::max(pop_max, pp);
-        ga = gb;
-    }
-    double *d_ws, *d_pop;
-    if (int rc = mem.alloc(d_ws, ws_max + 8)) return rc;
-    if (int rc = mem.alloc(d_pop, pop_max + 8)) return rc;
-    HIPCHK(hipMemcpyAsync(d_gs, gs.data(), gs.size() * sizeof(KinGraph), hipMemcpyHostToDevice, st));
-    constexpr size_t lds_small = (size_t)(4 * KIN_BATCH_LDS_STATES + 1 + KIN_BATCH_LDS_STATES * KIN_BATCH_LDS_STATES) * 8;
-    constexpr size_t lds_big = (size_t)(4 * RAFFT_KIN_BATCH_MAX_STATES + 1) * 8;
-    HIPCHK(hipFuncSetAttribute((const void *)kin_batch_integrate_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
-    // per chunk the graphs that are solved: those whose inverse fits LDS first, then the others
-    std::vector<int> order(n_graphs), n_small(chunks.size()), n_big(chunks.size());
-    for (size_t ci = 0; ci < chunks.size(); ci++) {
-        int at = chunks[ci].ga;
-        for (int g = chunks[ci].ga; g < chunks[ci].gb; g++) if (gs[g].S && gs[g].S <= KIN_BATCH_LDS_STATES) order[at++] = g;
-        n_small[ci] = at - chunks[ci].ga;
-        for (int g = chunks[ci].ga; g < chunks[ci].gb; g++) if (gs[g].S > KIN_BATCH_LDS_STATES) order[at++] = g;
-        n_big[ci] = at - chunks[ci].ga - n_small[ci];
-    }
-    int *d_order;
-    if (int rc = mem.alloc(d_order, g4)) return rc;
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), g4, hipMemcpyHostToDevice, st));
-    for (size_t ci = 0; ci < chunks.size(); ci++) {
-        const Chunk &c = chunks[ci];
-        const int ra = gs[c.ga].row0, rb = c.gb < n_graphs ? gs[c.gb].row0 : (int)n;
-        const int small = n_small[ci], big = n_big[ci];
-        size_t w = 0;
-        for (int g = c.ga; g < c.gb; g++) w += 3 * (size_t)gs[g].S * gs[g].S * 8;
-        if (rb == ra) continue;
-        if (!small && !big) { memset(pop_out + (size_t)n_times * ra, 0, (size_t)n_times * (rb - ra) * 8); continue; }
-        HIPCHK(hipMemsetAsync(d_ws, 0, w, st));
-        HIPCHK(hipMemsetAsync(d_pop, 0, (size_t)n_times * (rb - ra) * 8, st));
-        hipLaunchKernelGGL(kin_batch_rates_kernel, dim3((unsigned)(rb - ra)), dim3(KIN_NT), (size_t)Lmax * 2, st, ra, d_gs, d_rg, d_p0, d_np, d_pt, d_uid, d_enu, kt, d_ws);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(kin_batch_diag_kernel, dim3((unsigned)(rb - ra)), dim3(256), 0, st, ra, d_gs, d_rg, d_ws, d_ne);
-        HIPCHK(hipGetLastError());
-        if (small) {
-            hipLaunchKernelGGL(kin_batch_integrate_kernel<true>, dim3((unsigned)small), dim3(KINB_NT), lds_small, st, d_order + c.ga, ra, d_gs, d_ws, n_times, d_m, d_h, d_pop);
-            HIPCHK(hipGetLastError());
-        }
-        if (big) {
-            hipLaunchKernelGGL(kin_batch_integrate_kernel<false>, dim3((unsigned)big), dim3(KINB_NT), lds_big, st, d_order + c.ga + small, ra, d_gs, d_ws, n_times, d_m, d_h, d_pop);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(pop_out + (size_t)n_times * ra, d_pop, (size_t)n_times * (rb - ra) * 8, hipMemcpyDeviceToHost, st));
-        if (rate_out)
-            for (int g = c.ga; g < c.gb; g++)
-                if (rate_out[g] && gs[g].S) HIPCHK(hipMemcpyAsync(rate_out[g], d_ws + gs[g].mat, (size_t)gs[g].S * gs[g].S * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    std::vector<int> ne(n_graphs);
-    HIPCHK(hipMemcpy(ne.data(), d_ne, g4, hipMemcpyDeviceToHost));
-    for (int g = 0; g < n_graphs; g++) rec[g].n_edges = ne[g];
-    g_err = first_err;
     return 0;
 }
 
@@ -636,239 +452,6 @@ int score_result(const rafft_result *r, const char *const *known, rafft_score_ro
         rows_bytes = pack.size();
     }
     return score_held(sg.stream, n_seq, lens.data(), n_rows.data(), stride.data(), rows_off.data(), pre.data(), src, rows_bytes, known, row_out, seq_out);
-}
-
-// ---- minimum-free-energy folds
-
-constexpr size_t MFE_WORKSPACE = (size_t)512 << 20;
-
-// rafft_mfe_batch (arguments validated by the entry point).  Sequences up to `lds_len` go through mfe_lds_kernel in one launch, the
-// others through the HBM class in chunks whose tables fit the workspace budget (one sequence at least): per chunk one launch per
-// anti-diagonal, then the traceback.  One synchronise at the end.
-int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int lds_len, long long workspace_bytes, rafft_mfe_seq *seq_out,
-              char *const *db_out)
-{
-    // as the fold's entry (validate_params): before any sequence is looked at, so a batch of nothing but erroneous sequences fails too
-    if (!(temp > -273.15 && temp < 1000.0)) return fail(RAFFT_ERR_TEMP, "temp out of range");
-    if (temp != 37.0 && !param_set().has_dH)
-        return fail(RAFFT_ERR_TEMP, "temp != 37 needs the enthalpy tables of a ViennaRNA parameter file (rafft_load_params); the built-in tables are 37 C only");
-    if (n_seq == 0) return 0;
-    std::vector<MfeSeq> qs(n_seq);
-    std::vector<int> lds_order, hbm_order;
-    unsigned long long n_codes = 0, n_stack = 0, n_db = 0;
-    std::string first_err;
-    for (int s = 0; s < n_seq; s++) {
-        int st = 0;
-        if (lens[s] <= 0) st = RAFFT_ERR_EMPTY;
-        else if (lens[s] > RAFFT_MFE_MAX_LEN) st = RAFFT_ERR_TOO_LONG;
-        else for (int x = 0; x < lens[s] && !st; x++) if (kBaseCode[(unsigned char)seqs[s][x]] & 8) st = RAFFT_ERR_BAD_CHAR;
-        const int len = lens[s] > 0 ? lens[s] : 0;
-        seq_out[s] = rafft_mfe_seq{st, len, 0, 0};
-        memset(db_out[s], '.', (size_t)len);
-        db_out[s][len] = 0;
-        qs[s] = MfeSeq{n_codes, 0, n_stack, n_db, st ? 0 : len, 0};
-        if (st) {
-            if (first_err.empty())
-                first_err = "sequence " + std::to_string(s) + (st == RAFFT_ERR_EMPTY ? ": empty" : st == RAFFT_ERR_TOO_LONG ? ": longer than RAFFT_MFE_MAX_LEN" : ": character outside ACGUN");
-            continue;
-        }
-        n_codes += (unsigned long long)len; n_stack += (unsigned long long)len + 8; n_db += (unsigned long long)len + 1;
-        (len <= lds_len ? lds_order : hbm_order).push_back(s);
-    }
-    g_err = first_err;
-    if (lds_order.empty() && hbm_order.empty()) return 0;
-    std::vector<uint8_t> codes(n_codes + 16, 0);
-    for (int s = 0; s < n_seq; s++)
-        for (int x = 0; x < qs[s].L; x++) codes[qs[s].code_off + x] = (uint8_t)(kBaseCode[(unsigned char)seqs[s][x]] & 7);
-    // the longest first: the workgroups of a launch that run last are the short ones
-    std::stable_sort(lds_order.begin(), lds_order.end(), [&](int a, int b) { return qs[a].L > qs[b].L; });
-    // chunks of the HBM class, in input order
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE;
-    struct Chunk { size_t a, b; int Lmax; };
-    std::vector<Chunk> chunks;
-    size_t ws_max = 0;
-    for (size_t a = 0; a < hbm_order.size();) {
-        size_t w = 0, b = a;
-        int Lmax = 0;
-        while (b < hbm_order.size() && b - a < 65535) {
-            MfeSeq &q = qs[hbm_order[b]];
-            const size_t dw = 3 * (size_t)q.L * q.L * 4;
-            if (b > a && w + dw > budget) break;
-            q.tab_off = w / 4;
-            w += dw; Lmax = std::max(Lmax, q.L); b++;
-        }
-        chunks.push_back(Chunk{a, b, Lmax});
-        ws_max = std::max(ws_max, w);
-        a = b;
-    }
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    if (int rc = ensure_tables(temp)) return rc;
-    hipStream_t st = sg.stream;
-    DevScratch mem;
-    MfeSeq *d_qs; uint8_t *d_codes; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr;
-    std::vector<int> order(lds_order);
-    order.insert(order.end(), hbm_order.begin(), hbm_order.end());
-    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSeq))) return rc;
-    if (int rc = mem.alloc(d_codes, codes.size())) return rc;
-    if (int rc = mem.alloc(d_stack, n_stack * 4 + 16)) return rc;
-    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
-    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
-    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
-    if (ws_max) if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
-    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
-    if (!lds_order.empty()) {
-        HIPCHK(hipFuncSetAttribute((const void *)mfe_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MFE_LDS_BYTES));
-        hipLaunchKernelGGL(mfe_lds_kernel, dim3((unsigned)lds_order.size()), dim3(MFE_LDS_NT), (size_t)mfe_lds_bytes(qs[lds_order[0]].L), st, g.T, d_qs, d_order,
-                           d_codes, d_stack, d_db, d_rec);
-        HIPCHK(hipGetLastError());
-    }
-    for (const Chunk &c : chunks) {
-        const int *ord = d_order + lds_order.size() + c.a;
-        const unsigned ny = (unsigned)(c.b - c.a);
-        for (int d = 0; d < c.Lmax; d++) {
-            const unsigned nx = (unsigned)std::min((c.Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
-            hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d);
-        }
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(mfe_traceback_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_stack, d_db, d_rec);
-        HIPCHK(hipGetLastError());
-    }
-    std::vector<int4> rec(n_seq);
-    std::vector<char> db(n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int s = 0; s < n_seq; s++) {
-        if (seq_out[s].status) continue;
-        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
-        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
-        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
-    }
-    g_err = first_err;
-    return 0;
-}
-
-// ---- partition function and pair probabilities
-
-constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
-
-// rafft_pf_batch (arguments validated by the entry point).  The MFE of every sequence first (mfe_batch: its errors are this call's,
-// its energy gives the scale), then chunks of whole sequences in input order whose six L x L fp64 tables fit the workspace budget
-// (one sequence at least): per chunk one launch per anti-diagonal upwards, the exterior sums, one launch per anti-diagonal downwards,
-// the probabilities.  One synchronise at the end.
-int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, rafft_pf_seq *seq_out,
-             char *const *db_out, double *const *prob_out)
-{
-    std::vector<rafft_mfe_seq> mfe(std::max(n_seq, 1));
-    if (int rc = mfe_batch(n_seq, seqs, lens, temp, RAFFT_MFE_LDS_LEN, workspace_bytes, mfe.data(), db_out)) return rc;
-    if (n_seq == 0) return 0;
-    const std::string first_err = g_err;
-    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
-    std::vector<PfSeq> qs(n_seq);
-    std::vector<int> order;
-    unsigned long long n_codes = 0, n_aux = 0, n_db = 0;
-    for (int s = 0; s < n_seq; s++) {
-        const int len = mfe[s].length;
-        seq_out[s] = rafft_pf_seq{mfe[s].status, len, mfe[s].dcal, 0, 0.0, 0.0};
-        memset(db_out[s], '.', (size_t)len);
-        db_out[s][len] = 0;
-        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)len * len * sizeof(double));
-        const int L = mfe[s].status ? 0 : len;
-        const double ln_scale = L ? -sf * ((double)mfe[s].dcal / 100.0) / (kt * (double)L) : 0.0;
-        const double scale = std::exp(ln_scale);
-        qs[s] = PfSeq{n_codes, 0, n_aux, n_db, L, mfe[s].dcal, scale, std::log(scale)};
-        if (!L) continue;
-        n_codes += (unsigned long long)L; n_aux += 4 * ((unsigned long long)L + 1); n_db += (unsigned long long)L + 1;
-        order.push_back(s);
-    }
-    if (order.empty()) return 0;
-    std::vector<uint8_t> codes(n_codes + 16, 0);
-    for (int s = 0; s < n_seq; s++)
-        for (int x = 0; x < qs[s].L; x++) codes[qs[s].code_off + x] = (uint8_t)(kBaseCode[(unsigned char)seqs[s][x]] & 7);
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE;
-    struct Chunk { size_t a, b; int Lmax; };
-    std::vector<Chunk> chunks;
-    size_t ws_max = 0;
-    for (size_t a = 0; a < order.size();) {
-        size_t w = 0, b = a;
-        int Lmax = 0;
-        while (b < order.size() && b - a < 65535) {
-            PfSeq &q = qs[order[b]];
-            const size_t dw = 6 * (size_t)q.L * q.L * sizeof(double);
-            if (b > a && w + dw > budget) break;
-            q.tab_off = w / sizeof(double);
-            w += dw; Lmax = std::max(Lmax, q.L); b++;
-        }
-        chunks.push_back(Chunk{a, b, Lmax});
-        ws_max = std::max(ws_max, w);
-        a = b;
-    }
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    if (int rc = ensure_tables(temp)) return rc;
-    hipStream_t st = sg.stream;
-    DevScratch mem;
-    PfSeq *d_qs; uint8_t *d_codes; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
-    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(PfSeq))) return rc;
-    if (int rc = mem.alloc(d_codes, codes.size())) return rc;
-    if (int rc = mem.alloc(d_aux, n_aux * sizeof(double) + 16)) return rc;
-    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
-    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(PfRec))) return rc;
-    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
-    if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
-    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(PfSeq), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(PfRec), st));
-    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, d_qs, n_seq, d_aux, beta);
-    HIPCHK(hipGetLastError());
-    for (const Chunk &c : chunks) {
-        const int *ord = d_order + c.a;
-        const unsigned ny = (unsigned)(c.b - c.a);
-        const auto nx = [&](int d) { return (unsigned)std::min((c.Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); };
-        for (int d = 0; d < c.Lmax; d++)
-            hipLaunchKernelGGL(pf_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pf_exterior_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, kt, d_db, d_rec);
-        HIPCHK(hipGetLastError());
-        for (int d = c.Lmax - 1; d >= 4; d--)
-            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pf_prob_kernel, dim3(nx(0), ny), dim3(PF_NT), 0, st, d_qs, ord, d_ws, d_aux, d_db, d_rec);
-        HIPCHK(hipGetLastError());
-        if (prob_out)
-            for (size_t k = c.a; k < c.b; k++) {
-                const PfSeq &q = qs[order[k]];
-                if (prob_out[order[k]])
-                    HIPCHK(hipMemcpyAsync(prob_out[order[k]], d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
-            }
-    }
-    std::vector<PfRec> rec(n_seq);
-    std::vector<char> db(n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::string err = first_err;
-    for (int s = 0; s < n_seq; s++) {
-        if (seq_out[s].status) continue;
-        if (rec[s].status || rec[s].bad) {
-            // the scaled tables left the fp64 range: no number of this sequence is reported
-            seq_out[s].status = RAFFT_ERR_CAPACITY;
-            if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)qs[s].L * qs[s].L * sizeof(double));
-            if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
-            continue;
-        }
-        seq_out[s].n_pairs = rec[s].n_pairs;
-        seq_out[s].energy = rec[s].energy;
-        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
-        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
-    }
-    g_err = err;
-    return 0;
 }
 
 } // namespace

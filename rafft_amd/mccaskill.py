@@ -34,11 +34,7 @@ def pf_batch_raw(sequences, temp=37.0, scale_factor=0.0, workspace_bytes=0, prob
     L = N.lib()
     _params_mod.ensure_default_params()
     n = len(sequences)
-    enc = [s.encode("ascii", "replace") for s in sequences]
-    arr = (C.c_char_p * n)(*enc)
-    lens = (C.c_int * n)(*map(len, enc))
-    bufs = [C.create_string_buffer(len(e) + 1) for e in enc]
-    out = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+    enc, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
     rec = (N.PfSeq * n)()
     pr, ptrs = None, None
     if probs:

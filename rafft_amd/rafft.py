@@ -193,9 +193,7 @@ def submit_batch(sequences, nb_mode=100, max_stack=1, max_branch=100, min_hp=3, 
     _params_mod.ensure_default_params()
     p = _params(nb_mode, max_stack, max_branch, min_hp, min_nrj, traj, temp, gc_wei, au_wei, gu_wei)
     n = len(sequences)
-    enc = [s.encode("ascii", "replace") for s in sequences]
-    arr = (C.c_char_p * n)(*enc)
-    lens = (C.c_int * n)(*map(len, enc))
+    _, arr, lens = N.seq_arrays(sequences)
     job = C.c_void_p()
     N.check(L.rafft_fold_submit(C.byref(p), n, arr, lens, device, C.byref(job)))
     return PendingBatch(L, job, sequences, bool(traj), raise_errors)

@@ -1,7 +1,5 @@
 """Minimum-free-energy structures on the GPU (rafft_mfe_batch): what the reference gets from ViennaRNA's
 RNA.fold for the comparison column of its benchmark (benchmark_results/src/vrna_mfe.py:25, bench_mfe.py:11-15)."""
-import ctypes as C
-
 import numpy as np
 
 from . import _native as N
@@ -16,11 +14,7 @@ def mfe_batch_raw(sequences, temp=37.0, max_lds_len=0, workspace_bytes=0):
     L = N.lib()
     _params_mod.ensure_default_params()
     n = len(sequences)
-    enc = [s.encode("ascii", "replace") for s in sequences]
-    arr = (C.c_char_p * n)(*enc)
-    lens = (C.c_int * n)(*map(len, enc))
-    bufs = [C.create_string_buffer(len(e) + 1) for e in enc]
-    out = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+    _, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
     rec = (N.MfeSeq * n)()
     N.check(L.rafft_mfe_batch(n, arr, lens, float(temp), int(max_lds_len), int(workspace_bytes), rec, out))
     return ([b.value.decode("ascii") for b in bufs], [r.dcal for r in rec], [r.n_pairs for r in rec], [r.status for r in rec])
