@@ -1,5 +1,6 @@
 // rafft_expand_common.h - what expand_kernel (both its one-wavefront and its wide-team branch) and expand_small_kernel must
-// agree on bit for bit, written once: the record of a kept candidate and the statistics lines.  The kernels keep what differs
+// agree on bit for bit, written once: the value of a lag, the eligible prefix of a half-diagonal, the record of a kept candidate
+// and the statistics lines.  The kernels keep what differs
 // between team shapes and call these.  Everything here is inlined into its caller: the expand kernels have no registers to
 // spare for a call.
 #pragma once
@@ -25,6 +26,30 @@ __device__ __forceinline__ void emit_cand(const Dev &d, const uint32_t *brl, int
     cd.h1 = h1; cd.h2 = h2;
     d.cand[slot] = cd;
     d.cslot[slot] = 0ULL;      // (both child slots: nobody has asked yet)
+}
+
+// The value of lag k of a region with 2n-1 = m lags, from its three exact pair counts (rafft/utils.py:125-132): the weighted pairs of
+// the diagonal, both strands, over the length of the shorter arm + 1.  IEEE fp64, the same operations in the same order everywhere.
+__device__ __forceinline__ double lag_value(double cAU, double cGC, double cGU, int k, int m, const Dev &d)
+{
+    const double raw = (2.0 * cAU) * d.au + (2.0 * cGC) * d.gc + (2.0 * cGU) * d.gu;
+    const int nk = k < m - 1 - k ? k : m - 1 - k;
+    return raw / ((double)nk + 1.0);
+}
+
+// Eligible cells of a half-diagonal (pos[jp] - pos[ip] > min_hp; cell i is (ip0 + i, jp0 - i), i < len2) form a prefix: its length.
+// Positions are strictly increasing, so pos[jp] - pos[ip] >= jp - ip = len - 1 - 2 i: every cell with len - 1 - 2 i > min_hp is
+// eligible without looking, and the search only covers the (min_hp + 3) / 2 cells that remain at the inner end of the half-diagonal
+// (two steps for min_hp = 3 where the search over all of it took log2(len / 2) dependent pairs of LDS reads)
+__device__ __forceinline__ int eligible_prefix(const uint16_t *pos, int len, int len2, int ip0, int jp0, int min_hp)
+{
+    const int csure = len - 1 - min_hp;
+    int lo = csure > 0 ? min((csure + 1) >> 1, len2) : 0, hi = len2;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int)pos[jp0 - mid] - (int)pos[ip0 + mid] > min_hp) lo = mid + 1; else hi = mid;
+    }
+    return lo;
 }
 
 // A team's share of the launch's statistics, added to its line: regions expanded, their positions, lags and branches ...

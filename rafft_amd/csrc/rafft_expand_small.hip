@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
         const int rs = 32 - n;                                      // strand reversed: bit j of r? = bit n-1-j of m?
         const uint32_t rA = __brev(mA) >> rs, rC = __brev(mC) >> rs, rG = __brev(mG) >> rs, rU = __brev(mU) >> rs, rg = __brev(mg) >> rs;
         wave_sync();
-        double wgc = d.gc, wau = d.au, wgu = d.gu;      // (the pair weights in vector registers of their own: expand_kernel's cell loop)
+        double wgc = d.gc, wau = d.au, wgu = d.gu;      // (the pair weights in vector registers of their own: expand_kernel's window_slide)
         asm volatile("" : "+v"(wgc), "+v"(wau), "+v"(wgu));
 
         // ---- window_slide of every lag (rafft/rafft.py:36-83); a lane owns lags tl and tl + TL
@@ -156,14 +156,7 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
                 const int len = k < n ? k + 1 : 2 * n - k - 1;
                 const int len2 = (len >> 1) + (len & 1);
                 const int ip0 = k < n ? 0 : k - n + 1, jp0 = k < n ? k : n - 1;
-                // eligible cells (pos[jp]-pos[ip] > min_hp) form a prefix; those with jp - ip > min_hp are eligible without looking (expand_kernel)
-                const int csure = len - 1 - d.min_hp;
-                int lo = csure > 0 ? min((csure + 1) >> 1, len2) : 0, hi = len2;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if ((int)pos[jp0 - mid] - (int)pos[ip0 + mid] > d.min_hp) lo = mid + 1; else hi = mid;
-                }
-                const int lim = lo;
+                const int lim = eligible_prefix(pos, len, len2, ip0, jp0, d.min_hp);
                 if (lim > 0) {
                     const int sft = n - 1 - k;              // bit ip of x? = base at position k - ip
                     const uint32_t xA = sm_shift(rA, sft), xC = sm_shift(rC, sft), xG = sm_shift(rG, sft), xU = sm_shift(rU, sft);
@@ -298,10 +291,7 @@ __global__ __launch_bounds__(64 * SM_WG_WAVES, RAFFT_SMALL_WAVES) void expand_sm
             if ((w_keep[s] || dbg) && act && k < m) {
                 const int sft = n - 1 - k;
                 const uint32_t xU = sm_shift(rU, sft), xC = sm_shift(rC, sft);
-                const double nAU = 2.0 * (double)__popc(mA & xU), nGC = 2.0 * (double)__popc(mG & xC), nGU = 2.0 * (double)__popc(mG & xU);
-                const double raw = nAU * d.au + nGC * d.gc + nGU * d.gu;
-                const int nk = k < m - 1 - k ? k : m - 1 - k;
-                w_val[s] = raw / ((double)nk + 1.0);
+                w_val[s] = lag_value((double)__popc(mA & xU), (double)__popc(mG & xC), (double)__popc(mG & xU), k, m, d);
             }
         }
         int w_rank[2] = {0, 0};                       // seam only: rank of the lag by (value desc, lag desc) (rafft/rafft.py:117-118,92)

@@ -11,6 +11,8 @@
 //                       Template switch PROD: production builds with the debug seam and - for
 //                       the classes whose regions all take the popcount correlation - the FFT
 //                       compiled out (no register spills).
+//                       The body is the fetch loop and a list of phases (load_region ... emit_wave /
+//                       emit_team, inlined); RegionA is the one view of its time-shared LDS region.
 //   expand_small_kernel  (rafft_expand_small.hip) the same for regions of up to 16 / 32 positions:
 //                       teams of 16 / 32 lanes, four or two regions per wavefront
 //   beam_step_kernel    (rafft_beam.hip) one workgroup per sequence: helix combination in product order, flat
@@ -165,8 +167,8 @@ struct PlainView {
 
 // ---------------------------------------------------------------- kernels, one file each, in the order they need each other
 
-#include "rafft_expand_common.h"       // what the two expand kernels must agree on: candidate records, statistics lines
-#include "rafft_expand.hip"             // expand_kernel; fetch_plan / fetch_chunk, wave_sync
+#include "rafft_expand_common.h"       // what the two expand kernels must agree on: lag value, eligible prefix, candidate records, statistics lines
+#include "rafft_expand.hip"             // fetch_plan / fetch_chunk, wave_sync; RegionA, the phases, expand_kernel
 #include "rafft_expand_small.hip"       // expand_small_kernel
 #include "rafft_beam.hip"               // beam_step_kernel, the seen table
 #include "rafft_materialize.hip"        // materialize_kernel, materialize_team_kernel, dedupe_kernel

@@ -46,7 +46,8 @@ int class_cfg(const Config &cfg, int K, int maxL, ClsCfg out[NGEN + 1], bool nof
         int Kmax = std::max(1, std::min(K, c == 0 ? 2 * big_n - 1 : P[c] - 1));
         const bool nf = (c == 1 && nofft1 && WPB[1] > 1) || (c == 2 && nofft2);
         ExpandLds l = expand_lds(P[c], LM[c], nmax, BR[c], Kmax, TAB[c], WPB[c], nf, NT[c], c != 0);      // (class 0: no LDS copy of the base codes - expand_kernel's CODE_LDS)
-        // region A is time-shared: behind the fp64 lag values (8 P bytes) it must still hold the branch prefix sums
+        // region A is time-shared (its tenants, their offsets and sizes: the table above RegionA in rafft_expand.hip, which these
+        // checks bound per class): behind the fp64 lag values (8 P bytes) it must still hold the branch prefix sums
         // (10 bytes per branch), the select histogram and the window_slide scratch of this class
         // (the partial results of chunked diagonals: C chunks per ranked lag, C = min(8, NT / lags) - 512 records of 24 bytes
         //  at the most until there are more lags than threads, not 8 per lag: that bound refused nb_mode 214-399 on sequences
@@ -83,6 +84,7 @@ int class_cfg(const Config &cfg, int K, int maxL, ClsCfg out[NGEN + 1], bool nof
         // (256 threads: at the 168 VGPRs the kernel needs without spilling a SIMD holds three wavefronts - three 256-thread
         //  workgroups per CU; a 512-thread workgroup is two wavefronts per SIMD, and two of those would need 128 VGPRs: 44 spilled)
         const int Cc = std::max(1, std::min(8, 256 / std::max(Kmax, 1)));
+        // (the tenants of region A with the lag values in HBM: RegionA's table, rafft_expand.hip)
         const bool fits = 8 * MASK_WORDS * (nmax / 64) + 24 * Cc * Kmax + 2048 + 64 <= 16 * Pd && 10 * (MAX_BR + 1) + 16 + 8 * Kmax + 2048 <= 16 * Pd;
         ExpandLds l = expand_lds(Pd, 0, nmax, MAX_BR, Kmax, false, 1, false, 256);
         if (fits && l.total <= 80 * 1024) {
