@@ -95,6 +95,63 @@ def index_sensitive_par(par, seed=2004):
     return out
 
 
+TIE_ML = ((0, 0, 0), (0, -400, -200))     # (ml_base, ml_closing, ml_intern): multiloops cost nothing / multiloops win
+
+
+def tie_par(par, ml):
+    """a flat parameter set, under which many structures of a sequence share the minimum and only the traceback's candidate order
+    decides the row: every stack -100, every mismatch and dangle 0, every loop table one constant whatever the size (hairpin 300,
+    bulge and interior 200, the tabulated 1x1 / 2x1 / 2x2 loops 200 as well), no special loops, terminal_au = ninio = lxc = 0, and
+    the multiloop scalars `ml` = (ml_base, ml_closing, ml_intern).  Built from index_sensitive_par's copy of `par` (no enthalpies)."""
+    out = index_sensitive_par(par)
+
+    def flat(name, value):
+        old = np.asarray(out[name])
+        out[name] = np.where(old >= PR.INF, old, value)
+
+    flat("stack", -100)
+    for name in MM_TABLES + ("dangle5", "dangle3"):
+        flat(name, 0)
+    flat("hairpin", 300)
+    for name in ("bulge", "interior", "int11", "int21", "int22"):
+        flat(name, 200)
+    out.update(ml_base=ml[0], ml_closing=ml[1], ml_intern=ml[2], ninio=0, max_ninio=300, terminal_au=0, lxc=0.0)
+    for name in KINDS:
+        out[name] = []
+    return out
+
+
+def tie_short_sequences():
+    """low-complexity, GC-only and random sequences of at most 20 nt (every structure can be enumerated), then N bases in a hairpin
+    loop, beside a closing pair inside and outside, in an interior loop and between two stems of a multiloop"""
+    rng = np.random.default_rng(4242)
+    seqs = ["GU" * 9, "G" * 8 + "U" * 8, "GCGCAAAGCGCAAAGCGC", "GGGUUUGGGUUUCCC", "GGGAAACCCAGGGAAACCCA", "GCGCGCGCGCGCGCGC", "GGCCGGCCAAAAGGCCGGCC",
+            "CCCCAAAAGGGGAAAACCCC", "GGGGAAAACCCCAAAAGGGG", "AU" * 9]
+    seqs += ["".join(rng.choice(list("GC"), n)) for n in (14, 16, 18)]
+    seqs += ["".join(rng.choice(list("ACGU"), n)) for n in (16, 18, 20)]
+    return seqs + N_SEQS
+
+
+# N pairs with nothing and reads row 0 of the mismatch and dangle tables
+N_SEQS = ["GGGNAAACCC", "GGNGAAACNCC", "GGGAAANCCCAGGGNAACCC", "GNGAAACGAAACGNAACC"]
+
+
+def tie_long_sequences():
+    """40-105 nt: random, GU-only, GC-only, repeats, and two constructed ones.  Under tie_par a hairpin of n pairs costs 400 - 100 n,
+    so one of five pairs and more is strictly favourable and cannot be traded for unpaired bases:
+    * a closing helix around a hairpin of 24 pairs, 18 N, a CG and a GU hairpin of five pairs (no helix between the two pairs as
+      many bases): the M split of the multiloop has its last
+      stem 69 positions after the first, the C split its last stem further still;
+    * two hairpins of five and four + one pairs with 55 A between them: the second exterior stem starts at position 68."""
+    rng = np.random.default_rng(99)
+    rand = lambda n, letters="ACGU": "".join(rng.choice(list(letters), n))
+    hp = lambda n, loop: "C" * n + loop + "G" * n
+    seqs = [rand(40), rand(60), rand(80), rand(100), rand(64, "GU"), rand(90, "GU"), rand(60, "GC"), rand(96, "GC"), "GGGAAACCC" * 5, "GGGAAACCC" * 11]
+    seqs.append("GGG" + "N" + hp(24, "NNNN") + "N" * 18 + hp(5, "NNN") + "N" + "GGGGGNNNUUUUU" + "N" + "CCC")
+    seqs.append("GGGGGAAACCCCC" + "A" * 55 + "GGGGCAAAGCCCC")
+    return seqs
+
+
 def special_lists(par):
     """{kind: [loop with its closing pair, ...]} in table order, duplicates dropped (the first entry wins)"""
     out = {}

@@ -12,6 +12,8 @@
       F[j]     = min(F[j-1], min_i F[i-1] + C[i][j] + exterior stem(i,j)),  MFE = F[L-1]
   `Mirror.mfe(seq)` is the energy in dcal.  The interior-loop candidates of a whole anti-diagonal are evaluated as one numpy
   expression, so a 90-nt sequence takes a fraction of a second.
+  `Mirror.fold(seq, order)` is `(dcal, row)`: the same tables traced back in the candidate order section 9 documents ("first"), or
+  with the last reproducing candidate of every cell ("last").
 """
 import math
 from functools import lru_cache
@@ -67,6 +69,7 @@ class Mirror:
         self.T = tables
         self.sc = tables["scalars"]
         self.special = {s: e for ent in tables["special"].values() for s, e in reversed(ent)}     # (the first entry of a table wins)
+        self._filled = {}                       # fill() of the sequences fold() was asked for: "first" and "last" share the tables
 
     def hairpin(self, seq, S, i, j):
         n, t = j - i - 1, PT[S[i], S[j]]
@@ -112,7 +115,22 @@ class Mirror:
             e += self.sc["term_au"]
         return e if ext else e + self.sc["ml_intern"]
 
-    def mfe(self, seq):
+    def interior_candidates(self, S, C, i, j):
+        """interior-loop candidate x = (n1, n2) of the cells (i[a], j[a]): its energy with C[p][q], INF where there is no such loop.
+        Rows = cells, columns = candidates with n1 ascending, then n2 ascending: p ascending, then q descending."""
+        L = len(S)
+        t = PT[S[i], S[j]]
+        p, q = i[:, None] + 1 + _N1[None, :], j[:, None] - 1 - _N2[None, :]
+        good = (q - p >= MIN_HP + 1) & (t[:, None] > 0)
+        pc, qc = np.where(good, p, 1), np.where(good, q, 1)
+        t2 = PT[S[pc], S[qc]]
+        inner = C[pc, qc]
+        good &= (t2 > 0) & (inner < BIG)
+        e = self.interior(_N1[None, :], _N2[None, :], t[:, None], RT[t2], S[i + 1][:, None], S[j - 1][:, None], S[pc - 1], S[np.minimum(qc + 1, L - 1)])
+        return np.where(good, e + inner, INF)
+
+    def fill(self, seq):
+        """(S, C, M, M1, F): the three tables, (L + 1) x (L + 1) with INF where there is no structure, and F[j + 1] of positions 0..j"""
         L = len(seq)
         S = np.array([CODE[c] for c in seq], dtype=np.int64)
         sc = self.sc
@@ -123,15 +141,7 @@ class Mirror:
             i = np.arange(0, L - d)
             j = i + d
             t = PT[S[i], S[j]]
-            # interior loops of the whole diagonal: rows = cells, columns = (n1, n2)
-            p, q = i[:, None] + 1 + _N1[None, :], j[:, None] - 1 - _N2[None, :]
-            good = (q - p >= MIN_HP + 1) & (t[:, None] > 0)
-            pc, qc = np.where(good, p, 1), np.where(good, q, 1)
-            t2 = PT[S[pc], S[qc]]
-            inner = C[pc, qc]
-            good &= (t2 > 0) & (inner < INF)
-            e = self.interior(_N1[None, :], _N2[None, :], t[:, None], RT[t2], S[i + 1][:, None], S[j - 1][:, None], S[pc - 1], S[np.minimum(qc + 1, L - 1)])
-            best_int = np.where(good, e + inner, INF).min(axis=1)
+            best_int = self.interior_candidates(S, C, i, j).min(axis=1)
             for a in range(L - d):
                 b = a + d
                 if t[a]:
@@ -157,4 +167,96 @@ class Mirror:
                 if C[i, j] < INF:
                     best = min(best, F[i] + int(C[i, j]) + self.stem(int(PT[S[i], S[j]]), nb(i - 1), nb(j + 1), True))
             F[j + 1] = best
-        return F[L]
+        return S, C, M, M1, F
+
+    def mfe(self, seq):
+        return self.fill(seq)[4][len(seq)]
+
+    def fold(self, seq, order="first"):
+        """(dcal, row): the tables of `fill`, traced back as DESIGN.md section 9 says.  A cell's candidates are visited in the documented
+        order - C: the hairpin, the interior loops (p ascending, then q descending), the multiloop splits (k ascending); M1: the stem,
+        j unpaired; M: M1, i unpaired, the splits (k ascending); F: j unpaired, the stems (i ascending) - a term is a candidate only
+        if its parts are below BIG, and the FIRST candidate that reproduces the stored value is taken.  order="last" takes the last
+        one instead: another co-optimal structure wherever a cell ties, there to show that an input discriminates.
+        `self.offsets` then holds, per kind of multi-candidate choice, the largest candidate offset that was taken: "F" the 5' end i
+        of an exterior stem, "M" k - (i + 5) of an M split, "C" k - (i + 6) of a C split, "I" the number x of an interior loop."""
+        assert order in ("first", "last")
+        pick = (lambda hits: hits[0]) if order == "first" else (lambda hits: hits[-1])
+        L, sc = len(seq), self.sc
+        if seq not in self._filled:
+            self._filled[seq] = self.fill(seq)
+        S, C, M, M1, F = self._filled[seq]
+        nb = lambda x: int(S[x]) if 0 <= x < L else -1
+        mlb = sc["ml_base"]
+        off = self.offsets = dict(F=-1, M=-1, C=-1, I=-1)
+        note = lambda key, x: off.__setitem__(key, max(off[key], int(x)))
+        stack, pt = [], [-1] * L
+        j = L - 1
+        while j >= MIN_HP + 1:
+            v = F[j + 1]
+            hits = [-1] if v == F[j] else []
+            for i in range(0, j - MIN_HP):
+                if C[i, j] < BIG and F[i] + int(C[i, j]) + self.stem(int(PT[S[i], S[j]]), nb(i - 1), nb(j + 1), True) == v:
+                    hits.append(i)
+            i = pick(hits)
+            if i < 0:
+                j -= 1
+                continue
+            note("F", i)
+            stack.append((i, j, "C"))
+            j = i - 1
+        while stack:
+            i, j, kind = stack.pop()
+            if kind == "M":
+                while True:
+                    v = int(M[i, j])
+                    assert v < BIG
+                    hits = [("M1", 0)] if M1[i, j] == v else []
+                    if j > i and M[i + 1, j] < BIG and int(M[i + 1, j]) + mlb == v:
+                        hits.append(("skip", 0))
+                    k = np.arange(i + MIN_HP + 2, j - MIN_HP)
+                    if len(k):
+                        a, b = M[i, k - 1], M1[k, j]
+                        hits += [("split", int(x)) for x in k[(a < BIG) & (b < BIG) & (a + b == v)]]
+                    what, k = pick(hits)
+                    if what == "skip":
+                        i += 1
+                        continue
+                    if what == "split":
+                        note("M", k - (i + MIN_HP + 2))
+                        stack.append((i, k - 1, "M"))
+                        i = k
+                    break
+                kind = "M1"
+            if kind == "M1":
+                while True:
+                    v = int(M1[i, j])
+                    assert v < BIG
+                    hits = []
+                    if C[i, j] < BIG and int(C[i, j]) + self.stem(int(PT[S[i], S[j]]), nb(i - 1), nb(j + 1), False) == v:
+                        hits.append("C")
+                    if j > i and M1[i, j - 1] < BIG and int(M1[i, j - 1]) + mlb == v:
+                        hits.append("skip")
+                    if pick(hits) == "C":
+                        break
+                    j -= 1
+            pt[i], pt[j] = j, i
+            v, t = int(C[i, j]), int(PT[S[i], S[j]])
+            assert t and v < BIG
+            hits = [("hairpin", 0)] if self.hairpin(seq, S, i, j) == v else []
+            il = self.interior_candidates(S, C, np.array([i]), np.array([j]))[0]
+            hits += [("interior", int(x)) for x in np.nonzero(il == v)[0]]
+            k = np.arange(i + MIN_HP + 3, j - MIN_HP - 1)
+            if len(k):
+                close = sc["ml_closing"] + self.stem(int(RT[t]), int(S[j - 1]), int(S[i + 1]), False)
+                a, b = M[i + 1, k - 1], M1[k, j - 1]
+                hits += [("split", int(x)) for x in k[(a < BIG) & (b < BIG) & (a + b + close == v)]]
+            what, x = pick(hits)
+            if what == "interior":
+                note("I", x)
+                stack.append((i + 1 + int(_N1[x]), j - 1 - int(_N2[x]), "C"))
+            elif what == "split":
+                note("C", x - (i + MIN_HP + 3))
+                stack.append((i + 1, x - 1, "M"))
+                stack.append((x, j - 1, "M1"))
+        return F[L], "".join("." if y < 0 else "(" if y > x else ")" for x, y in enumerate(pt))

@@ -108,6 +108,25 @@ def add_synthetic_enthalpies(par, seed=1):
     return out
 
 
+def synthetic_par(builtin):
+    """`builtin` (the built-in set as read_par returns it) with made-up enthalpies and every table moved off the built-in values, so
+    that a temperature other than 37 C is allowed and a loaded file is told from the built-in tables (mechanism tests only)."""
+    par = add_synthetic_enthalpies(builtin, seed=11)
+    rng = np.random.default_rng(5)
+    for k in ("stack", "int11", "int21", "int22", "mismatch_hairpin", "mismatch_interior", "mismatch_multi", "mismatch_exterior",
+              "dangle5", "dangle3", "mismatch_interior_1n", "mismatch_interior_23"):
+        par[k] = par[k] + 10 * rng.integers(-3, 4, size=par[k].shape)          # not the built-in values any more
+    st = par["stack"][:6, :6]
+    par["stack"][:6, :6] = np.minimum(st, st.T)                                  # (a stack table is symmetric in its two pairs)
+    par["hairpin"] = par["hairpin"].copy(); par["hairpin"][3:] += 10 * rng.integers(-3, 4, size=28)
+    par["bulge"] = par["bulge"].copy(); par["bulge"][1:] += 10 * rng.integers(-3, 4, size=30)
+    par["interior"] = par["interior"].copy(); par["interior"][2:] += 10 * rng.integers(-3, 4, size=29)
+    par["ml_closing"] += 30; par["ml_intern"] -= 10; par["terminal_au"] += 10; par["ninio"] += 10; par["lxc"] = 99.5
+    par["Tetraloops"] = par["Tetraloops"] + [("GAAAAC", 120, 500), ("CGAAAG", 90, -300)]
+    par["Triloops"] = par["Triloops"] + [("GAAAC", 300, 1000)]
+    return par
+
+
 def _rescale(g, dh, tempf):
     g = np.asarray(g, dtype=np.float64)
     dh = np.asarray(dh, dtype=np.float64)

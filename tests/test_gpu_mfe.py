@@ -1,9 +1,11 @@
 """rafft_mfe_batch on a real MI355X (`-m gpu`): the minimum over every structure of short sequences (evaluated by eval_kernel in one
 call), the tests' own mirror of the recurrences where enumeration cannot reach, the published ViennaRNA MFE rows as an upper bound,
-same input - same bits across batch position, order, chunking and size class, and errors that stay with their sequence.
-Integers and bytes: no tolerance."""
+same input - same bits across batch position, order, chunking and size class, errors that stay with their sequence, the rows of the
+mirror's traceback in the documented candidate order on tables that tie, other temperatures under a parameter file with enthalpies,
+and the length limit of 4096 nt.  Integers and bytes: no tolerance."""
 import gzip
 import os
+import time
 
 import numpy as np
 import pytest
@@ -25,16 +27,21 @@ def sets(tmp_path_factory):
     builtin = LP.builtin_par()
     idx = LP.index_sensitive_par(builtin)
     idx.update(ml_closing=-700, ml_intern=-300)               # negative enough that multiloops win at 16-20 nt
-    path = tmp_path_factory.mktemp("par") / "multiloops_win.par"
-    PR.write_par(idx, path, comment="index-sensitive, multiloops win")
-    return dict(builtin=builtin, multiloops_win=idx, path=path)
+    out = dict(builtin=builtin, multiloops_win=idx, tie0=LP.tie_par(builtin, LP.TIE_ML[0]), tie1=LP.tie_par(builtin, LP.TIE_ML[1]),
+               synthetic=PR.synthetic_par(builtin), paths={})
+    d = tmp_path_factory.mktemp("par")
+    for name, comment in (("multiloops_win", "index-sensitive, multiloops win"), ("tie0", "flat, multiloops cost nothing"),
+                          ("tie1", "flat, multiloops win"), ("synthetic", "made-up enthalpies")):
+        out["paths"][name] = d / (name + ".par")
+        PR.write_par(out[name], out["paths"][name], comment=comment)
+    return out
 
 
 def install(sets, which):
     if which == "builtin":
         params.reset_params()
     else:
-        params.load_params(sets["path"])
+        params.load_params(sets["paths"][which])
 
 
 @pytest.fixture(autouse=True)
@@ -59,11 +66,11 @@ def multiloops(db):
     return n
 
 
-def check_rows(seqs, raw):
+def check_rows(seqs, raw, temp=37.0):
     """what holds for every result: the row's own energy is the reported one, the pair count is the row's, pairs are canonical"""
     rows, dcal, n_pairs, status = raw
     assert not any(status)
-    got, st = R.eval_structures(seqs, rows)
+    got, st = R.eval_structures(seqs, rows, temp=temp)
     assert not any(st) and got == dcal
     assert n_pairs == [r.count("(") for r in rows]
     for s, r in zip(seqs, rows):
@@ -83,7 +90,7 @@ def exhaustive_sequences():
         for sp in LP.OWN_SPECIAL[name]:
             seqs.append("GG" + sp + "CC")
     seqs += ["GGGACACCCAGGACCACCC", "G" * 10 + "U" * 10, "GU" * 9, "GGGUUUGGGUUUCCC", "GCGCAAAGCGCAAAGCGC", "GGGAAACCCAGGGAAACCCA"]
-    return seqs
+    return seqs + LP.N_SEQS                                                        # N pairs with nothing and reads row 0 of the mismatch tables
 
 
 _ENUM = {}
@@ -96,20 +103,26 @@ def enumerated(seqs):
     return [_ENUM[s] for s in seqs]
 
 
-@pytest.mark.parametrize("which", TABLES)
-def test_gpu_mfe_is_the_minimum_over_every_structure_in_both_classes(sets, which):
-    install(sets, which)
-    seqs = exhaustive_sequences()
-    assert 36 <= len(seqs) <= 45 and max(map(len, seqs)) == 20
+def exhaustive_minimum(seqs, temp=37.0):
+    """the minimum of eval_kernel over every structure of each sequence, under the installed tables (one call)"""
     rows = enumerated(seqs)
     flat_s = [s for s, rr in zip(seqs, rows) for _ in rr]
     flat_r = [r for rr in rows for r in rr]
-    en, st = R.eval_structures(flat_s, flat_r)                                     # one call
+    en, st = R.eval_structures(flat_s, flat_r, temp=temp)
     assert not any(st)
     want, at = [], 0
     for rr in rows:
         want.append(min(en[at:at + len(rr)]))
         at += len(rr)
+    return want
+
+
+@pytest.mark.parametrize("which", TABLES)
+def test_gpu_mfe_is_the_minimum_over_every_structure_in_both_classes(sets, which):
+    install(sets, which)
+    seqs = exhaustive_sequences()
+    assert 40 <= len(seqs) <= 49 and max(map(len, seqs)) == 20 and sum("N" in s for s in seqs) == 4
+    want = exhaustive_minimum(seqs)
     lds = zuker.mfe_batch_raw(seqs)
     hbm = zuker.mfe_batch_raw(seqs, max_lds_len=4)
     assert lds == hbm                                                              # rows, energies, pair counts: byte-identical
@@ -258,7 +271,110 @@ def test_gpu_mfe_hbm_class_at_1000_nt():
     assert tuple(x[::-1] for x in rev) == raw
 
 
-# ---- 7. the command line with the real scorer
+# ---- 7. the traceback's candidate order
+
+_FOLD = {}
+
+
+def mirror_folds(sets, which, seqs, temp=37.0):
+    """Mirror.fold(s, "first") of every sequence under a table set: (dcal, row), computed once"""
+    key = (which, temp)
+    if key not in _FOLD:
+        _FOLD[key] = (MF.Mirror(PR.tables_at(sets[which], temp)), {})
+    mirror, done = _FOLD[key]
+    for s in seqs:
+        if s not in done:
+            done[s] = mirror.fold(s, "first")
+    return [done[s] for s in seqs]
+
+
+def assert_rows_are_the_mirrors(sets, which, seqs, temp=37.0):
+    want = mirror_folds(sets, which, seqs, temp)
+    routed = zuker.mfe_batch_raw(seqs, temp=temp)
+    forced = zuker.mfe_batch_raw(seqs, temp=temp, max_lds_len=4)
+    assert routed == forced
+    wrong = [(s, r, w[1]) for s, r, w in zip(seqs, routed[0], want) if r != w[1]]
+    assert not wrong, (which, len(wrong), wrong[:3])
+    assert routed[1] == [w[0] for w in want] and routed[2] == [w[1].count("(") for w in want]
+    check_rows(seqs, routed, temp)
+    return routed
+
+
+@pytest.mark.parametrize("which", ["tie0", "tie1"])
+def test_gpu_mfe_rows_follow_the_documented_order_where_the_tables_tie(sets, which):
+    """flat tables: most of these sequences have several structures of minimum energy (tests/test_mfe_host.py counts them and shows
+    that the reversed candidate order returns other rows), so the row is the documented order's or the test fails; the long list
+    reaches the second and later rounds of the four ballots"""
+    install(sets, which)
+    assert_rows_are_the_mirrors(sets, which, LP.tie_short_sequences() + LP.tie_long_sequences())
+    assert exhaustive_minimum(LP.tie_short_sequences()) == [w[0] for w in mirror_folds(sets, which, LP.tie_short_sequences())]
+
+
+@pytest.mark.parametrize("which", TABLES)
+def test_gpu_mfe_rows_are_the_mirrors_at_60_to_90_nt(sets, which):
+    install(sets, which)
+    assert_rows_are_the_mirrors(sets, which, mirror_sequences())
+
+
+# ---- 8. other temperatures
+
+@pytest.mark.parametrize("temp", [25.0, 60.0])
+def test_gpu_mfe_at_another_temperature(sets, temp):
+    """a parameter file with (made-up) enthalpies: at 25 and 60 C the energy is the minimum of eval_kernel at that temperature over
+    every structure, the mirror's over tables rescaled by the tests' own reader at 60-90 nt, rows included; both classes agree; the
+    results are not those of 37 C, and 37 C comes back afterwards"""
+    install(sets, "synthetic")
+    short, longer = exhaustive_sequences(), mirror_sequences()
+    at37 = zuker.mfe_batch_raw(short + longer)
+    lds = zuker.mfe_batch_raw(short, temp=temp)
+    assert lds == zuker.mfe_batch_raw(short, temp=temp, max_lds_len=4)
+    assert lds[1] == exhaustive_minimum(short, temp)
+    check_rows(short, lds, temp)
+    got = assert_rows_are_the_mirrors(sets, "synthetic", longer, temp)
+    n_other = sum(a != b for a, b in zip(lds[1] + got[1], at37[1]))
+    print(f"\n{temp} C: {n_other} of {len(at37[1])} energies differ from those at 37 C")
+    assert n_other >= 1
+    assert zuker.mfe_batch_raw(short + longer) == at37
+    assert at37[1][len(short):] == [w[0] for w in mirror_folds(sets, "synthetic", longer)]
+
+
+# ---- 9. the length limit
+
+def test_gpu_mfe_at_4096_nt(sets):
+    """positions up to 4095 through the 12-bit fields of the stack words.  Sequence 0: two hairpins 4068 A apart (no U: the spacer
+    pairs with nothing; an interior loop spans at most 30; ml_base is 0, so a multiloop across the spacer costs the same at any
+    length; a hairpin across it only gets dearer with lxc > 0) - its energy and row are the mirror's at a spacer of 40, stretched.
+    Sequence 1: 2100 nt of tiled hairpins, bit 11 of the stack words.  Sequence 2 is one too long, sequence 3 is short."""
+    h1, h2 = "GGGGGAAAACCCCC", "GCGCGGAAACGCGC"
+    tile, tile_row = "GGGGGAAAACCCCCAA", "(((((....))))).."
+    seqs = [h1 + "A" * (N.MFE_MAX_LEN - 28) + h2, tile * 131 + "GGGG", "A" * (N.MFE_MAX_LEN + 1), "GGGAAACCC"]
+    assert [len(s) for s in seqs] == [4096, 2100, 4097, 9]
+    assert sets["builtin"]["ml_base"] >= 0 and sets["builtin"]["lxc"] >= 0
+    small = h1 + "A" * 40 + h2
+    mirror = MF.Mirror(PR.tables_at(sets["builtin"], 37.0))
+    d40, row40 = mirror.fold(small, "first")
+    assert mirror.fold(small, "last") == (d40, row40)
+    pt = LP.pair_table(row40)
+    across = [(i, j) for i, j in enumerate(pt) if i < len(h1) and j >= len(h1) + 40]
+    assert not any("(" not in row40[i + 1:j] for i, j in across)                 # no hairpin closed across the spacer
+    t0 = time.perf_counter()
+    rows, dcal, n_pairs, status = zuker.mfe_batch_raw(seqs)
+    wall = time.perf_counter() - t0
+    print(f"\n4096 + 2100 nt in one call: {wall:.2f} s; MFE {dcal[0]} and {dcal[1]} dcal/mol, {n_pairs[0]} and {n_pairs[1]} pairs")
+    assert status == [0, 0, N.ERR_TOO_LONG, 0]
+    assert dcal[0] == d40 and rows[0] == row40[:len(h1)] + "." * (N.MFE_MAX_LEN - 28) + row40[len(h1) + 40:]
+    assert rows[0][N.MFE_MAX_LEN - 1] == ")" and LP.pair_table(rows[0])[N.MFE_MAX_LEN - 1] == N.MFE_MAX_LEN - len(h2)
+    keep = (0, 1, 3)
+    check_rows([seqs[k] for k in keep], ([rows[k] for k in keep], [dcal[k] for k in keep], [n_pairs[k] for k in keep], [0] * 3))
+    tiled, st = R.eval_structures([seqs[1]], [tile_row * 131 + "...."])
+    assert st == [0] and dcal[1] <= tiled[0] < 0
+    assert max(LP.pair_table(rows[1])) >= 2048                                     # pairs beyond bit 11
+    assert (rows[2], dcal[2], n_pairs[2]) == ("." * (N.MFE_MAX_LEN + 1), 0, 0)
+    alone = zuker.mfe_batch_raw(seqs[3:])
+    assert (rows[3], dcal[3], n_pairs[3]) == (alone[0][0], alone[1][0], alone[2][0])
+
+
+# ---- 10. the command line with the real scorer
 
 def test_gpu_cli_mfe_scores_table(tmp_path):
     from rafft_amd import cli, scoring

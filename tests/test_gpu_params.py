@@ -21,19 +21,7 @@ def synthetic(tmp_path):
     params.reset_params()
     p0 = tmp_path / "builtin.par"
     params.save_params(p0)
-    par = PR.add_synthetic_enthalpies(PR.read_par(p0), seed=11)
-    rng = np.random.default_rng(5)
-    for k in ("stack", "int11", "int21", "int22", "mismatch_hairpin", "mismatch_interior", "mismatch_multi", "mismatch_exterior",
-              "dangle5", "dangle3", "mismatch_interior_1n", "mismatch_interior_23"):
-        par[k] = par[k] + 10 * rng.integers(-3, 4, size=par[k].shape)          # not the built-in values any more
-    st = par["stack"][:6, :6]
-    par["stack"][:6, :6] = np.minimum(st, st.T)                                  # (a stack table is symmetric in its two pairs)
-    par["hairpin"] = par["hairpin"].copy(); par["hairpin"][3:] += 10 * rng.integers(-3, 4, size=28)
-    par["bulge"] = par["bulge"].copy(); par["bulge"][1:] += 10 * rng.integers(-3, 4, size=30)
-    par["interior"] = par["interior"].copy(); par["interior"][2:] += 10 * rng.integers(-3, 4, size=29)
-    par["ml_closing"] += 30; par["ml_intern"] -= 10; par["terminal_au"] += 10; par["ninio"] += 10; par["lxc"] = 99.5
-    par["Tetraloops"] = par["Tetraloops"] + [("GAAAAC", 120, 500), ("CGAAAG", 90, -300)]
-    par["Triloops"] = par["Triloops"] + [("GAAAC", 300, 1000)]
+    par = PR.synthetic_par(PR.read_par(p0))
     path = tmp_path / "synthetic.par"
     PR.write_par(par, path)
     yield path, par

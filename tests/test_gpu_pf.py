@@ -1,6 +1,7 @@
 """rafft_pf_batch on a real MI355X (`-m gpu`): Z and every P(i,j) against the sums over every structure of short sequences (evaluated
 by eval_kernel in one call, summed with fsum), against the tests' own mirror where enumeration cannot reach, invariance under the
-scale, a sequence an unscaled fp64 sum could not hold, same input - same bits across batch position, order and chunking, and errors
+scale, a sequence an unscaled fp64 sum could not hold, one whose scaled sums leave the fp64 range in either direction, other
+temperatures under a parameter file with enthalpies, same input - same bits across batch position, order and chunking, and errors
 that stay with their sequence.
 The bounds - 1e-8 kcal/mol on the ensemble energy, 1e-9 on a probability, 1e-9 relative on the MFE's share - are what fp64 sums of
 positive terms leave (a few thousand operations times 2^-53) with two orders of margin; they are not measured values."""
@@ -35,16 +36,19 @@ def sets(tmp_path_factory):
     builtin = LP.builtin_par()
     idx = LP.index_sensitive_par(builtin)
     idx.update(ml_closing=-700, ml_intern=-300)               # negative enough that multiloops hold most of Z at 16-20 nt
-    path = tmp_path_factory.mktemp("par") / "multiloops_win.par"
-    PR.write_par(idx, path, comment="index-sensitive, multiloops win")
-    return dict(builtin=builtin, multiloops_win=idx, path=path)
+    out = dict(builtin=builtin, multiloops_win=idx, synthetic=PR.synthetic_par(builtin), paths={})
+    d = tmp_path_factory.mktemp("par")
+    for name, comment in (("multiloops_win", "index-sensitive, multiloops win"), ("synthetic", "made-up enthalpies")):
+        out["paths"][name] = d / (name + ".par")
+        PR.write_par(out[name], out["paths"][name], comment=comment)
+    return out
 
 
 def install(sets, which):
     if which == "builtin":
         params.reset_params()
     else:
-        params.load_params(sets["path"])
+        params.load_params(sets["paths"][which])
 
 
 @pytest.fixture(autouse=True)
@@ -84,7 +88,7 @@ def exhaustive_sequences():
         for sp in LP.OWN_SPECIAL[name]:
             seqs.append("GG" + sp + "CC")
     seqs += ["GGGACACCCAGGACCACCC", "G" * 10 + "U" * 10, "GU" * 9, "GGGUUUGGGUUUCCC", "GCGCAAAGCGCAAAGCGC", "GGGAAACCCAGGGAAACCCA", "NGGGAAACCCN"]
-    return seqs + MULTILOOP_SEQS
+    return seqs + LP.N_SEQS + MULTILOOP_SEQS
 
 
 _ENUM = {}
@@ -101,7 +105,7 @@ def enumerated(seqs):
 def test_gpu_pf_equals_the_sums_over_every_structure(sets, which):
     install(sets, which)
     seqs = exhaustive_sequences()
-    assert 40 <= len(seqs) <= 55 and max(map(len, seqs)) == 20
+    assert 44 <= len(seqs) <= 59 and max(map(len, seqs)) == 20 and sum("N" in s for s in seqs) == 5
     rows = enumerated(seqs)
     flat_s = [s for s, rr in zip(seqs, rows) for _ in rr]
     flat_r = [r for rr in rows for r in rr]
@@ -206,7 +210,98 @@ def test_gpu_pf_holds_a_sequence_an_unscaled_sum_could_not():
     assert bits(rows, recs, probs, 1) == bits(*alone, 0)
 
 
-# ---- 6. same input, same bits
+def test_gpu_pf_reports_a_sequence_whose_scaled_sums_leave_the_fp64_range():
+    """a helix of 200 GC stacks between two ordinary sequences.  With a scale of practically 1 its sums overflow, with a scale far too
+    large they underflow to 0: in both calls it - and only it - gets RAFFT_ERR_CAPACITY, an all-dot row and zeros (mfe_dcal keeps the
+    MFE's energy, which the driver has before the sums are formed); with the default scale it is held"""
+    rng = np.random.default_rng(404)
+    big, left, right = "G" * 200 + "GAAA" + "C" * 200, rand(rng, 40), rand(rng, 25)
+    seqs = [left, big, right]
+    mfe = zuker.mfe_batch_raw([big])[1][0]
+    print(f"\n404 nt: MFE {mfe} dcal/mol")
+    assert mfe < -60000                                                            # exp(437.4 / kT) is the largest fp64 at 37 C
+    for sf in (1e-9, 3.0):
+        without = mccaskill.pf_batch_raw([left, right], scale_factor=sf)           # (a sequence's bits depend on the scale)
+        assert not any(x["status"] for x in without[1])
+        rows, recs, probs = mccaskill.pf_batch_raw(seqs, scale_factor=sf)
+        r = recs[1]
+        assert [x["status"] for x in recs] == [0, N.ERR_CAPACITY, 0], sf
+        assert N.lib().rafft_last_error().decode().startswith("sequence 1:")
+        assert rows[1] == "." * len(big) and r["energy"] == 0.0 and r["mfe_frequency"] == 0.0 and r["n_pairs"] == 0 and r["length"] == len(big)
+        assert r["mfe_dcal"] == mfe
+        assert probs[1].shape == (len(big), len(big)) and not probs[1].any()
+        assert [bits(rows, recs, probs, 0), bits(rows, recs, probs, 2)] == [bits(*without, 0), bits(*without, 1)]
+        rows2, recs2, none = mccaskill.pf_batch_raw(seqs, scale_factor=sf, probs=False)
+        assert none is None and rows2 == rows and recs2 == recs
+    without = mccaskill.pf_batch_raw([left, right])
+    rows, recs, probs = mccaskill.pf_batch_raw(seqs)
+    r, P = recs[1], probs[1]
+    assert r["status"] == N.OK and r["mfe_dcal"] == mfe and math.isfinite(r["energy"]) and r["energy"] <= mfe / 100.0
+    assert np.isfinite(P).all() and P.min() >= 0.0
+    per_base = P.sum(axis=0) + P.sum(axis=1)
+    print(f"default scale: ensemble energy {r['energy']:.4f} kcal/mol, {r['n_pairs']} centroid pairs, largest sum of P over the partners of a position: 1 + {per_base.max() - 1.0:.3g}")
+    assert per_base.max() <= 1.0 + 1e-9
+    assert [bits(rows, recs, probs, 0), bits(rows, recs, probs, 2)] == [bits(*without, 0), bits(*without, 1)]
+
+
+# ---- 6. other temperatures
+
+def exact_errors(seqs, recs, probs, temp):
+    """largest errors of the energy, of P and of the MFE's share against the exact sums over every structure of each sequence, under
+    the installed tables at `temp` (one eval_kernel call)"""
+    kt = PF.kt_of(temp)
+    rows = enumerated(seqs)
+    en, st = R.eval_structures([s for s, rr in zip(seqs, rows) for _ in rr], [r for rr in rows for r in rr], temp=temp)
+    assert not any(st)
+    worst_e = worst_p = worst_f = 0.0
+    at = 0
+    for k, rr in enumerate(rows):
+        e = en[at:at + len(rr)]
+        at += len(rr)
+        Z, P = PF.exact(rr, e, kt)
+        assert min(e) == recs[k]["mfe_dcal"]
+        worst_e = max(worst_e, abs(recs[k]["energy"] - (-kt * math.log(Z))))
+        worst_p = max(worst_p, float(np.abs(probs[k] - P).max()))
+        worst_f = max(worst_f, abs(recs[k]["mfe_frequency"] / (math.exp(-min(e) / (100.0 * kt)) / Z) - 1.0))
+    return worst_e, worst_p, worst_f
+
+
+_MIRROR_T = {}
+
+
+@pytest.mark.parametrize("temp", [25.0, 60.0])
+def test_gpu_pf_at_another_temperature(sets, temp):
+    """a parameter file with (made-up) enthalpies: kT and the tables are those of the call's temperature - against the exact sums
+    with eval_kernel's energies at that temperature and kt_of(temp), and against the mirror over tables rescaled by the tests' own
+    reader at 60-90 nt; the bounds are those of 37 C (their derivation does not involve kT); 37 C comes back afterwards"""
+    install(sets, "synthetic")
+    short, longer = exhaustive_sequences(), mirror_sequences()
+    at37 = mccaskill.pf_batch_raw(short + longer)
+    rows, recs, probs = mccaskill.pf_batch_raw(short, temp=temp)
+    assert not any(r["status"] for r in recs)
+    worst_e, worst_p, worst_f = exact_errors(short, recs, probs, temp)
+    print(f"\n{temp} C, every structure: largest error of the energy {worst_e:.3g} kcal/mol, of P {worst_p:.3g}, of the MFE share {worst_f:.3g} (relative)")
+    assert worst_e <= E_TOL and worst_p <= P_TOL and worst_f <= F_TOL
+    if temp not in _MIRROR_T:
+        m = PF.PfMirror(PR.tables_at(sets["synthetic"], temp), temp)
+        _MIRROR_T[temp] = [m.run(s) for s in longer]
+    kt = PF.kt_of(temp)
+    rows, recs, probs = mccaskill.pf_batch_raw(longer, temp=temp)
+    assert not any(r["status"] for r in recs)
+    worst_e = max(abs(recs[k]["energy"] - (-kt * math.log(z))) for k, (z, _) in enumerate(_MIRROR_T[temp]))
+    worst_p = max(float(np.abs(probs[k] - p).max()) for k, (_, p) in enumerate(_MIRROR_T[temp]))
+    print(f"{temp} C, mirror at 60-90 nt: largest error of the energy {worst_e:.3g} kcal/mol, of P {worst_p:.3g}")
+    assert worst_e <= E_TOL and worst_p <= P_TOL
+    # kT differs by 4 % and 7 % from 310.15 K's and every table is rescaled: ensemble energies of -5 to -30 kcal/mol move by far more
+    # than the bound - a kT or a table left at 37 C cannot pass
+    shift = [abs(recs[k]["energy"] - at37[1][len(short) + k]["energy"]) for k in range(len(longer))]
+    print(f"{temp} C: the ensemble energies differ from those at 37 C by {min(shift):.3g} to {max(shift):.3g} kcal/mol")
+    assert min(shift) > 1e5 * E_TOL
+    again = mccaskill.pf_batch_raw(short + longer)
+    assert [bits(*again, k) for k in range(len(short + longer))] == [bits(*at37, k) for k in range(len(short + longer))]
+
+
+# ---- 7. same input, same bits
 
 def test_gpu_pf_same_input_same_bits():
     rng = np.random.default_rng(6)
@@ -224,7 +319,7 @@ def test_gpu_pf_same_input_same_bits():
         assert [bits(*got, k) for k in range(len(seqs))] == [want[s] for s in seqs]
 
 
-# ---- 7. sanity at 100-200 nt
+# ---- 8. sanity at 100-200 nt
 
 def test_gpu_pf_sanity_at_100_to_200_nt():
     rng = np.random.default_rng(7)
@@ -250,7 +345,7 @@ def test_gpu_pf_sanity_at_100_to_200_nt():
     assert not any(st)
 
 
-# ---- 8. errors stay with their sequence
+# ---- 9. errors stay with their sequence
 
 def test_gpu_pf_errors_stay_with_their_sequence():
     good = ["GGGGAAAACCCC", "GGGAAACCCAGGGAAACCC", "GCGCUUCGGCGC", "ACGUACGUACGUACGUAGC"]
@@ -291,7 +386,7 @@ def test_gpu_pf_errors_stay_with_their_sequence():
         assert e.value.code == N.ERR_TEMP
 
 
-# ---- 9. the command line as a process, with the real scorer
+# ---- 10. the command line as a process, with the real scorer
 
 def test_gpu_cli_pf_scores_table(tmp_path):
     from rafft_amd import cli, scoring

@@ -1,6 +1,7 @@
 """The host side of the MFE folds (rafft_mfe_batch, rafft_amd.mfe_batch, `rafft --mfe`) and the tests' own mirror of the
-recurrences: the mirror equals the minimum of the oracle's energy over every structure of a short sequence, the record's layout,
-the option surface, and the errors that need no device.  No GPU."""
+recurrences: the mirror equals the minimum of the oracle's energy over every structure of a short sequence, its traceback returns
+rows of the co-optimal set - another one in the reversed candidate order wherever the tables tie -, the record's layout, the option
+surface, and the errors that need no device.  No GPU."""
 import ctypes
 import os
 import re
@@ -30,7 +31,7 @@ def short_sequences():
     seqs += ["".join(rng.choice(list("GC"), n)) for n in (9, 12, 14)]                       # many pairs, many structures
     seqs += ["GGGGAAAACCCC", "GACAC", "GGACACC", "GGACCACC", "GGACACCACC", "GUGUGUGUGUGUGU", "GGGUUUGGGUUUCCC", "NGGGAAACCCN",
              "GCGCAAAGCGCAAAGC"]
-    return seqs
+    return seqs + LP.N_SEQS
 
 
 def test_enumeration_counts():
@@ -63,6 +64,60 @@ def test_mirror_is_the_minimum_of_the_oracle_over_every_structure(which):
         n_multi += "(" in best and any(len(LP.branches_of(best, [k])) > 1 for k in range(len(s)) if best[k] == "." and 0 < k < len(s) - 1)
     if which == "multiloops_win":
         assert n_multi > 0                                   # the M / M1 recurrences decide some of these minima
+
+
+def tie_tables(which):
+    par = LP.builtin_par()
+    if which != "builtin":
+        par = LP.tie_par(par, LP.TIE_ML[int(which[-1])])
+        oracle.set_tables(PR.tables_at(par, 37.0))
+    return PR.tables_at(par, 37.0)
+
+
+@pytest.mark.parametrize("which", ["builtin", "tie0", "tie1"])
+def test_fold_returns_rows_of_the_cooptimal_set_and_the_tie_tables_tie(which):
+    """both candidate orders trace back to a structure of minimum energy; under the flat tables most sequences have several such
+    structures and the two orders return different ones - so a device row equal to fold(..., "first") pins the order"""
+    mirror = MF.Mirror(tie_tables(which))
+    seqs = LP.tie_short_sequences()
+    assert len(seqs) == 20 and max(map(len, seqs)) == 20 and sum("N" in s for s in seqs) == 4
+    n_cooptimal = n_differ = 0
+    for s in seqs:
+        rows = MF.enumerate_structures(s)
+        en = [oracle.eval_structure(s, r) for r in rows]
+        best = {r for r, e in zip(rows, en) if e == min(en)}
+        first, last = mirror.fold(s, "first"), mirror.fold(s, "last")
+        assert first[0] == last[0] == min(en) == mirror.mfe(s), (which, s)
+        assert first[1] in best and last[1] in best, (which, s)
+        n_cooptimal += len(best) >= 2
+        n_differ += first[1] != last[1]
+    print(f"\n{which}: {n_cooptimal} of {len(seqs)} sequences with two or more co-optimal structures, first and last rows differ on {n_differ}")
+    if which != "builtin":
+        assert n_cooptimal >= 6 and n_differ >= 6
+
+
+def test_long_tie_list_reaches_the_later_rounds_of_every_ballot():
+    """the traceback takes 64 candidates per round; on the long tie list the mirror takes an exterior stem at i >= 64, an M split and
+    a C split 64 and more candidates into their ranges, and an interior loop with candidate number >= 64 - under the variant without
+    multiloop terms; every row evaluates to the reported energy, and the two orders give different rows on most sequences under
+    both variants"""
+    seqs = LP.tie_long_sequences()
+    assert 40 <= min(map(len, seqs)) and max(map(len, seqs)) <= 105
+    reached = {}
+    for which in ("tie0", "tie1"):
+        mirror = MF.Mirror(tie_tables(which))
+        off = dict(F=-1, M=-1, C=-1, I=-1)
+        n_differ = 0
+        for s in seqs:
+            first = mirror.fold(s, "first")
+            off = {k: max(v, mirror.offsets[k]) for k, v in off.items()}
+            last = mirror.fold(s, "last")
+            assert oracle.eval_structure(s, first[1]) == first[0] == last[0] == oracle.eval_structure(s, last[1]), (which, s)
+            n_differ += first[1] != last[1]
+        print(f"\n{which}: largest candidate offsets taken in the documented order {off}; first and last rows differ on {n_differ} of {len(seqs)}")
+        assert n_differ >= 6
+        reached[which] = off
+    assert all(reached["tie0"][k] >= 64 for k in "FMCI"), reached
 
 
 def test_mfe_record_matches_the_header():

@@ -37,7 +37,7 @@ def short_sequences():
     seqs += ["".join(rng.choice(list("ACGU"), n)) for n in (5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20)]
     seqs += ["".join(rng.choice(list("GC"), n)) for n in (9, 12, 14)]
     seqs += ["GGGGAAAACCCC", "GACAC", "GGACACC", "GUGUGUGUGUGUGU", "GGGUUUGGGUUUCCC", "NGGGAAACCCN", "GCGCAAAGCGCAAAGC", "GGGAAACCCAGGGAAACCCA"]
-    return seqs + MULTILOOP_SEQS
+    return seqs + LP.N_SEQS + MULTILOOP_SEQS
 
 
 def table_set(which):
