@@ -61,11 +61,59 @@ __device__ inline void seen_insert(uint64_t *tab, uint32_t cap, uint64_t h1, uin
 }
 
 
-// move every key of a sequence's `seen` set into a bigger, zeroed table.  (round 5: four slots per thread read together and their
+// ---- the same set with its occupancy kept in LDS: bit s of `bm` set <=> slot s of the table holds a key.
+// A sequence's table is only ever touched by that sequence's workgroup, one beam step at a time, so which slots are taken need not be
+// asked of HBM: the workgroup loads the table's bitmap (cap / 8 bytes) when it starts and stores it when its inserts are done.  A
+// lookup whose home slot is free - the usual answer, the tables are at most half full - makes no HBM access at all, an insert claims
+// its slot with an LDS atomic and writes the entry with one plain 16-byte store, and a table need not be zeroed: a slot is read only
+// where its bit is set.
+__device__ __forceinline__ bool bm_test(const uint32_t *bm, uint32_t s) { return (bm[s >> 5] >> (s & 31)) & 1u; }
+// (the slots of a run of set bits are loaded together, as in seen_lookup; the run's end is known before anything is loaded)
+__device__ inline bool seen_lookup_bm(const uint64_t *tab, const uint32_t *bm, uint32_t cap, uint64_t h1, uint64_t h2, uint32_t &free_sl)
+{
+    const uint32_t mask = cap - 1;
+    uint32_t sl = (uint32_t)h1 & mask;
+    const ulonglong2 *t2 = (const ulonglong2 *)tab;
+    for (;;) {
+        if (!bm_test(bm, sl)) { free_sl = sl; return false; }
+        const uint32_t s1 = (sl + 1) & mask, s2 = (sl + 2) & mask, s3 = (sl + 3) & mask;
+        const bool b1 = bm_test(bm, s1), b2 = b1 && bm_test(bm, s2), b3 = b2 && bm_test(bm, s3);
+        ulonglong2 e0 = t2[sl], e1 = make_ulonglong2(0ULL, 0ULL), e2 = e1, e3 = e1;
+        if (b1) e1 = t2[s1];
+        if (b2) e2 = t2[s2];
+        if (b3) e3 = t2[s3];
+        pin(e0); pin(e1); pin(e2); pin(e3);
+        if (e0.x == h1 && e0.y == h2) return true;
+        if (!b1) { free_sl = s1; return false; }
+        if (e1.x == h1 && e1.y == h2) return true;
+        if (!b2) { free_sl = s2; return false; }
+        if (e2.x == h1 && e2.y == h2) return true;
+        if (!b3) { free_sl = s3; return false; }
+        if (e3.x == h1 && e3.y == h2) return true;
+        sl = (sl + 4) & mask;
+    }
+}
+// insert a key that is not in the set, starting at a slot at or before its first free one (seen_lookup_bm's free_sl, or its home slot in
+// a table being filled by a rehash).  A slot found taken is never compared: the keys inserted side by side are distinct (wk_tab, the
+// keys of a table), and the slot of a concurrent insert may not be written yet - the table is not zeroed, what it holds until then is
+// whatever the arena held before, possibly this very key from an earlier wave.
+__device__ inline void seen_insert_at_bm(uint64_t *tab, uint32_t *bm, uint32_t cap, uint64_t h1, uint64_t h2, uint32_t sl)
+{
+    const uint32_t mask = cap - 1;
+    for (;;) {
+        const uint32_t bit = 1u << (sl & 31);
+        if (!(atomicOr(&bm[sl >> 5], bit) & bit)) { ((ulonglong2 *)tab)[sl] = make_ulonglong2((unsigned long long)h1, (unsigned long long)h2); return; }
+        sl = (sl + 1) & mask;
+    }
+}
+
+// move every key of a sequence's `seen` set into a bigger table.  (round 5: four slots per thread read together and their
 // compare-and-swaps issued together - one slot at a time was a chain of two or three dependent round trips per slot, 32 slots per
 // thread for the first growth: ~60 us of a workgroup's ~250)
+// `sbm`: the old table's bitmap - it is read only where a bit is set (null: an empty slot holds zero); `nbm`: the new table's bitmap,
+// zeroed by the caller and filled here (null: the new table itself was zeroed, slots are claimed by compare-and-swap)
 template <int NT>
-__device__ inline void seen_rehash(const uint64_t *stab, uint32_t scap, uint64_t *ntab, uint32_t ncap, int tid)
+__device__ inline void seen_rehash(const uint64_t *stab, uint32_t scap, const uint32_t *sbm, uint64_t *ntab, uint32_t ncap, uint32_t *nbm, int tid)
 {
     const ulonglong2 *src = (const ulonglong2 *)stab;
     const uint32_t mask = ncap - 1;
@@ -73,7 +121,15 @@ __device__ inline void seen_rehash(const uint64_t *stab, uint32_t scap, uint64_t
         ulonglong2 e[4];
         unsigned long long old[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) { const uint32_t i = base + (uint32_t)u * NT + (uint32_t)tid; e[u] = i < scap ? src[i] : make_ulonglong2(0ULL, 0ULL); }
+        for (int u = 0; u < 4; u++) {
+            const uint32_t i = base + (uint32_t)u * NT + (uint32_t)tid;
+            e[u] = i < scap && (!sbm || bm_test(sbm, i)) ? src[i] : make_ulonglong2(0ULL, 0ULL);
+        }
+        if (nbm) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) if (e[u].x) seen_insert_at_bm(ntab, nbm, ncap, e[u].x, e[u].y, (uint32_t)e[u].x & mask);
+            continue;
+        }
 #pragma unroll
         for (int u = 0; u < 4; u++) { old[u] = 1; if (e[u].x) old[u] = atomicCAS((unsigned long long *)&ntab[2 * (uint64_t)((uint32_t)e[u].x & mask)], 0ULL, (unsigned long long)e[u].x); }
 #pragma unroll
@@ -83,6 +139,49 @@ __device__ inline void seen_rehash(const uint64_t *stab, uint32_t scap, uint64_t
                 else seen_insert(ntab, ncap, e[u].x, e[u].y);        // home slot taken: the probing insert
             }
     }
+}
+
+// The set of sequence `sq` moves into a table of `ncap` slots from the arena (workgroup-uniform call).  The new table is in bitmap
+// mode when its bitmap fits the launch's budget `bm_max` (bytes): then it is not zeroed, its bitmap is built in `bm` - the old one,
+// if there was one, is parked in `obm` (ncap / 16 bytes at the most) meanwhile.  Otherwise the table is zeroed here (the arena is
+// not) and keeps the compare-and-swap protocol from now on.  False: the arena is full (OVF_SEEN is set).
+template <int NT>
+__device__ inline bool seen_grow(const Dev &d, int sq, uint32_t ncap, uint64_t *&stab, uint32_t &scap, bool &bmode, uint32_t *bm, uint32_t *obm,
+                                 uint32_t bm_max, int *sh, int tid)
+{
+    if (tid == 0) {
+        unsigned long long o = atomicAdd(&d.c->seen_top, (unsigned long long)ncap);
+        // (a table's bitmap starts at bit `o` of the bitmap arena: whole words, since every table is a power of two >= 2048 slots)
+        if (o + ncap > d.seen_cap_total || (o & 31)) { atomicOr(&d.c->overflow, OVF_SEEN); *(unsigned long long *)&sh[8] = ~0ULL; }
+        else *(unsigned long long *)&sh[8] = o;
+    }
+    __syncthreads();
+    const unsigned long long o = *(unsigned long long *)&sh[8];
+    __syncthreads();
+    if (o == ~0ULL) return false;
+    uint64_t *ntab = d.seen + 2 * o;
+    // (a rare path inside the product walk's loop: the per-thread addresses of the bitmap loops below are formed here, from a copy of
+    //  the thread id that the compiler cannot see through - hoisted in front of the walk's loop they would take registers of the walk,
+    //  and the 256-thread kernel has none to spare)
+    uint32_t t = (uint32_t)tid;
+    asm volatile("" : "+v"(t));
+    const bool nmode = ncap / 8 <= bm_max;
+    const uint32_t *sbm = bmode ? bm : nullptr;
+    if (bmode && nmode) {
+        for (uint32_t i = t; i < scap / 32; i += NT) obm[i] = bm[i];
+        sbm = obm;
+        __syncthreads();
+    }
+    if (nmode) for (uint32_t i = t; i < ncap / 32; i += NT) bm[i] = 0;
+    else for (uint32_t i = tid; i < ncap; i += NT) ((ulonglong2 *)ntab)[i] = make_ulonglong2(0ULL, 0ULL);
+    __syncthreads();
+    seen_rehash<NT>(stab, scap, sbm, ntab, ncap, nmode ? bm : nullptr, tid);
+    __syncthreads();
+    // (stored at once: the step may accept nothing more, and nobody else stores a bitmap that no insert of the walk changed)
+    if (nmode) { uint32_t *gbm = d.seen_bm + o / 32; for (uint32_t i = t; i < ncap / 32; i += NT) gbm[i] = bm[i]; }
+    stab = ntab; scap = ncap; bmode = nmode;
+    if (tid == 0) { d.seen_off[sq] = o; d.seen_cap[sq] = ncap; d.seen_mode[sq] = nmode ? 1u : 0u; }
+    return true;
 }
 
 struct ParentInfo {         // filled by the parallel prepass, one entry per beam member
@@ -102,13 +201,15 @@ __device__ __forceinline__ unsigned long long sat_mul(unsigned long long a, unsi
     return (a > lim / b) ? lim : a * b;
 }
 
-// LDS: sort keys (dynamic) + product description + per-parent prepass records
+// LDS: sort keys (dynamic) + product description + per-parent prepass records.  `bm_max`: bytes of LDS for the bitmap of the sequence's
+// `seen` table, the launch's budget - a table whose bitmap does not fit keeps the compare-and-swap protocol on a zeroed table.
 template <int BS_NT>
-__global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(Dev d, int sort_cap)
+__global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(Dev d, int sort_cap, int bm_max)
 {
     extern __shared__ __align__(16) unsigned char lds[];
-    // region 0 is time-shared: scratch of the product walk (per-thread keys + dedupe table), then the sort keys
-    const size_t r0 = max((size_t)8 * (size_t)sort_cap, (size_t)24 * BS_NT);
+    // region 0 is time-shared: scratch of the product walk (per-thread keys + dedupe table) and behind it the bitmap of the `seen` table
+    // (stored back when the walk is over), then the sort keys
+    const size_t r0 = max((size_t)8 * (size_t)sort_cap, (size_t)24 * BS_NT + (size_t)bm_max);
     unsigned long long *skey = (unsigned long long *)lds;                       // [sort_cap]
     unsigned long long *wk_h1 = (unsigned long long *)lds;                      // [BS_NT] keys of this chunk's combos
     unsigned long long *wk_h2 = wk_h1 + BS_NT;                                  // [BS_NT]
@@ -118,7 +219,10 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
     ParentInfo *pinfo = (ParentInfo *)(rl_cnt + RL_CAP);                        // [B]
     unsigned long long *ppre = (unsigned long long *)(pinfo + d.B);             // [B + 1] flat positions of the products
     int *oldbeam = (int *)(ppre + d.B + 1);                                     // [B]
-    int *sh = oldbeam + ((d.B + 3) & ~3);                                       // scratch [32]
+    int *sh = oldbeam + ((d.B + 3) & ~3);                                       // scratch [32], then the prepass's pnode0 [B]
+    // (at a fixed address: the bitmap's per-thread addresses cost the product walk's loop no register)
+    uint32_t *bm = (uint32_t *)(lds + 24 * BS_NT);                              // [bm_max / 4] occupancy of the `seen` table
+    uint32_t *obm = (uint32_t *)lds;                                            // ... of the old table while a set grows (in wk_h1 / wk_h2)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int sq = blockIdx.x;
     // snapshot of the region allocators: whatever materialize adds after this kernel is "new"
@@ -310,10 +414,24 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
         }
         if (lane == 0) ppre[0] = 0;
     }
-    for (int i = tid; i < 2 * BS_NT; i += BS_NT) wk_tab[i] = 0;
-    __syncthreads();
+    // the `seen` table of this sequence: in bitmap mode its occupancy bitmap comes into LDS (a table in compare-and-swap mode was
+    // zeroed by the host, or by seen_grow when it was handed out)
     uint64_t *stab = d.seen + 2 * d.seen_off[sq];
     uint32_t scap = d.seen_cap[sq], scnt = d.seen_cnt[sq];
+    bool bmode = d.seen_mode[sq] != 0;
+    if (bmode && scap / 8 > (uint32_t)bm_max) {       // (never: the host hands a launch no table in bitmap mode beyond its budget)
+        if (tid == 0) atomicOr(&d.c->overflow, OVF_SEEN);
+        d.done[sq] = 1;
+        return;
+    }
+    if (bmode) {
+        const uint32_t *gbm = d.seen_bm + (size_t)(stab - d.seen) / 64;
+#pragma unroll 1
+        for (uint32_t i = tid; i < scap / 32; i += BS_NT) bm[i] = gbm[i];
+    }
+    bool seen_full = false;        // the arena had no bigger table left (OVF_SEEN): the walk stops, the sequence leaves once the bitmap is stored
+    for (int i = tid; i < 2 * BS_NT; i += BS_NT) wk_tab[i] = 0;
+    __syncthreads();
     const size_t chb = (size_t)sq * d.ch_cap;
     int nb_branch = 0, nchild = 0;
     int single_from = nbeam;
@@ -325,25 +443,10 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
     while (single_from == nbeam && W < Ptot) {
         const unsigned long long left = Ptot - W;
         const int chunk = left < (unsigned long long)BS_NT ? (int)left : BS_NT;
-        if ((unsigned long long)(scnt + chunk) * 2 > scap) {   // grow the seen set (rehash into a zeroed region)
+        if ((unsigned long long)(scnt + chunk) * 2 > scap) {   // grow the seen set (rehash into a bigger table)
             uint32_t ncap = scap;
             while ((unsigned long long)(scnt + BS_NT) * 2 > ncap) ncap <<= 1;
-            if (tid == 0) {
-                unsigned long long o = atomicAdd(&d.c->seen_top, (unsigned long long)ncap);
-                if (o + ncap > d.seen_cap_total) { atomicOr(&d.c->overflow, OVF_SEEN); *(unsigned long long *)&sh[8] = ~0ULL; }
-                else *(unsigned long long *)&sh[8] = o;
-            }
-            __syncthreads();
-            unsigned long long o = *(unsigned long long *)&sh[8];
-            __syncthreads();
-            if (o == ~0ULL) { d.done[sq] = 1; return; }
-            uint64_t *ntab = d.seen + 2 * o;
-            for (uint32_t i = tid; i < ncap; i += BS_NT) ((ulonglong2 *)ntab)[i] = make_ulonglong2(0ULL, 0ULL);   // arena is not pre-zeroed
-            __syncthreads();
-            seen_rehash<BS_NT>(stab, scap, ntab, ncap, tid);
-            __syncthreads();
-            stab = ntab; scap = ncap;
-            if (tid == 0) { d.seen_off[sq] = o; d.seen_cap[sq] = ncap; }
+            if (!seen_grow<BS_NT>(d, sq, ncap, stab, scap, bmode, bm, obm, (uint32_t)bm_max, sh, tid)) { seen_full = true; break; }
         }
         const int need = d.max_branch - nb_branch;      // > 0
         int b = 0, sidb = 0, cd = 0, slot = -1;
@@ -413,7 +516,7 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
             }
             h1 = a1 ? a1 : 1; h2 = a2 ? a2 : 1; cd = ad;
             wk_h1[tid] = h1; wk_h2[tid] = h2;
-            cand_new = !seen_lookup(stab, scap, h1, h2, free_sl);
+            cand_new = bmode ? !seen_lookup_bm(stab, bm, scap, h1, h2, free_sl) : !seen_lookup(stab, scap, h1, h2, free_sl);
         }
         // the same structure can come from several parents of this chunk: its first position wins (`seen` order)
         if (cand_new) {
@@ -444,7 +547,8 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
                 d.ch_h[2 * (chb + ci2)] = h1;
                 d.ch_h[2 * (chb + ci2) + 1] = h2;
             } else atomicOr(&d.c->overflow, OVF_SORT);
-            seen_insert_at(stab, scap, h1, h2, free_sl);
+            if (bmode) seen_insert_at_bm(stab, bm, scap, h1, h2, free_sl);
+            else seen_insert_at(stab, scap, h1, h2, free_sl);
         }
         if (hit) {
             // the reference stops walking after the combo that brings nb_branch to max_branch
@@ -466,31 +570,16 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
         for (int i = tid; i < 2 * BS_NT; i += BS_NT) wk_tab[i] = 0;
         __syncthreads();
     }
-    if (single_from < nbeam) {
+    if (single_from < nbeam && !seen_full) {
         // ---- parents in "one combo then break" mode: combo 0 of each (from the prepass), accepted in
         // beam order if its structure is new; a parent whose cursor already moved replays a known combo
         const int nrest = nbeam - single_from;
         if ((unsigned long long)(scnt + nrest) * 2 > scap) {
             uint32_t ncap = scap;
             while ((unsigned long long)(scnt + nrest + BS_NT) * 2 > ncap) ncap <<= 1;
-            if (tid == 0) {
-                unsigned long long o = atomicAdd(&d.c->seen_top, (unsigned long long)ncap);
-                if (o + ncap > d.seen_cap_total) { atomicOr(&d.c->overflow, OVF_SEEN); *(unsigned long long *)&sh[8] = ~0ULL; }
-                else *(unsigned long long *)&sh[8] = o;
-            }
-            __syncthreads();
-            unsigned long long o = *(unsigned long long *)&sh[8];
-            __syncthreads();
-            if (o == ~0ULL) { d.done[sq] = 1; return; }
-            uint64_t *ntab = d.seen + 2 * o;
-            for (uint32_t i = tid; i < ncap; i += BS_NT) ((ulonglong2 *)ntab)[i] = make_ulonglong2(0ULL, 0ULL);   // arena is not pre-zeroed
-            __syncthreads();
-            seen_rehash<BS_NT>(stab, scap, ntab, ncap, tid);
-            __syncthreads();
-            stab = ntab; scap = ncap;
-            if (tid == 0) { d.seen_off[sq] = o; d.seen_cap[sq] = ncap; }
+            if (!seen_grow<BS_NT>(d, sq, ncap, stab, scap, bmode, bm, obm, (uint32_t)bm_max, sh, tid)) seen_full = true;
         }
-        for (int base = single_from; base < nbeam; base += BS_NT) {
+        for (int base = single_from; base < nbeam && !seen_full; base += BS_NT) {
             const int b = base + tid;
             int isnew = 0;
             uint32_t free_sl = 0;
@@ -499,7 +588,7 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
                 h1 = pinfo[b].h1; h2 = pinfo[b].h2;
                 if (h1 == 0) h1 = 1;
                 if (h2 == 0) h2 = 1;
-                isnew = seen_lookup(stab, scap, h1, h2, free_sl) ? 0 : 1;
+                isnew = (bmode ? seen_lookup_bm(stab, bm, scap, h1, h2, free_sl) : seen_lookup(stab, scap, h1, h2, free_sl)) ? 0 : 1;
                 // an earlier parent of this phase producing the same structure wins (`seen` order)
                 for (int e = single_from; isnew && e < b; e++)
                     if (pinfo[e].flag == 0) {
@@ -519,13 +608,26 @@ __global__ __launch_bounds__(BS_NT, BS_NT == 256 ? 5 : 1) void beam_step_kernel(
                     d.ch_h[2 * (chb + ci2)] = h1;
                     d.ch_h[2 * (chb + ci2) + 1] = h2;
                 } else atomicOr(&d.c->overflow, OVF_SORT);
-                seen_insert_at(stab, scap, h1, h2, free_sl);
+                if (bmode) seen_insert_at_bm(stab, bm, scap, h1, h2, free_sl);
+                else seen_insert_at(stab, scap, h1, h2, free_sl);
             }
             if (b < nbeam && pinfo[b].flag == 0) { d.st[oldbeam[b]].cursor = 1; d.st[oldbeam[b]].total = pinfo[b].total; }
             nchild += tot; nb_branch += tot; scnt += tot;
             __syncthreads();
         }
     }
+    // (every insert of this step lies before a barrier: the pass's own, or the one that ends a round of the loop above)
+    // The bitmap goes back to HBM, before the sort keys take its place - and before any return: the step's entries are in the table,
+    // their bits must not be lost.  (A table that seen_grow filled is stored there.)
+    if (bmode) {
+        if (nchild > 0) {
+            uint32_t *gbm = d.seen_bm + (size_t)(stab - d.seen) / 64;
+#pragma unroll 1
+            for (uint32_t i = tid; i < scap / 32; i += BS_NT) gbm[i] = bm[i];
+        }
+        __syncthreads();           // (the sort keys below overwrite the bitmap's LDS)
+    }
+    if (seen_full) { d.done[sq] = 1; return; }
     if (tid == 0) { d.seen_cnt[sq] = scnt; atomicAdd(&d.c->xstat[1][sq & (NSHARD - 1)].children, (unsigned long long)nchild); }
     if (nchild > d.ch_cap) nchild = d.ch_cap;
 

@@ -56,8 +56,10 @@ struct Config {
     int test_ovf_at = -1;      // RAFFT_TEST_OVF_AT     H  pretend an arena overflowed at this step of the first attempt
     int seen_fixed = 0;        // RAFFT_SEEN_FIXED    H  1: every `seen` set starts at SEEN0 slots instead of a table sized from the length (the growth path)
     int test_cand_limit = 0;   // RAFFT_TEST_CAND_LIMIT H  lower the 31-bit limit of the candidate table (split path on small jobs)
+    int seen_bm_max = -1;      // RAFFT_SEEN_BM_MAX   H  bytes of a `seen` table's occupancy bitmap that the beam step keeps in LDS (-1: 4 KiB / 32 KiB for the 256- / 1024-thread kernel, 0: never a bitmap)
+    int pad_ = 0;              // (keeps the number of ints even)
 };
-static_assert(sizeof(Config) == 8 * 6 + 4 * 30, "Config: 8-byte fields first, an even number of ints - no padding (same_config compares bytes)");
+static_assert(sizeof(Config) == 8 * 6 + 4 * 32, "Config: 8-byte fields first, an even number of ints - no padding (same_config compares bytes)");
 
 inline Config read_config()
 {
@@ -80,6 +82,7 @@ inline Config read_config()
 #ifndef RAFFT_NO_TEST_HOOKS
     I("RAFFT_MAT_TILE", c.mat_tile); I("RAFFT_RL_CAP", c.rl_cap); F("RAFFT_EST", c.est); I("RAFFT_SEEN_FIXED", c.seen_fixed);
     I("RAFFT_TEST_CAND_LIMIT", c.test_cand_limit); I("RAFFT_TEST_HARD_FAIL", c.test_hard_fail); I("RAFFT_TEST_MAX_PROD", c.test_max_prod); I("RAFFT_TEST_OVF_AT", c.test_ovf_at);
+    I("RAFFT_SEEN_BM_MAX", c.seen_bm_max);
 #endif
     return c;
 }

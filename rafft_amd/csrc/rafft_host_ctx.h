@@ -31,7 +31,7 @@ struct PinBuf { void *p = nullptr; size_t cap = 0; };
 // classes), not from the wave's plan.
 #define WS_BUFFERS(X)                                                                                                           \
     X(codes, 1) X(seq_off, 1) X(seq_len, 1) X(beam, 1) X(beam_n, 1) X(done, 1) X(nsteps, 1) X(ch_parent, 1) X(ch_combo, 1)      \
-    X(ch_dcal, 1) X(ch_h, 1) X(seen, 1) X(seen_off, 1) X(seen_cap, 1) X(seen_cnt, 1) X(st, 1) X(prod, 1) X(nd, 1) X(nlist, 1)   \
+    X(ch_dcal, 1) X(ch_h, 1) X(seen, 1) X(seen_off, 1) X(seen_cap, 1) X(seen_cnt, 1) X(seen_bm, 1) X(seen_mode, 1) X(st, 1) X(prod, 1) X(nd, 1) X(nlist, 1)   \
     X(nd_slot, 1) X(cslot, 1) X(pos, 1) X(br, 1) X(sp, 1) X(cand, 1) X(looptab, 1) X(trec, 1) X(tsid, 1) X(work0, 1)            \
     X(work1, 1) X(work2, 1) X(work3, 1) X(work4, 1) X(work5, 1) X(mat, 1) X(counters, 1) X(row_off, 1) X(out_db, 1)             \
     X(out_dcal, 1) X(row_off2, 1) X(out_db2, 1) X(out_dcal2, 1) X(dbg, 0) X(big, 0)

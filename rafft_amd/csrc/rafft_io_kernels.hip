@@ -36,7 +36,9 @@ __global__ void init_roots_kernel(Dev d)
         d.nd[sq].ncand = -1; d.nd[sq].cand = 0;
         d.beam[(size_t)sq * d.B] = sq; d.beam_n[sq] = 1; d.nsteps[sq] = 0;
         d.done[sq] = L > 0 ? 0 : 1;
-        d.seen_cnt[sq] = 0;       // (seen_off / seen_cap: uploaded by the host - tables sized from the lengths, zeroed by its memset)
+        d.seen_cnt[sq] = 0;       // (seen_off / seen_cap: uploaded by the host - tables sized from the lengths)
+        // bitmap mode (the host zeroed the bitmap) or, beyond the first launch's bitmap budget, a table that the host zeroed
+        d.seen_mode[sq] = d.seen_cap[sq] / 8 <= d.seen_bm0 ? 1u : 0u;
         if (L > 0) {
             int cls = node_class(L, L, 0, 0, d.cls1_P, d.cls1_br);
             unsigned int w = atomicAdd(&d.c->n_work[cls].v, 1u);

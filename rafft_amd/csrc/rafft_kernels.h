@@ -24,7 +24,8 @@
 //   pos arena           uint16 root positions of every node, ascending
 //   br arena            uint32 (p | q<<16) outermost pair of every branch, ascending
 //   cand arena          32-byte stem candidates, dE-sorted per canonical node
-//   seen arena          per-sequence open-addressing sets of 128-bit structure hashes
+//   seen arena          per-sequence open-addressing sets of 128-bit structure hashes; which slots are taken: one bit per slot
+//                       (seen_bm) for the tables whose bitmap fits beam_step_kernel's LDS, a zero first word otherwise
 //   children[S][cap]    per-step accepted children (parent, combo, dcal, hash)
 // Names follow the reference: Node/Structure (rafft/utils.py:24-39), beam =
 // glob_tree, trajectory = glob_traj (rafft/rafft.py:156-216).
@@ -54,6 +55,7 @@ static_assert(sizeof(Cand) == 32, "Cand must be 32 bytes");
 #ifndef SEEN0
 #define SEEN0 8192      // initial slots of a sequence's `seen` set (grows x2 by rehash)
 #endif
+static_assert(SEEN0 >= 2048 && (SEEN0 & (SEEN0 - 1)) == 0, "seen tables are powers of two >= 2048 slots (their bitmaps start on whole words)");
 #define NCLS 6          // expand size classes: 0-3 the general kernel (NGEN), 4-5 the small-region kernel (teams of 16 / 32 lanes)
 #define NGEN 4
 struct ShardCtr { unsigned long long v; unsigned long long pad[7]; };   // one 64-byte line each
@@ -144,6 +146,11 @@ struct Dev {
     // seen sets
     uint64_t *seen; uint64_t seen_cap_total;
     uint64_t *seen_off; uint32_t *seen_cap, *seen_cnt;
+    uint32_t *seen_bm;           // occupancy bitmaps of the tables, one bit per slot of the seen arena: a table's bitmap starts at bit seen_off[sq]
+                                 // (whole words: tables are powers of two >= 2048 slots, back to back).  Valid for tables in bitmap mode:
+    uint32_t *seen_mode;         // per sequence, 1: bit s set <=> slot s holds a key, the table is never zeroed (beam_step_kernel keeps the bitmap in
+                                 // LDS); 0: an empty slot holds zero, slots are claimed by compare-and-swap
+    uint32_t seen_bm0;           // initial tables of up to 8 x this many slots start in bitmap mode (bytes of bitmap: the first launch's LDS budget)
     // structures
     uint32_t st_cap;
     StRec *st;                   // one 128-byte record per structure (two cache lines)

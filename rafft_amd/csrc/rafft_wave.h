@@ -90,12 +90,12 @@ struct Wave {
     Batch &bt;                                      // the first of them: carries the wave's timing spans and statistics
     std::vector<Span> &spans;
     const SeamIn *seam;
-    size_t S = 0, sumL = 0, B = 0, bs_lds[2] = {0, 0}, mat_lds = RAFFT_MAX_LEN, out_row_lds = RAFFT_MAX_LEN;
+    size_t S = 0, sumL = 0, B = 0, bs_lds[2] = {0, 0}, bs_bm[2] = {0, 0} /* bitmap budget of the 256- / 1024-thread beam step (bytes) */, mat_lds = RAFFT_MAX_LEN, out_row_lds = RAFFT_MAX_LEN;
     double reserve = 1.0;         // buffers are allocated for a wave this many times bigger (merged batches to come)
     bool longseq = false;         // a sequence longer than LDS_SEQ: its loops' bases are read from HBM, regions beyond 4096 positions exist
     std::vector<int> off, len;
     std::vector<uint32_t> seen_cap0;      // initial slots of every sequence's `seen` set (seen_slots0)
-    size_t seen0_total = 0;
+    size_t seen0_total = 0, seen0_zeroed = 0;      // slots of all initial tables; of those beyond the bitmap budget, which come first and start zeroed
     ClsCfg cf[NGEN + 1];          // (cf[NGEN]: the FFT plan of class 3 beside its FFT-free kernel)
     Caps c;
     Dev d;
@@ -229,7 +229,7 @@ int Wave::setup()
     ENS(codes, sumLr + 16); ENS(seq_off, Sr * 4); ENS(seq_len, Sr * 4);
     ENS(beam, Sr * B * 4); ENS(beam_n, Sr * 4); ENS(done, Sr * 4); ENS(nsteps, Sr * 4);
     ENS(ch_parent, Sr * c.ch_cap * 2); ENS(ch_combo, Sr * c.ch_cap * 8); ENS(ch_dcal, Sr * c.ch_cap * 4); ENS(ch_h, Sr * c.ch_cap * 16);
-    ENS(seen, cr.seen * 16); ENS(seen_off, Sr * 8); ENS(seen_cap, Sr * 4); ENS(seen_cnt, Sr * 4);
+    ENS(seen, cr.seen * 16); ENS(seen_off, Sr * 8); ENS(seen_cap, Sr * 4); ENS(seen_cnt, Sr * 4); ENS(seen_bm, cr.seen / 8 + 64); ENS(seen_mode, Sr * 4);
     ENS(st, cr.st * sizeof(StRec)); ENS(prod, cr.nd * 16);
     ENS(nd, cr.nd * sizeof(NodeRec)); ENS(nlist, cr.nd * 4); ENS(nd_slot, cr.nd * 4); ENS(cslot, cr.cand * 8);
     ENS(pos, cr.pos * 2); ENS(br, cr.br * 4); ENS(sp, cr.sp * 4); ENS(cand, cr.cand * 32);
@@ -290,6 +290,7 @@ int Wave::setup()
     d.ch_parent = (uint16_t *)ws.ch_parent.p; d.ch_combo = (uint64_t *)ws.ch_combo.p; d.ch_dcal = (int *)ws.ch_dcal.p; d.ch_h = (uint64_t *)ws.ch_h.p;
     d.seen = (uint64_t *)ws.seen.p; d.seen_cap_total = c.seen;
     d.seen_off = (uint64_t *)ws.seen_off.p; d.seen_cap = (uint32_t *)ws.seen_cap.p; d.seen_cnt = (uint32_t *)ws.seen_cnt.p;
+    d.seen_bm = (uint32_t *)ws.seen_bm.p; d.seen_mode = (uint32_t *)ws.seen_mode.p;
     d.st_cap = (uint32_t)c.st;
     d.st = (StRec *)ws.st.p;
     d.prod = (ProdEnt *)ws.prod.p; d.prod_shard_cap = c.nd / NSHARD;
@@ -311,6 +312,25 @@ int Wave::setup()
     if (seam) d.dbg = seam->dbg;
 
 
+    // beam_step_kernel LDS: time-shared region 0 (walk scratch 24 B/thread and the occupancy bitmap of the sequence's `seen` table, then
+    // the sort keys), region list, per-member records.  The bitmap's budget: for the 256-thread kernel 4 KiB - tables of up to 32 768
+    // slots -, which keeps five workgroups on a CU with the benchmark's plan (measured against 8 KiB: DESIGN.md 3.11); for the
+    // 1024-thread kernel, one workgroup per CU, 32 KiB.  While a set grows the old bitmap is parked in the walk's scratch, 16 bytes
+    // per thread: a budget is at most twice that.  A table beyond the budget keeps the compare-and-swap protocol.  (A wave only ever
+    // goes from the 256-thread kernel to the 1024-thread one, so that one's budget is never the smaller: no launch meets a table in
+    // bitmap mode that it cannot hold.)
+    for (int v = 1; v >= 0; v--) {
+        const size_t nt = v ? 1024 : 256;
+        const size_t rest = RL_CAP * 12 + B * sizeof(ParentInfo) + (B + 1) * 8 + ((B + 3) & ~(size_t)3) * 4 + 128 + B * 4;      // (+ B ints: the prepass's first node-list entries)
+        size_t bm = v ? 32768 : 4096;
+        if (cfg.seen_bm_max >= 0) bm = std::min((size_t)cfg.seen_bm_max & ~(size_t)15, 32 * nt);
+        while (bm && 24 * nt + bm + rest > 160 * 1024) bm = (bm / 2) & ~(size_t)15;
+        if (v == 0) bm = std::min(bm, bs_bm[1]);
+        bs_bm[v] = bm;
+        bs_lds[v] = std::max((size_t)c.sort_cap * 8, 24 * nt + bm) + rest;
+    }
+    d.seen_bm0 = (uint32_t)bs_bm[S < (size_t)std::max(0, cfg.wide_below) ? 1 : 0];      // (issue_step: which kernel takes the first step)
+
     const double ms_plan = since(tw0);
     hipStream_t st = ws.stream;
     // (RAFFT_TRACE: a call of this section that keeps the scheduler thread for more than a millisecond is named - every wave in flight waits)
@@ -328,8 +348,18 @@ int Wave::setup()
         // the sequences' initial `seen` tables, back to back (seen_slots0)
         uint64_t *so = (uint64_t *)((char *)stage.p + st_soff);
         uint32_t *sc = (uint32_t *)((char *)stage.p + st_scap);
+        // (the tables beyond the first launch's bitmap budget come first: they start zeroed, by one memset - init_roots_kernel applies
+        //  the same test to set Dev::seen_mode)
         size_t o = 0;
-        for (size_t i = 0; i < S; i++) { so[i] = o; sc[i] = seen_cap0[i]; o += seen_cap0[i]; }
+        for (int big = 1; big >= 0; big--) {
+            for (size_t i = 0; i < S; i++) {
+                if ((seen_cap0[i] / 8 > d.seen_bm0) != (big != 0)) continue;
+                // (a table's bitmap is addressed as bit so[i] of the bitmap arena, in whole 32-bit words)
+                if ((o | seen_cap0[i]) & 31) return fail(RAFFT_ERR_PARAM, "internal: a seen table does not start on a whole word of the bitmap arena");
+                so[i] = o; sc[i] = seen_cap0[i]; o += seen_cap0[i];
+            }
+            if (big) seen0_zeroed = o;
+        }
         // base codes | offsets | lengths | seen-table offsets | sizes | counters image: one kernel reads them out of the pinned chunk
         StageIn si;
         memset(&si, 0, sizeof si);
@@ -345,17 +375,16 @@ int Wave::setup()
     slow_call("the launch of stage_in_kernel");
     if (d.memo) HIPCHK(hipMemsetAsync(ws.looptab.p, 0, c.looptab * 8, st));
     slow_call("the memset of the loop table");
-    HIPCHK(hipMemsetAsync(ws.seen.p, 0, seen0_total * 16, st));   // first region of every sequence; later regions are zeroed on allocation
-    slow_call("the memset of the seen tables");
+    // the bitmaps of every sequence's first table (1/128 of the tables' own bytes; the tables are not zeroed: a slot is read only where
+    // its bit is set), and the first tables beyond the bitmap budget themselves; tables handed out later build their bitmap, or are
+    // zeroed, where they are allocated (seen_grow).
+    if (d.seen_bm0) HIPCHK(hipMemsetAsync(ws.seen_bm.p, 0, seen0_total / 8, st));
+    if (seen0_zeroed) HIPCHK(hipMemsetAsync(ws.seen.p, 0, seen0_zeroed * 16, st));
+    slow_call("the memset of the seen bitmaps");
     hipLaunchKernelGGL(init_roots_kernel, dim3((unsigned)S), dim3(64), 0, st, d);
     HIPCHK(hipGetLastError());
     slow_call("the launch of init_roots_kernel");
     if (seam) HIPCHK(hipStreamSynchronize(st));      // (the seam overwrites the root region with synchronous copies right after)
-    // beam_step_kernel LDS: time-shared region 0 (walk scratch 24 B/thread, then sort keys), region list, per-member records
-    for (int v = 0; v < 2; v++) {
-        const size_t nt = v ? 1024 : 256;
-        bs_lds[v] = std::max((size_t)c.sort_cap * 8, 24 * nt) + RL_CAP * 12 + B * sizeof(ParentInfo) + (B + 1) * 8 + ((B + 3) & ~(size_t)3) * 4 + 128 + B * 4;      // (+ B ints: the prepass's first node-list entries)
-    }
     mat_lds = 20 * (size_t)d.max_prod;
     out_row_lds = ((size_t)maxL + 15) & ~(size_t)15;      // output_kernel builds a dot-bracket row in LDS: the longest sequence of the wave
     n_active = (unsigned)S;
@@ -413,8 +442,8 @@ int Wave::issue_step()
         SPAN_REC(sp.a, st, sp.kind);
         // few sequences left (the long ones): a 1024-thread workgroup per sequence shortens the serial
         // chains (16 wavefronts for the prepass, 1024 combos per chunk); many sequences: 256 threads
-        if (n_active < wide_below) hipLaunchKernelGGL((beam_step_kernel<1024>), dim3((unsigned)S), dim3(1024), bs_lds[1], st, d, c.sort_cap);
-        else hipLaunchKernelGGL((beam_step_kernel<256>), dim3((unsigned)S), dim3(256), bs_lds[0], st, d, c.sort_cap);
+        if (n_active < wide_below) hipLaunchKernelGGL((beam_step_kernel<1024>), dim3((unsigned)S), dim3(1024), bs_lds[1], st, d, c.sort_cap, (int)bs_bm[1]);
+        else hipLaunchKernelGGL((beam_step_kernel<256>), dim3((unsigned)S), dim3(256), bs_lds[0], st, d, c.sort_cap, (int)bs_bm[0]);
         HIPCHK(hipGetLastError());
         SPAN_REC(sp.b, st, sp.kind);
         spans.push_back(sp);
