@@ -195,7 +195,8 @@ int rafft_param_value(const char *table, int enthalpy, long index, int *value_ou
  * auto_cor (rafft/utils.py:125-132) + ranking (rafft/rafft.py:117-118,92) +
  * window_slide (rafft/rafft.py:36-83) + the energy filter/sort of
  * find_best_consecutives (rafft/rafft.py:86-109) for ONE unpaired region `pos[0..n)`
- * of the structure `db`.  Output arrays must hold min(nb_mode, 2n-1) entries. */
+ * of the structure `db`.  Output arrays must hold min(nb_mode, 2n-1) entries.
+ * RAFFT_ERR_PARAM when the region's loop has more than 4095 branch helices. */
 int rafft_expand_node(const rafft_params *p, const char *seq, const char *db, const int *pos, int n,
                       int *n_ranked, int *lag, double *corval, int *nb, int *mi, int *mj,
                       double *score, int *ddcal, int *n_kept, int *kept);

@@ -115,9 +115,13 @@ int expand_node(const rafft_params *p, const char *seq, const char *db, const in
     if (L == 0 || L > RAFFT_MAX_LEN || n < 1 || n > L) return fail(RAFFT_ERR_PARAM, "bad node");
     std::vector<int16_t> pt;
     if (!parse_db(db, L, pt)) return fail(RAFFT_ERR_STRUCT, "malformed dot-bracket");
+    LoopOf lp = enclosing_loop(pt, pos[0]);
+    // (a candidate's four cut points are 12-bit branch counts and the class for the biggest regions stages BIG_BR + 1 branch words in
+    //  LDS: a loop with more helices is refused here, before the device is touched - Cand::set_cuts, class_cfg's BR[0])
+    if ((int)lp.br.size() > BIG_BR)
+        return fail(RAFFT_ERR_PARAM, "loop with " + std::to_string(lp.br.size()) + " branch helices: at most " + std::to_string(BIG_BR) + " in one loop (12-bit branch cut points)");
     SeamGuard sg;
     if (int rc = sg.enter()) return rc;
-    LoopOf lp = enclosing_loop(pt, pos[0]);
     SeamIn sm;
     sm.ci = lp.ci; sm.cj = lp.cj; sm.br = std::move(lp.br);
     sm.pos.assign(pos, pos + n);
