@@ -386,6 +386,43 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
                    double *const *prob_out     /* may be NULL, and so may prob_out[s]: lens[s] x lens[s] doubles, row-major,
                                                   P(i pairs j) at [i][j] for i < j, 0 elsewhere */);
 
+/* Structures drawn from the Boltzmann ensemble of a batch (stochastic traceback).  Replaces:
+ * RNA.fold_compound(seq, md).pbacktrack(n) / `RNAsubopt -p n`, what a user of the reference takes from ViennaRNA to compare
+ * fast-folding paths with the thermodynamic ensemble.
+ * The ensemble, the weights, kT and the scaling are rafft_pf_batch's: row k of sequence s is ONE structure, drawn with probability
+ * exp(-dcal / (100 kT)) / Z.  The call runs the MFE path and the inside pass of rafft_pf_batch (three L x L fp64 tables a sequence,
+ * in chunks of whole sequences whose tables and whose rows fit workspace_bytes each; one sequence at least) and then walks the
+ * tables once per sample; dcal_out[s][k] is the sum of the integer loop energies of the terms the walk picked - rafft_eval_structure
+ * of the row gives the same number.  seq_out[s].energy and mfe_dcal have the bits rafft_pf_batch returns.
+ * Random numbers: Philox4x32-10 under the key seeds[s], counter (k, number of the choice within the sample) - nothing is stored.
+ * Same input, same bits: row k of a sequence depends on the sequence, the energy tables, temp, scale_factor, the sequence's seed
+ * and k only - not on the batch, its order, the workspace or n_samples: the first n rows of a call with n_samples = m > n are the
+ * rows of a call with n_samples = n.  Two equal sequences with equal seeds get equal rows: give every copy a seed of its own when
+ * independent samples are wanted.
+ * Outputs (host): seq_out[s]; db_out[s] = n_samples rows, lens[s] + 1 bytes apart, NUL terminated; dcal_out may be NULL and so
+ * may dcal_out[s], else n_samples ints.  n_samples = 0 is valid: the records are filled, no row is touched.
+ * RAFFT_ERR_BAD_CHAR, RAFFT_ERR_EMPTY, RAFFT_ERR_TOO_LONG (above RAFFT_PF_MAX_LEN) and RAFFT_ERR_CAPACITY (the scaled exterior
+ * sum left the fp64 range) are errors of that sequence only: its record has n_samples = 0, its rows are all dots and its dcal 0,
+ * the call returns RAFFT_OK and rafft_last_error() names the first such sequence.  RAFFT_ERR_PARAM, before anything is launched:
+ * a null seq_out, a null db_out with n_samples > 0, a negative n_seq or n_samples, n_samples above RAFFT_SAMPLE_MAX, a
+ * scale_factor that is negative or not finite.  RAFFT_ERR_TEMP as for the fold. */
+#define RAFFT_SAMPLE_MAX (1 << 20)
+typedef struct {
+    int32_t status;      /* as rafft_pf_seq: BAD_CHAR / EMPTY / TOO_LONG / CAPACITY stay with their sequence */
+    int32_t length;
+    int32_t mfe_dcal;    /* the MFE the scale was taken from */
+    int32_t n_samples;   /* rows written: n_samples of the call, or 0 when status != 0 */
+    double  energy;      /* ensemble free energy, the same bits rafft_pf_batch returns */
+} rafft_sample_seq;      /* 24 bytes */
+int rafft_sample_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                       double scale_factor,        /* 0: 1.07 */
+                       long long workspace_bytes,  /* 0: 512 MiB; one sequence at least */
+                       int n_samples,
+                       const unsigned long long *seeds /* [n_seq]; NULL: all 0 */,
+                       rafft_sample_seq *seq_out,
+                       char *const *db_out         /* db_out[s]: n_samples rows, lens[s]+1 bytes apart, NUL terminated */,
+                       int *const *dcal_out        /* may be NULL and so may dcal_out[s]: n_samples ints */);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

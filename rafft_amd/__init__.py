@@ -9,7 +9,7 @@ from .rafft import fold, fold_batch, submit_batch, eval_structures, eval_structu
 from .params import load_params, load_params_from_viennarna, reset_params, save_params, params_info, unpinned_entries  # noqa: F401
 from .rafft_kin import kinetics, kinetics_batch  # noqa: F401
 from .zuker import mfe, mfe_batch  # noqa: F401
-from .mccaskill import pf, pf_batch  # noqa: F401
+from .mccaskill import pf, pf_batch, sample, sample_batch  # noqa: F401
 # (the function `landscape.landscape` is exported as folding_landscape: `rafft_amd.landscape` stays the module)
 from .landscape import landscape as folding_landscape, distance_matrix_gpu, mds_gpu, surface_gpu, Landscape  # noqa: F401
 from .utils import Structure, parse_rafft_output, paired_positions, dot_bracket, read_fasta, format_trajectory  # noqa: F401

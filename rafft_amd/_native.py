@@ -67,12 +67,21 @@ class PfSeq(C.Structure):
 
 PF_MAX_LEN = MFE_MAX_LEN         # RAFFT_PF_MAX_LEN
 
+
+class SampleSeq(C.Structure):
+    """rafft_sample_seq: one record per sequence of rafft_sample_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("mfe_dcal", C.c_int32), ("n_samples", C.c_int32), ("energy", C.c_double)]
+
+
+SAMPLE_MAX = 1 << 20             # RAFFT_SAMPLE_MAX
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
            "rafft_param_value", "rafft_kin_rate_matrix", "rafft_shutdown", "rafft_alloc_counters", "rafft_eval_structures_info", "rafft_params_unpinned",
            "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
-           "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch"]
+           "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
+           "rafft_sample_batch"]
 
 _lib = None
 
@@ -165,6 +174,8 @@ def lib():
     L.rafft_mfe_lds_len.argtypes = []
     L.rafft_pf_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.POINTER(PfSeq),
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_sample_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.c_int,
+                                     C.POINTER(C.c_ulonglong), C.POINTER(SampleSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 

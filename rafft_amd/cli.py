@@ -58,6 +58,12 @@ _OPTIONS = [
                                                "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
                                                "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
                                                "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --kin or --traj")),
+    (("--sample",), dict(type=int, metavar="N", help="no RAFFT fold: N structures drawn from the Boltzmann ensemble of every sequence on the GPU\n"
+                                                     "(rafft_amd.sample_batch; the ensemble of --pf).  Per sequence the fast-folding-graph text with a single\n"
+                                                     "step 0 that holds the distinct sampled structures, energy ascending - `rafft_landscape OUT` draws the\n"
+                                                     "sampled ensemble.  With --scores the samples of every sequence are scored as a beam.\n"
+                                                     "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --pf, --kin or --traj")),
+    (("--seed",), dict(type=int, default=0, help="with --sample: the seed (default 0); the same seed gives the same structures")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
     (("--output", "-o"), dict(help="write the result there instead of stdout")),
@@ -242,6 +248,38 @@ def main_pf(args, seqs, known, names, pf_batch=None, scorer=None):
         sys.stdout.write(text)
 
 
+def sampled_step(structs):
+    """the distinct structures of a list of samples, energy ascending, ties by row text"""
+    seen = {}
+    for st in structs:
+        seen.setdefault(st.str_struct, st)
+    return sorted(seen.values(), key=lambda st: (st.dcal, st.str_struct))
+
+
+def main_sample(args, seqs, known, names, sample_batch=None, scorer=None):
+    """--sample N: structures drawn from the ensemble instead of the fold.  `scorer` as for main_mfe."""
+    if args.mfe or args.pf or args.kin or args.traj:
+        raise SystemExit("--sample gives structures drawn from the ensemble of every sequence: no --mfe, no --pf, no --kin, no --traj")
+    if args.sample < 1:
+        raise SystemExit("--sample needs a positive number of structures")
+    if sample_batch is None:
+        from .mccaskill import sample_batch
+    samples = sample_batch(seqs, args.sample, args.seed, args.temp)
+    if args.scores:
+        if scorer is None:
+            from .scoring import score_rows_gpu as scorer
+        write_scores(args.scores, seqs, names, samples, scorer(samples, known), args.select)
+        if not args.output:
+            return
+    from .utils import format_trajectory
+    text = "".join(format_trajectory(s, [sampled_step(sm)]) for s, sm in zip(seqs, samples))
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def _table_note():
     """one line on stderr when the fold used rule / model values of the built-in tables (never with ViennaRNA's own tables loaded)"""
     try:
@@ -256,13 +294,16 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None):
-    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch`: injection points for tests (the fold, the callable (results,
-    known) -> score table that stands in for scoring.score_batch_gpu - with --mfe and --pf for scoring.score_rows_gpu -, the
-    callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable (sequences, temp) that stands
-    in for zuker.mfe_batch, and the callable (sequences, temp) that stands in for mccaskill.pf_batch)."""
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None):
+    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch`: injection points for tests (the fold, the
+    callable (results, known) -> score table that stands in for scoring.score_batch_gpu - with --mfe, --pf and --sample for
+    scoring.score_rows_gpu -, the callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable
+    (sequences, temp) that stands in for zuker.mfe_batch, the callable (sequences, temp) that stands in for mccaskill.pf_batch,
+    and the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch)."""
     args = parse_arguments(argv)
     seqs, known, names = read_records(args)
+    if args.sample is not None and (args.mfe or args.pf or args.kin or args.traj):
+        raise SystemExit("--sample gives structures drawn from the ensemble of every sequence: no --mfe, no --pf, no --kin, no --traj")
     if args.pf and (args.mfe or args.kin or args.traj):
         raise SystemExit("--pf gives the ensemble of every sequence: no --mfe, no --kin, no --traj")
     if args.kin:
@@ -274,6 +315,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
             raise SystemExit("--scores needs -sf CSV --batch with a known structure per sequence "
                              f"(column {args.known_column!r}, or the headerless seq,struct,name file)")
         names = names if names is not None else [""] * len(seqs)
+    if args.sample is not None:
+        return main_sample(args, seqs, known, names, sample_batch, scorer)
     if args.pf:
         return main_pf(args, seqs, known, names, pf_batch, scorer)
     if args.mfe:

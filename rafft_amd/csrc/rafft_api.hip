@@ -40,6 +40,7 @@
 #include "rafft_score.hip"
 #include "rafft_mfe.hip"
 #include "rafft_pf.hip"
+#include "rafft_sample.hip"
 
 // host side, one responsibility per file (each in its own anonymous namespace)
 #include "rafft_host_ctx.h"     // errors, workspaces and their buffers, the global context, memory pools, initialisation
@@ -48,7 +49,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -358,6 +359,19 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
     if (n_seq < 0 || workspace_bytes < 0 || !std::isfinite(scale_factor) || scale_factor < 0.0) return fail(RAFFT_ERR_PARAM, "bad argument");
     if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
     return pf_batch(n_seq, seqs, lens, temp, scale_factor, workspace_bytes, seq_out, db_out, prob_out);
+}
+
+int rafft_sample_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes,
+                       int n_samples, const unsigned long long *seeds, rafft_sample_seq *seq_out, char *const *db_out, int *const *dcal_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || n_samples < 0 || n_samples > RAFFT_SAMPLE_MAX || workspace_bytes < 0 || !std::isfinite(scale_factor) || scale_factor < 0.0)
+        return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (!seq_out || (n_samples > 0 && !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    if (n_seq > 0 && (!seqs || !lens)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int s = 0; s < n_seq; s++)
+        if ((n_samples > 0 && !db_out[s]) || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    return sample_batch(n_seq, seqs, lens, temp, scale_factor, workspace_bytes, n_samples, seeds, seq_out, db_out, dcal_out);
 }
 
 } // extern "C"

@@ -1,7 +1,8 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
-// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds) and pf_batch (partition
-// function and pair probabilities), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence
-// pack, the graph pack, the solve order of a chunk - is in rafft_hostpure.h, where the CPU suite checks it.
+// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
+// function and pair probabilities) and sample_batch (structures drawn from the ensemble), with their *_WORKSPACE budgets.  What
+// they plan without the device - the chunks, the sequence pack, the graph pack, the solve order of a chunk - is in
+// rafft_hostpure.h, where the CPU suite checks it.
 // Part of the single translation unit of rafft_api.hip (included there, after rafft_seam.h, whose SeamGuard and DevScratch they use).
 #pragma once
 
@@ -282,20 +283,92 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
 
 constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
 
-// rafft_pf_batch (arguments validated by the entry point).  One pack, one guard, one upload of the bases.  The MFE of every sequence
-// first (mfe_held: its energy gives the scale; its device buffers are freed before the tables here are allocated), then chunks of
-// whole sequences in input order whose six L x L fp64 tables fit the workspace budget (one sequence at least): per chunk one launch
-// per anti-diagonal upwards, the exterior sums, one launch per anti-diagonal downwards, the probabilities.  One synchronise at the end.
+// The front rafft_pf_batch and rafft_sample_batch share, under the caller's guard: the device copy of the bases, the MFE of every
+// sequence (mfe_held: its energy gives the scale; its device buffers are freed before the tables here are allocated), the scales and
+// their powers, and the plan of chunks of whole sequences in input order whose `n_tabs` L x L fp64 tables - and, with cost2, a second
+// cost per sequence - fit the workspace budget (one sequence at least).  Then, per chunk, pf_front_inside: one launch per
+// anti-diagonal upwards and the exterior sums.  The buffers live in the caller's DevScratch.
+struct PfFront {
+    double kt, beta;
+    std::vector<rafft_mfe_seq> mfe;
+    std::vector<PfSeq> qs;
+    ChunkPlan plan;
+    unsigned long long n_db = 0;
+    uint8_t *d_codes; PfSeq *d_qs; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
+};
+
+int pf_front(hipStream_t st, DevScratch &mem, const SeqPack &pk, double temp, double scale_factor, long long workspace_bytes, int n_tabs,
+             const size_t *cost2, PfFront &f)
+{
+    const int n_seq = (int)pk.L.size();
+    const std::vector<int> &order = pk.fold;
+    f.mfe.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) f.mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+    if (int rc = mem.alloc(f.d_codes, pk.codes.size())) return rc;
+    HIPCHK(hipMemcpyAsync(f.d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
+    if (int rc = mfe_held(st, pk, f.d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, f.mfe.data(), nullptr)) return rc;
+    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
+    f.kt = kt; f.beta = beta;
+    std::vector<PfSeq> &qs = f.qs;
+    qs.resize(n_seq);
+    unsigned long long n_aux = 0, n_db = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const int L = pk.L[s];
+        const double ln_scale = L ? -sf * ((double)f.mfe[s].dcal / 100.0) / (kt * (double)L) : 0.0;
+        const double scale = std::exp(ln_scale);
+        qs[s] = PfSeq{pk.code_off[s], 0, n_aux, n_db, L, f.mfe[s].dcal, scale, std::log(scale)};
+        if (!L) continue;
+        n_aux += 4 * ((unsigned long long)L + 1); n_db += (unsigned long long)L + 1;
+    }
+    f.n_db = n_db;
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE;
+    std::vector<size_t> tab_bytes(order.size());
+    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)n_tabs * qs[order[k]].L * qs[order[k]].L * sizeof(double);
+    f.plan = plan_chunks(order.size(), tab_bytes.data(), cost2, budget, 65535);                       // (gridDim.y, as mfe_held)
+    for (size_t k = 0; k < order.size(); k++) qs[order[k]].tab_off = f.plan.off[k] / sizeof(double);
+    if (int rc = mem.alloc(f.d_qs, qs.size() * sizeof(PfSeq))) return rc;
+    if (int rc = mem.alloc(f.d_aux, n_aux * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(f.d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(f.d_rec, qs.size() * sizeof(PfRec))) return rc;
+    if (int rc = mem.alloc(f.d_order, order.size() * 4)) return rc;
+    if (int rc = mem.alloc(f.d_ws, f.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(f.d_qs, qs.data(), qs.size() * sizeof(PfSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(f.d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(f.d_rec, 0, qs.size() * sizeof(PfRec), st));
+    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, f.d_qs, n_seq, f.d_aux, beta);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// launches per anti-diagonal of a chunk whose longest sequence has Lmax positions: four cells per workgroup
+unsigned pf_diag_blocks(int Lmax, int d) { return (unsigned)std::min((Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); }
+
+// the inside tables and the exterior sums of chunk c; Lmax: the chunk's longest sequence
+int pf_front_inside(hipStream_t st, const SeqPack &pk, const PfFront &f, const ChunkPlan::Range &c, int &Lmax)
+{
+    const int *ord = f.d_order + c.a;
+    const unsigned ny = (unsigned)(c.b - c.a);
+    Lmax = 0;
+    for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, f.qs[pk.fold[k]].L);
+    for (int d = 0; d < Lmax; d++)
+        hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(Lmax, d), ny), dim3(PF_NT), 0, st, g.T, f.d_qs, ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(pf_exterior_kernel, dim3(ny), dim3(64), 0, st, g.T, f.d_qs, ord, f.d_codes, f.d_ws, f.d_aux, f.beta, f.kt, f.d_db, f.d_rec);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// rafft_pf_batch (arguments validated by the entry point).  One pack, one guard, one upload of the bases.  The shared front, then
+// per chunk of six tables a sequence: the inside pass, one launch per anti-diagonal downwards, the probabilities.  One synchronise at
+// the end.
 int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, rafft_pf_seq *seq_out,
              char *const *db_out, double *const *prob_out)
 {
     if (int rc = check_temp(temp)) return rc;
     if (n_seq == 0) return 0;
     const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);     // (RAFFT_PF_MAX_LEN is RAFFT_MFE_MAX_LEN)
-    std::vector<rafft_mfe_seq> mfe(n_seq);
     for (int s = 0; s < n_seq; s++) {
         const int len = pk.len[s];
-        mfe[s] = rafft_mfe_seq{pk.status[s], len, 0, 0};
         seq_out[s] = rafft_pf_seq{pk.status[s], len, 0, 0, 0.0, 0.0};
         dot_row(db_out[s], len);
         if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)len * len * sizeof(double));
@@ -308,67 +381,31 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
     if (int rc = ensure_tables(temp)) return rc;
     hipStream_t st = sg.stream;
     DevScratch mem;
-    uint8_t *d_codes;
-    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
-    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
-    if (int rc = mfe_held(st, pk, d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, mfe.data(), nullptr)) return rc;
-    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
-    std::vector<PfSeq> qs(n_seq);
-    unsigned long long n_aux = 0, n_db = 0;
-    for (int s = 0; s < n_seq; s++) {
-        const int L = pk.L[s];
-        seq_out[s].mfe_dcal = mfe[s].dcal;
-        const double ln_scale = L ? -sf * ((double)mfe[s].dcal / 100.0) / (kt * (double)L) : 0.0;
-        const double scale = std::exp(ln_scale);
-        qs[s] = PfSeq{pk.code_off[s], 0, n_aux, n_db, L, mfe[s].dcal, scale, std::log(scale)};
-        if (!L) continue;
-        n_aux += 4 * ((unsigned long long)L + 1); n_db += (unsigned long long)L + 1;
-    }
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE;
-    std::vector<size_t> tab_bytes(order.size());
-    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = 6 * (size_t)qs[order[k]].L * qs[order[k]].L * sizeof(double);
-    const ChunkPlan plan = plan_chunks(order.size(), tab_bytes.data(), nullptr, budget, 65535);      // (gridDim.y, as mfe_held)
-    for (size_t k = 0; k < order.size(); k++) qs[order[k]].tab_off = plan.off[k] / sizeof(double);
-    const size_t ws_max = plan.max_cost;
-    PfSeq *d_qs; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
-    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(PfSeq))) return rc;
-    if (int rc = mem.alloc(d_aux, n_aux * sizeof(double) + 16)) return rc;
-    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
-    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(PfRec))) return rc;
-    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
-    if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
-    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(PfSeq), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(PfRec), st));
-    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, d_qs, n_seq, d_aux, beta);
-    HIPCHK(hipGetLastError());
-    for (const ChunkPlan::Range &c : plan.chunks) {
-        const int *ord = d_order + c.a;
+    PfFront f;
+    if (int rc = pf_front(st, mem, pk, temp, scale_factor, workspace_bytes, 6, nullptr, f)) return rc;
+    const std::vector<PfSeq> &qs = f.qs;
+    for (int s = 0; s < n_seq; s++) seq_out[s].mfe_dcal = f.mfe[s].dcal;
+    for (const ChunkPlan::Range &c : f.plan.chunks) {
+        const int *ord = f.d_order + c.a;
         const unsigned ny = (unsigned)(c.b - c.a);
-        int Lmax = 0;
-        for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, qs[order[k]].L);
-        const auto nx = [&](int d) { return (unsigned)std::min((Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); };
-        for (int d = 0; d < Lmax; d++)
-            hipLaunchKernelGGL(pf_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pf_exterior_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, kt, d_db, d_rec);
-        HIPCHK(hipGetLastError());
+        int Lmax;
+        if (int rc = pf_front_inside(st, pk, f, c, Lmax)) return rc;
         for (int d = Lmax - 1; d >= 4; d--)
-            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(nx(d), ny), dim3(PF_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_aux, beta, d);
+            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(Lmax, d), ny), dim3(PF_NT), 0, st, g.T, f.d_qs, ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pf_prob_kernel, dim3(nx(0), ny), dim3(PF_NT), 0, st, d_qs, ord, d_ws, d_aux, d_db, d_rec);
+        hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(Lmax, 0), ny), dim3(PF_NT), 0, st, f.d_qs, ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
         HIPCHK(hipGetLastError());
         if (prob_out)
             for (size_t k = c.a; k < c.b; k++) {
                 const PfSeq &q = qs[order[k]];
                 if (prob_out[order[k]])
-                    HIPCHK(hipMemcpyAsync(prob_out[order[k]], d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipMemcpyAsync(prob_out[order[k]], f.d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
             }
     }
     std::vector<PfRec> rec(n_seq);
-    std::vector<char> db(n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    std::vector<char> db(f.n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), f.d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), f.d_db, f.n_db, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     std::string err = pk.first_err;
     for (int s = 0; s < n_seq; s++) {
@@ -384,6 +421,92 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
         seq_out[s].energy = rec[s].energy;
         seq_out[s].mfe_frequency = rec[s].mfe_frequency;
         memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    g_err = err;
+    return 0;
+}
+
+// ---- structures drawn from the ensemble
+
+// rafft_sample_batch (arguments validated by the entry point).  The shared front with three tables a sequence - the inside tables
+// are all a stochastic traceback reads - and the rows of a chunk (n_samples (L + 1) bytes a sequence) as the planner's second cost.
+// Per chunk: the inside pass, sample_kernel over (groups of four samples, sequences), one synchronise, the rows and energies of the
+// sequences that passed the range check straight into the caller's buffers.
+int sample_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, int n_samples,
+                 const unsigned long long *seeds, rafft_sample_seq *seq_out, char *const *db_out, int *const *dcal_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    for (int s = 0; s < n_seq; s++) {
+        seq_out[s] = rafft_sample_seq{pk.status[s], pk.len[s], 0, 0, 0.0};
+        if (!pk.status[s]) continue;
+        for (int k = 0; k < n_samples; k++) dot_row(db_out[s] + (size_t)k * ((size_t)pk.len[s] + 1), pk.len[s]);
+        if (dcal_out && dcal_out[s]) memset(dcal_out[s], 0, (size_t)n_samples * sizeof(int));
+    }
+    g_err = pk.first_err;
+    const std::vector<int> &order = pk.fold;
+    if (order.empty()) return 0;
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    if (int rc = ensure_tables(temp)) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    PfFront f;
+    std::vector<size_t> row_bytes(order.size());
+    for (size_t k = 0; k < order.size(); k++) row_bytes[k] = (size_t)n_samples * ((size_t)pk.L[order[k]] + 1);
+    if (int rc = pf_front(st, mem, pk, temp, scale_factor, workspace_bytes, 3, row_bytes.data(), f)) return rc;
+    const std::vector<PfSeq> &qs = f.qs;
+    std::vector<SampleSeq> smp(n_seq, SampleSeq{0, 0, 0});
+    size_t max_seqs = 0;
+    for (const ChunkPlan::Range &c : f.plan.chunks) {
+        unsigned long long at = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            smp[order[k]] = SampleSeq{seeds ? seeds[order[k]] : 0ull, at, (unsigned long long)(k - c.a) * (unsigned long long)n_samples};
+            at += row_bytes[k];
+        }
+        max_seqs = std::max(max_seqs, c.b - c.a);
+    }
+    SampleSeq *d_smp; char *d_rows; int *d_dcal, *d_bad;
+    if (int rc = mem.alloc(d_smp, smp.size() * sizeof(SampleSeq))) return rc;
+    if (int rc = mem.alloc(d_rows, f.plan.max_cost2 + 16)) return rc;
+    if (int rc = mem.alloc(d_dcal, max_seqs * (size_t)n_samples * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_bad, (size_t)n_seq * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(d_smp, smp.data(), smp.size() * sizeof(SampleSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_bad, 0, (size_t)n_seq * 4, st));
+    std::vector<PfRec> rec(n_seq);
+    std::vector<int> bad(n_seq);
+    std::string err = pk.first_err;
+    for (const ChunkPlan::Range &c : f.plan.chunks) {
+        int Lmax;
+        if (int rc = pf_front_inside(st, pk, f, c, Lmax)) return rc;
+        if (n_samples > 0) {
+            hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n_samples + SAMPLE_NT / 64 - 1) / (SAMPLE_NT / 64)), (unsigned)(c.b - c.a)), dim3(SAMPLE_NT),
+                               (size_t)sample_lds_bytes(Lmax), st, g.T, f.d_qs, f.d_order + c.a, f.d_codes, f.d_ws, f.d_aux, f.beta, f.d_rec, d_smp, n_samples,
+                               Lmax, d_rows, d_dcal, d_bad);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(rec.data(), f.d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(bad.data(), d_bad, (size_t)n_seq * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = order[k], L = qs[s].L;
+            seq_out[s].mfe_dcal = f.mfe[s].dcal;
+            if (bad[s]) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + (bad[s] == SAMPLE_BAD_STACK ? ": the sampling stack is full" : ": a sampled cell has no candidate"));
+            if (rec[s].status) {
+                // the scaled tables left the fp64 range: nothing of this sequence is sampled
+                seq_out[s].status = RAFFT_ERR_CAPACITY;
+                for (int r = 0; r < n_samples; r++) dot_row(db_out[s] + (size_t)r * ((size_t)L + 1), L);
+                if (dcal_out && dcal_out[s]) memset(dcal_out[s], 0, (size_t)n_samples * sizeof(int));
+                if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
+                continue;
+            }
+            seq_out[s].energy = rec[s].energy;
+            seq_out[s].n_samples = n_samples;
+            if (n_samples == 0) continue;
+            HIPCHK(hipMemcpy(db_out[s], d_rows + smp[s].row_off, row_bytes[k], hipMemcpyDeviceToHost));
+            if (dcal_out && dcal_out[s]) HIPCHK(hipMemcpy(dcal_out[s], d_dcal + smp[s].dcal_off, (size_t)n_samples * sizeof(int), hipMemcpyDeviceToHost));
+        }
     }
     g_err = err;
     return 0;

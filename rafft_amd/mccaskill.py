@@ -1,6 +1,7 @@
 """Partition function, base-pair probabilities and centroid structures on the GPU (rafft_pf_batch): what a
 user of the reference gets from ViennaRNA's RNA.fold_compound(seq, md).pf() / bpp(), the calls beside the RNA.fold of
-benchmark_results/src/vrna_mfe.py:25.  The ensemble is the one mfe_batch minimises over."""
+benchmark_results/src/vrna_mfe.py:25.  The ensemble is the one mfe_batch minimises over.  Structures drawn from that ensemble
+(rafft_sample_batch): what ViennaRNA's pbacktrack / `RNAsubopt -p` give."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +9,7 @@ import numpy as np
 from . import _native as N
 from . import params as _params_mod
 from .rafft import _raise_like_reference
+from .utils import Structure, energies_from_dcal
 
 
 class PfResult:
@@ -67,3 +69,68 @@ def pf_batch(sequences, temp=37.0, probs=True, raise_errors=True):
 
 def pf(sequence, temp=37.0, probs=True):
     return pf_batch([sequence], temp, probs)[0]
+
+
+def _seeds_of(seeds, n):
+    """None, one int for every sequence, or one int per sequence -> a list of n ints below 2^64, or None"""
+    if seeds is None:
+        return None
+    if isinstance(seeds, (int, np.integer)):
+        seeds = [int(seeds)] * n
+    seeds = [int(x) for x in seeds]
+    if len(seeds) != n:
+        raise ValueError(f"{len(seeds)} seeds for {n} sequences")
+    if any(not 0 <= x < 1 << 64 for x in seeds):
+        raise ValueError("a seed is an integer in 0 .. 2^64 - 1")
+    return seeds
+
+
+def sample_batch_raw(sequences, n_samples, seeds=None, temp=37.0, scale_factor=0.0, workspace_bytes=0):
+    """(records, rows, dcal) of rafft_sample_batch: one dict per sequence with the fields of rafft_sample_seq, per sequence an
+    (n_samples, L + 1) uint8 array - a row is the dot-bracket text and its NUL - and an int32 array of the rows' energies in
+    dcal/mol.  Nothing is raised for a sequence's own error (its rows are all dots, its record has n_samples 0).  seeds: None (all
+    0), one int used for every sequence, or one int per sequence; row k of a sequence depends on its seed and k, not on n_samples
+    or the batch.  scale_factor / workspace_bytes as in include/rafft_hip.h."""
+    L = N.lib()
+    _params_mod.ensure_default_params()
+    n, n_samples = len(sequences), int(n_samples)
+    enc, arr, lens = N.seq_arrays(sequences)
+    seeds = _seeds_of(seeds, n)
+    sd = (C.c_ulonglong * n)(*seeds) if seeds is not None else None
+    rec = (N.SampleSeq * n)()
+    if not 0 <= n_samples <= N.SAMPLE_MAX:       # (no buffers for a call the library refuses)
+        N.check(L.rafft_sample_batch(n, arr, lens, float(temp), float(scale_factor), int(workspace_bytes), n_samples, sd, rec, None, None))
+    rows = [np.zeros((n_samples, len(e) + 1), dtype=np.uint8) for e in enc]
+    dcal = [np.zeros(n_samples, dtype=np.int32) for _ in enc]
+    out = (C.c_void_p * n)(*[r.ctypes.data for r in rows])
+    dc = (C.c_void_p * n)(*[d.ctypes.data for d in dcal])
+    N.check(L.rafft_sample_batch(n, arr, lens, float(temp), float(scale_factor), int(workspace_bytes), n_samples, sd, rec, out, dc))
+    recs = [{k: getattr(r, k) for k, _ in N.SampleSeq._fields_} for r in rec]
+    return recs, rows, dcal
+
+
+def sample_batch(sequences, n_samples, seeds=None, temp=37.0, raise_errors=True):
+    """n_samples structures drawn from the Boltzmann ensemble of every sequence, as a list of lists of utils.Structure (in the
+    order drawn, repeats included).  A sequence with an error raises what fold_batch raises for it (raise_errors=False: None)."""
+    recs, rows, dcal = sample_batch_raw(sequences, n_samples, seeds, temp)
+    out = []
+    for k, s in enumerate(sequences):
+        st = recs[k]["status"]
+        if st != N.OK:
+            if raise_errors:
+                if st == N.ERR_TOO_LONG:
+                    raise ValueError(f"sequence of {len(s)} nt: sample_batch takes up to {N.PF_MAX_LEN} nt (RAFFT_PF_MAX_LEN)")
+                if st == N.ERR_CAPACITY:
+                    raise N.RafftError(st, f"sequence {k}: the scaled partition function left the fp64 range")
+                _raise_like_reference(st, s)
+            out.append(None)
+            continue
+        en = energies_from_dcal(dcal[k]).tolist()
+        text = rows[k][:, :-1].tobytes().decode("ascii")
+        n = len(s)
+        out.append([Structure(text[r * n:(r + 1) * n], int(dcal[k][r]), en[r]) for r in range(len(en))])
+    return out
+
+
+def sample(sequence, n_samples, seed=None, temp=37.0):
+    return sample_batch([sequence], n_samples, seed, temp)[0]
