@@ -423,6 +423,51 @@ int rafft_sample_batch(int n_seq, const char *const *seqs, const int *lens, doub
                        char *const *db_out         /* db_out[s]: n_samples rows, lens[s]+1 bytes apart, NUL terminated */,
                        int *const *dcal_out        /* may be NULL and so may dcal_out[s]: n_samples ints */);
 
+/* Every structure of a batch within an energy band above the minimum (Wuchty et al. 1999).  Replaces:
+ * `RNAsubopt -e delta -s`, the producer of the file the reference's landscape tool reads with --sub (utility/surface.py:54-63).
+ * The ensemble is rafft_mfe_batch's: canonical pairs, hairpins of at least 3, interior loops of at most 30 unpaired positions,
+ * lonely pairs allowed, dangles=2.  The number of rows is not known before the call, so the library owns the result, as
+ * rafft_fold_batch does: free it with rafft_subopt_free.
+ * Completeness and energies: the rows of a sequence are exactly the structures of the ensemble with rafft_eval_structure(row) <=
+ * mfe_dcal + delta_dcal, none twice.  dcal[k] is the sum of the integer loop terms the enumeration took - rafft_eval_structure of
+ * the row gives the same number.
+ * Order: rows are sorted by dcal ascending; among equal energies they come in enumeration order, the left-to-right order of the
+ * leaves of the decision tree of DESIGN.md section 12.
+ * Same input, same bits: a sequence's rows are a function of the sequence, the energy tables, temp and delta_dcal only - not of
+ * the batch, its order, the workspace, the chunking, or max_structs when it is large enough.
+ * Capacity: a sequence with more than max_structs structures in the band gets RAFFT_ERR_CAPACITY, no rows, and n_reached; the
+ * call still returns RAFFT_OK, its neighbours are unaffected and rafft_last_error() names the first such sequence.  Exactly
+ * max_structs structures is not an error.
+ * Device memory: every sequence keeps three L x L int32 tables and two buffers of max_structs partial structures (DESIGN.md
+ * section 12 states their bytes); sequences are taken in chunks of whole sequences in input order whose tables and whose buffers
+ * fit workspace_bytes each, one sequence at least.
+ * RAFFT_ERR_BAD_CHAR, RAFFT_ERR_EMPTY and RAFFT_ERR_TOO_LONG (above RAFFT_SUBOPT_MAX_LEN) are errors of that sequence only, as in
+ * rafft_mfe_batch: the call returns RAFFT_OK and rafft_last_error() names the first such sequence.  RAFFT_ERR_PARAM, before
+ * anything is launched: a null argument, a negative n_seq or workspace_bytes, delta_dcal outside [0, RAFFT_SUBOPT_MAX_DELTA],
+ * max_structs outside [1, RAFFT_SUBOPT_MAX_STRUCTS].  RAFFT_ERR_TEMP as for the fold.  A batch of nothing but erroneous sequences
+ * never touches the device.  An internal inconsistency (a partial structure without a continuation, a full stack) is
+ * RAFFT_ERR_HIP with a message, never a short list.  On any error of the call *out is NULL. */
+#define RAFFT_SUBOPT_MAX_LEN     RAFFT_MFE_MAX_LEN
+#define RAFFT_SUBOPT_MAX_STRUCTS (1 << 24)
+#define RAFFT_SUBOPT_MAX_DELTA   1000000          /* dcal: mfe + delta stays far below the 5e8 guard of section 9 */
+typedef struct {
+    int32_t status;        /* BAD_CHAR / EMPTY / TOO_LONG / CAPACITY stay with their sequence */
+    int32_t length;
+    int32_t mfe_dcal;      /* what rafft_mfe_batch returns */
+    int32_t n_structs;     /* rows; 0 when status != 0 */
+    int64_t n_reached;     /* CAPACITY only: the count that first exceeded max_structs - a lower bound of the true count */
+    const char *db;        /* n_structs rows, length + 1 bytes apart, NUL terminated */
+    const int32_t *dcal;   /* [n_structs] */
+} rafft_subopt_seq;        /* 40 bytes */
+typedef struct { int32_t n_seq, n_failed; rafft_subopt_seq *seq; void *_owner; } rafft_subopt_result;
+int  rafft_subopt_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int delta_dcal,
+                        int max_structs, long long workspace_bytes /* 0: 512 MiB */, rafft_subopt_result **out);
+void rafft_subopt_free(rafft_subopt_result *r);
+/* of the last rafft_subopt_batch: levels of the deepest sequence, kernel launches of the enumeration, launches of the table fill,
+ * chunks, sequences that ended in RAFFT_ERR_CAPACITY, microseconds spent filling the tables, microseconds spent enumerating and
+ * copying */
+int  rafft_subopt_counters(long long out[7]);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

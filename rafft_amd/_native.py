@@ -75,13 +75,27 @@ class SampleSeq(C.Structure):
 
 SAMPLE_MAX = 1 << 20             # RAFFT_SAMPLE_MAX
 
+
+class SuboptSeq(C.Structure):
+    """rafft_subopt_seq: one record per sequence of a rafft_subopt_result"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("mfe_dcal", C.c_int32), ("n_structs", C.c_int32), ("n_reached", C.c_int64),
+                ("db", C.POINTER(C.c_char)), ("dcal", C.POINTER(C.c_int32))]
+
+
+class SuboptResult(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("n_failed", C.c_int32), ("seq", C.POINTER(SuboptSeq)), ("_owner", C.c_void_p)]
+
+
+SUBOPT_MAX_STRUCTS = 1 << 24     # RAFFT_SUBOPT_MAX_STRUCTS
+SUBOPT_MAX_DELTA = 1000000       # RAFFT_SUBOPT_MAX_DELTA (dcal)
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
            "rafft_param_value", "rafft_kin_rate_matrix", "rafft_shutdown", "rafft_alloc_counters", "rafft_eval_structures_info", "rafft_params_unpinned",
            "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
            "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
-           "rafft_sample_batch"]
+           "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters"]
 
 _lib = None
 
@@ -176,6 +190,11 @@ def lib():
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_sample_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.c_int,
                                      C.POINTER(C.c_ulonglong), C.POINTER(SampleSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_subopt_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_int, C.c_longlong,
+                                     C.POINTER(C.POINTER(SuboptResult))]
+    L.rafft_subopt_free.argtypes = [C.POINTER(SuboptResult)]
+    L.rafft_subopt_free.restype = None
+    L.rafft_subopt_counters.argtypes = [C.POINTER(C.c_longlong * 7)]
     _lib = L
     return L
 

@@ -63,6 +63,13 @@ _OPTIONS = [
                                                      "step 0 that holds the distinct sampled structures, energy ascending - `rafft_landscape OUT` draws the\n"
                                                      "sampled ensemble.  With --scores the samples of every sequence are scored as a beam.\n"
                                                      "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --pf, --kin or --traj")),
+    (("--subopt",), dict(type=float, metavar="DELTA", help="no RAFFT fold: every structure of every sequence within DELTA kcal/mol of its minimum free energy on\n"
+                                                           "the GPU (rafft_amd.subopt_batch; the ensemble of --mfe; as `RNAsubopt -e DELTA -s`).  Per sequence the\n"
+                                                           "fast-folding-graph text with a single step 0 that holds the band, energy ascending - `rafft_landscape OUT`\n"
+                                                           "draws it.  With --scores the band of every sequence is scored as a beam.\n"
+                                                           "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --pf, --sample, --kin or --traj")),
+    (("--max-structs",), dict(type=int, default=100000, metavar="N", help="with --subopt: a sequence with more than N structures in the band is an error\n"
+                                                                          "(default 100000)")),
     (("--seed",), dict(type=int, default=0, help="with --sample: the seed (default 0); the same seed gives the same structures")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
@@ -280,6 +287,35 @@ def main_sample(args, seqs, known, names, sample_batch=None, scorer=None):
         sys.stdout.write(text)
 
 
+SUBOPT_EXCLUSIVE = "--subopt gives every structure of every sequence within an energy band: no --mfe, no --pf, no --sample, no --kin, no --traj"
+
+
+def main_subopt(args, seqs, known, names, subopt_batch=None, scorer=None):
+    """--subopt DELTA: the structures within DELTA kcal/mol of the minimum instead of the fold.  `scorer` as for main_mfe."""
+    if args.mfe or args.pf or args.sample is not None or args.kin or args.traj:
+        raise SystemExit(SUBOPT_EXCLUSIVE)
+    if not args.subopt >= 0.0:
+        raise SystemExit("--subopt needs an energy band of 0 kcal/mol or more")
+    if args.max_structs < 1:
+        raise SystemExit("--max-structs needs a positive number of structures")
+    if subopt_batch is None:
+        from .wuchty import subopt_batch
+    bands = subopt_batch(seqs, args.subopt, args.max_structs, args.temp)
+    if args.scores:
+        if scorer is None:
+            from .scoring import score_rows_gpu as scorer
+        write_scores(args.scores, seqs, names, bands, scorer(bands, known), args.select)
+        if not args.output:
+            return
+    from .utils import format_trajectory
+    text = "".join(format_trajectory(s, [list(band)]) for s, band in zip(seqs, bands))          # (the library's order)
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def _table_note():
     """one line on stderr when the fold used rule / model values of the built-in tables (never with ViennaRNA's own tables loaded)"""
     try:
@@ -294,14 +330,17 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None):
-    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch`: injection points for tests (the fold, the
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None):
+    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch` / `subopt_batch`: injection points for tests (the fold, the
     callable (results, known) -> score table that stands in for scoring.score_batch_gpu - with --mfe, --pf and --sample for
     scoring.score_rows_gpu -, the callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable
     (sequences, temp) that stands in for zuker.mfe_batch, the callable (sequences, temp) that stands in for mccaskill.pf_batch,
-    and the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch)."""
+    the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch, and the callable (sequences, delta,
+    max_structs, temp) that stands in for wuchty.subopt_batch)."""
     args = parse_arguments(argv)
     seqs, known, names = read_records(args)
+    if args.subopt is not None and (args.mfe or args.pf or args.sample is not None or args.kin or args.traj):
+        raise SystemExit(SUBOPT_EXCLUSIVE)
     if args.sample is not None and (args.mfe or args.pf or args.kin or args.traj):
         raise SystemExit("--sample gives structures drawn from the ensemble of every sequence: no --mfe, no --pf, no --kin, no --traj")
     if args.pf and (args.mfe or args.kin or args.traj):
@@ -315,6 +354,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
             raise SystemExit("--scores needs -sf CSV --batch with a known structure per sequence "
                              f"(column {args.known_column!r}, or the headerless seq,struct,name file)")
         names = names if names is not None else [""] * len(seqs)
+    if args.subopt is not None:
+        return main_subopt(args, seqs, known, names, subopt_batch, scorer)
     if args.sample is not None:
         return main_sample(args, seqs, known, names, sample_batch, scorer)
     if args.pf:

@@ -41,6 +41,7 @@
 #include "rafft_mfe.hip"
 #include "rafft_pf.hip"
 #include "rafft_sample.hip"
+#include "rafft_subopt.hip"
 
 // host side, one responsibility per file (each in its own anonymous namespace)
 #include "rafft_host_ctx.h"     // errors, workspaces and their buffers, the global context, memory pools, initialisation
@@ -49,7 +50,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -372,6 +373,33 @@ int rafft_sample_batch(int n_seq, const char *const *seqs, const int *lens, doub
     for (int s = 0; s < n_seq; s++)
         if ((n_samples > 0 && !db_out[s]) || (lens[s] > 0 && !seqs[s])) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
     return sample_batch(n_seq, seqs, lens, temp, scale_factor, workspace_bytes, n_samples, seeds, seq_out, db_out, dcal_out);
+}
+
+int rafft_subopt_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int delta_dcal, int max_structs, long long workspace_bytes,
+                       rafft_subopt_result **out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    *out = nullptr;
+    if (n_seq < 0 || workspace_bytes < 0 || delta_dcal < 0 || delta_dcal > RAFFT_SUBOPT_MAX_DELTA || max_structs < 1 || max_structs > RAFFT_SUBOPT_MAX_STRUCTS)
+        return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_seq > 0 && (!seqs || !lens)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int s = 0; s < n_seq; s++)
+        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": null pointer");
+    return subopt_batch(n_seq, seqs, lens, temp, delta_dcal, max_structs, workspace_bytes, out);
+}
+
+void rafft_subopt_free(rafft_subopt_result *r)
+{
+    if (r && r->_owner) delete (SuboptOwner *)r->_owner;
+}
+
+int rafft_subopt_counters(long long out[7])
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < 7; k++) out[k] = g_subopt_counters[k];
+    return 0;
 }
 
 } // extern "C"

@@ -1,8 +1,8 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
-// function and pair probabilities) and sample_batch (structures drawn from the ensemble), with their *_WORKSPACE budgets.  What
-// they plan without the device - the chunks, the sequence pack, the graph pack, the solve order of a chunk - is in
-// rafft_hostpure.h, where the CPU suite checks it.
+// function and pair probabilities), sample_batch (structures drawn from the ensemble) and subopt_batch (every structure within an
+// energy band), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
+// pack, the solve order of a chunk - is in rafft_hostpure.h, where the CPU suite checks it.
 // Part of the single translation unit of rafft_api.hip (included there, after rafft_seam.h, whose SeamGuard and DevScratch they use).
 #pragma once
 
@@ -182,6 +182,18 @@ void dot_row(char *db, int len)
     db[len] = 0;
 }
 
+// The HBM-class tables of a chunk of `ny` sequences (d_order: their numbers in d_qs; Lmax: the longest): one launch per
+// anti-diagonal, stream order being the synchronisation.  mfe_held and subopt_batch fill their tables through this.
+int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const int *d_order, unsigned ny, int Lmax, const uint8_t *d_codes, int *d_ws)
+{
+    for (int d = 0; d < Lmax; d++) {
+        const unsigned nx = (unsigned)std::min((Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
+        hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, d_order, d_codes, d_ws, d);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // The MFE folds of a pack, under the caller's guard: the device tables are scaled for the call's temp, d_codes is the device copy
 // of pk.codes, seq_out[s].status is set.  Sequences up to `lds_len` go through mfe_lds_kernel in one launch, the others through
 // the HBM class in chunks whose tables fit the workspace budget (one sequence at least): per chunk one launch per anti-diagonal,
@@ -232,11 +244,7 @@ int mfe_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, int lds_
         const unsigned ny = (unsigned)(c.b - c.a);
         int Lmax = 0;
         for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, qs[hbm_order[k]].L);
-        for (int d = 0; d < Lmax; d++) {
-            const unsigned nx = (unsigned)std::min((Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
-            hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d);
-        }
-        HIPCHK(hipGetLastError());
+        if (int rc = mfe_fill_chunk(st, d_qs, ord, ny, Lmax, d_codes, d_ws)) return rc;
         hipLaunchKernelGGL(mfe_traceback_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_stack, d_db, d_rec);
         HIPCHK(hipGetLastError());
     }
@@ -510,6 +518,182 @@ int sample_batch(int n_seq, const char *const *seqs, const int *lens, double tem
     }
     g_err = err;
     return 0;
+}
+
+// ---- every structure within an energy band
+
+constexpr size_t SUBOPT_WORKSPACE = (size_t)512 << 20;
+constexpr int SUBOPT_POLL_LEVELS = 8;       // levels between two reads of the chunk's "sequences that go on" word
+
+// what a rafft_subopt_result points into; rafft_subopt_free deletes it
+struct SuboptOwner {
+    rafft_subopt_result res;
+    std::vector<rafft_subopt_seq> seq;
+    std::vector<std::vector<char>> db;
+    std::vector<std::vector<int32_t>> dcal;
+};
+
+// of the last call: levels, kernel launches of the enumeration, launches of the table fill, chunks, sequences over their capacity,
+// microseconds of the fill, microseconds of the enumeration with its copies (tools/subopt_measure.py)
+long long g_subopt_counters[7];
+
+// rafft_subopt_batch (arguments validated by the entry point).  One pack, one guard, one upload of the bases.  Chunks of whole
+// sequences in input order: three L x L int32 tables a sequence as the primary cost, its two frontier buffers of max_structs states
+// and its max_structs counts as the second.  Per chunk: the tables (mfe_fill_chunk), the exterior energies and the first state
+// (subopt_init_kernel), then levels of count / scan / emit until the word read back every SUBOPT_POLL_LEVELS levels says that no
+// sequence goes on; the finished states are packed on the device and copied.  The final order - a stable sort on dcal of rows that
+// arrive in enumeration order - is an index permutation on the host, applied while the result is filled.
+int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int delta, int max_structs, long long workspace_bytes,
+                 rafft_subopt_result **out)
+{
+    *out = nullptr;
+    if (int rc = check_temp(temp)) return rc;
+    for (long long &c : g_subopt_counters) c = 0;
+    std::unique_ptr<SuboptOwner> own(new SuboptOwner);
+    own->seq.resize(n_seq); own->db.resize(n_seq); own->dcal.resize(n_seq);
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    int n_failed = 0;
+    for (int s = 0; s < n_seq; s++) {
+        own->db[s].assign(1, 0); own->dcal[s].assign(1, 0);
+        own->seq[s] = rafft_subopt_seq{pk.status[s], pk.len[s], 0, 0, 0, own->db[s].data(), own->dcal[s].data()};
+        n_failed += pk.status[s] != 0;
+    }
+    auto finish = [&](const std::string &err) {
+        own->res = rafft_subopt_result{n_seq, n_failed, own->seq.data(), own.get()};
+        *out = &own->res;
+        own.release();
+        g_err = err;
+        return 0;
+    };
+    const std::vector<int> &order = pk.fold;
+    if (order.empty()) return finish(pk.first_err);
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    if (int rc = ensure_tables(temp)) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    // the plan
+    std::vector<MfeSeq> mq(n_seq, MfeSeq{0, 0, 0, 0, 0, 0});
+    std::vector<SuboptSeq> qs(n_seq, SuboptSeq{0, 0, 0, {0, 0}, 0, 0, 0});
+    std::vector<size_t> tab_bytes(order.size()), front_bytes(order.size());
+    unsigned long long n_f = 0;
+    for (size_t k = 0; k < order.size(); k++) {
+        const int L = pk.L[order[k]];
+        tab_bytes[k] = 3 * (size_t)L * L * 4;
+        front_bytes[k] = 2 * (size_t)max_structs * (size_t)subopt_state_bytes(L) + (((size_t)max_structs * 4 + 255) & ~(size_t)255);
+    }
+    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : SUBOPT_WORKSPACE;
+    const ChunkPlan plan = plan_chunks(order.size(), tab_bytes.data(), front_bytes.data(), budget, 65535);
+    size_t max_seqs = 0;
+    for (const ChunkPlan::Range &c : plan.chunks) {
+        size_t at = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = order[k], L = pk.L[s];
+            const size_t one = (size_t)max_structs * (size_t)subopt_state_bytes(L);
+            mq[s] = MfeSeq{pk.code_off[s], plan.off[k] / 4, 0, 0, L, 0};
+            qs[s] = SuboptSeq{pk.code_off[s], plan.off[k] / 4, n_f, {at, at + one}, (at + 2 * one) / 4, L, 0};
+            n_f += (unsigned long long)L + 1;
+            at += front_bytes[k];
+        }
+        max_seqs = std::max(max_seqs, c.b - c.a);
+    }
+    uint8_t *d_codes; MfeSeq *d_mq; SuboptSeq *d_qs; SuboptRec *d_rec; int *d_order, *d_ws, *d_f, *d_open; unsigned char *d_front;
+    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
+    if (int rc = mem.alloc(d_mq, mq.size() * sizeof(MfeSeq))) return rc;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(SuboptSeq))) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(SuboptRec))) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_f, n_f * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_open, 16)) return rc;
+    if (int rc = mem.alloc(d_ws, plan.max_cost + 16)) return rc;
+    if (int rc = mem.alloc(d_front, plan.max_cost2 + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mq, mq.data(), mq.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(SuboptSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(SuboptRec), st));
+    const unsigned nx = (unsigned)std::min((max_structs + SUBOPT_NT / 64 - 1) / (SUBOPT_NT / 64), 1024);
+    std::vector<SuboptRec> rec(max_seqs);
+    std::vector<char> rows;
+    std::vector<int> dc, perm;
+    std::string err = pk.first_err;
+    using clk = std::chrono::steady_clock;
+    auto us = [](clk::time_point a, clk::time_point b) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
+    g_subopt_counters[3] = (long long)plan.chunks.size();
+    for (const ChunkPlan::Range &c : plan.chunks) {
+        const int *ord = d_order + c.a;
+        const unsigned ny = (unsigned)(c.b - c.a);
+        int Lmax = 0;
+        for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, pk.L[order[k]]);
+        const clk::time_point t0 = clk::now();
+        if (int rc = mfe_fill_chunk(st, d_mq, ord, ny, Lmax, d_codes, d_ws)) return rc;
+        hipLaunchKernelGGL(subopt_init_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_f, d_front, d_rec);
+        HIPCHK(hipGetLastError());
+        int open = (int)ny;
+        HIPCHK(hipMemcpyAsync(d_open, &open, 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const clk::time_point t1 = clk::now();
+        g_subopt_counters[2] += Lmax + 1;
+        g_subopt_counters[5] += us(t0, t1);
+        // a step fixes a pair, an unpaired base or a split: fewer than 3 L + 8 of them lead to any structure
+        const int max_levels = 3 * Lmax + 8;
+        int level = 0;
+        while (open > 0) {
+            if (level > max_levels) return fail(RAFFT_ERR_HIP, "internal: the enumeration did not end after " + std::to_string(level) + " levels");
+            for (int r = 0; r < SUBOPT_POLL_LEVELS; r++, level++) {
+                const int src = level & 1;
+                hipLaunchKernelGGL(subopt_level_kernel<false>, dim3(nx, ny), dim3(SUBOPT_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_f, d_front, (int *)d_front, d_rec, src, delta);
+                hipLaunchKernelGGL(subopt_scan_kernel, dim3(ny), dim3(SUBOPT_SCAN_NT), 0, st, d_qs, ord, (int *)d_front, d_rec, src, max_structs, d_open);
+                hipLaunchKernelGGL(subopt_level_kernel<true>, dim3(nx, ny), dim3(SUBOPT_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_f, d_front, (int *)d_front, d_rec, src, delta);
+            }
+            HIPCHK(hipGetLastError());
+            g_subopt_counters[1] += 3 * SUBOPT_POLL_LEVELS;
+            HIPCHK(hipMemcpyAsync(&open, d_open, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        hipLaunchKernelGGL(subopt_pack_kernel, dim3(nx, ny), dim3(SUBOPT_NT), 0, st, d_qs, ord, d_front, d_rec);
+        HIPCHK(hipGetLastError());
+        g_subopt_counters[1] += 1;
+        // (the records of a chunk's sequences are not contiguous in d_rec: one copy each)
+        for (size_t k = c.a; k < c.b; k++) HIPCHK(hipMemcpyAsync(&rec[k - c.a], d_rec + order[k], sizeof(SuboptRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = order[k], L = pk.L[s];
+            const SuboptRec &r = rec[k - c.a];
+            rafft_subopt_seq &o = own->seq[s];
+            o.mfe_dcal = r.mfe;
+            g_subopt_counters[0] = std::max(g_subopt_counters[0], (long long)r.levels);
+            if (r.state == SUBOPT_BROKEN || r.state == SUBOPT_ACTIVE)
+                return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + (r.bad == SUBOPT_BAD_STACK ? ": the stack of pending segments is full"
+                                           : r.bad == SUBOPT_BAD_CELL ? ": a kept state has no candidate within the band" : ": the enumeration stopped early"));
+            if (r.state == SUBOPT_OVER) {
+                o.status = RAFFT_ERR_CAPACITY;
+                o.n_reached = r.n_reached;
+                n_failed++;
+                g_subopt_counters[4]++;
+                if (err.empty())
+                    err = "sequence " + std::to_string(s) + ": at least " + std::to_string(r.n_reached) + " structures within the band, max_structs is " + std::to_string(max_structs);
+                continue;
+            }
+            const int n = r.n[r.final_buf];
+            const size_t rb = (size_t)n * ((size_t)L + 1);
+            rows.resize(rb); dc.resize(n); perm.resize(n);
+            const unsigned char *src = d_front + qs[s].buf_off[r.final_buf ^ 1];
+            HIPCHK(hipMemcpy(rows.data(), src, rb, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(dc.data(), src + subopt_pack_dcal_off(n, L), (size_t)n * 4, hipMemcpyDeviceToHost));
+            for (int x = 0; x < n; x++) perm[x] = x;
+            std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return dc[a] < dc[b]; });
+            own->db[s].resize(rb); own->dcal[s].resize(n);
+            for (int x = 0; x < n; x++) {
+                memcpy(own->db[s].data() + (size_t)x * (L + 1), rows.data() + (size_t)perm[x] * (L + 1), (size_t)L + 1);
+                own->dcal[s][x] = dc[perm[x]];
+            }
+            o.n_structs = n;
+            o.db = own->db[s].data(); o.dcal = own->dcal[s].data();
+        }
+        g_subopt_counters[6] += us(t1, clk::now());
+    }
+    return finish(err);
 }
 
 } // namespace
