@@ -86,6 +86,7 @@ class SuboptResult(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_failed", C.c_int32), ("seq", C.POINTER(SuboptSeq)), ("_owner", C.c_void_p)]
 
 
+SUBOPT_MAX_LEN = MFE_MAX_LEN     # RAFFT_SUBOPT_MAX_LEN
 SUBOPT_MAX_STRUCTS = 1 << 24     # RAFFT_SUBOPT_MAX_STRUCTS
 SUBOPT_MAX_DELTA = 1000000       # RAFFT_SUBOPT_MAX_DELTA (dcal)
 

@@ -2,7 +2,9 @@
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
 // function and pair probabilities), sample_batch (structures drawn from the ensemble) and subopt_batch (every structure within an
 // energy band), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
-// pack, the solve order of a chunk - is in rafft_hostpure.h, where the CPU suite checks it.
+// pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
+// sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
+// the launches.  The sequence drivers share their opening (SeqCall) and their view of a chunk (ChunkView).
 // Part of the single translation unit of rafft_api.hip (included there, after rafft_seam.h, whose SeamGuard and DevScratch they use).
 #pragma once
 
@@ -162,9 +164,7 @@ int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *cons
     return 0;
 }
 
-// ---- minimum-free-energy folds (DESIGN.md section 9)
-
-constexpr size_t MFE_WORKSPACE = (size_t)512 << 20;
+// ---- what the four sequence drivers share
 
 // as the fold's entry (validate_params): before any sequence is looked at, so a batch of nothing but erroneous sequences fails too
 int check_temp(double temp)
@@ -182,13 +182,50 @@ void dot_row(char *db, int len)
     db[len] = 0;
 }
 
-// The HBM-class tables of a chunk of `ny` sequences (d_order: their numbers in d_qs; Lmax: the longest): one launch per
-// anti-diagonal, stream order being the synchronisation.  mfe_held and subopt_batch fill their tables through this.
-int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const int *d_order, unsigned ny, int Lmax, const uint8_t *d_codes, int *d_ws)
+// The opening of a call that has something to fold, in this order: the seam's entry, the device tables scaled for the call's temp,
+// the device copy of pk.codes in the caller's DevScratch (declared after the SeqCall, so that it is freed under the guard).
+struct SeqCall {
+    SeamGuard sg;
+    hipStream_t st = nullptr;
+    uint8_t *d_codes = nullptr;
+    int open(DevScratch &mem, const SeqPack &pk, double temp)
+    {
+        if (int rc = sg.enter()) return rc;
+        if (int rc = ensure_tables(temp)) return rc;
+        st = sg.stream;
+        if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
+        HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
+
+// chunk c of a plan over `order` (d_order: where the device copy of order[0] lies): its part of the order, its sequences, its longest
+struct ChunkView { const int *ord; unsigned ny; int Lmax; };
+ChunkView chunk_view(const ChunkPlan::Range &c, const int *d_order, const std::vector<int> &order, const SeqPack &pk)
 {
-    for (int d = 0; d < Lmax; d++) {
-        const unsigned nx = (unsigned)std::min((Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
-        hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, d_order, d_codes, d_ws, d);
+    return ChunkView{d_order + c.a, (unsigned)(c.b - c.a), chunk_lmax(c, order, pk.L)};
+}
+
+// Sequence s's scaled tables left the fp64 range, so no number of it is reported: its status, the call's first error if it has
+// none yet, and `bytes` zeros over what it was given for its numbers (zero may be null)
+void pf_left_range(int s, int &status, std::string &err, void *zero, size_t bytes)
+{
+    status = RAFFT_ERR_CAPACITY;
+    if (zero) memset(zero, 0, bytes);
+    if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
+}
+
+// ---- minimum-free-energy folds (DESIGN.md section 9)
+
+constexpr size_t MFE_WORKSPACE = (size_t)512 << 20;
+
+// The HBM-class tables of a chunk (its sequences' numbers in d_qs): one launch per anti-diagonal, stream order being the
+// synchronisation.  mfe_held and subopt_batch fill their tables through this.
+int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const ChunkView &v, const uint8_t *d_codes, int *d_ws)
+{
+    for (int d = 0; d < v.Lmax; d++) {
+        const unsigned nx = (unsigned)std::min((v.Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
+        hipLaunchKernelGGL(mfe_diag_kernel, dim3(nx, v.ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -196,62 +233,41 @@ int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const int *d_order, unsig
 
 // The MFE folds of a pack, under the caller's guard: the device tables are scaled for the call's temp, d_codes is the device copy
 // of pk.codes, seq_out[s].status is set.  Sequences up to `lds_len` go through mfe_lds_kernel in one launch, the others through
-// the HBM class in chunks whose tables fit the workspace budget (one sequence at least): per chunk one launch per anti-diagonal,
-// then the traceback.  One synchronise at the end; its device buffers are freed on return.  db_out may be null (no rows wanted).
+// the HBM class in chunks whose tables fit the workspace budget (one sequence at least; mfe_layout): per chunk one launch per
+// anti-diagonal, then the traceback.  One synchronise at the end; its device buffers are freed on return.  db_out may be null (no
+// rows wanted).
 int mfe_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, int lds_len, long long workspace_bytes, rafft_mfe_seq *seq_out, char *const *db_out)
 {
     const int n_seq = (int)pk.L.size();
-    std::vector<MfeSeq> qs(n_seq);
-    std::vector<int> lds_order, hbm_order;
-    unsigned long long n_stack = 0, n_db = 0;
-    for (int s = 0; s < n_seq; s++) {
-        const int len = pk.L[s];
-        qs[s] = MfeSeq{pk.code_off[s], 0, n_stack, n_db, len, 0};
-        if (!len) continue;
-        n_stack += (unsigned long long)len + 8; n_db += (unsigned long long)len + 1;
-        (len <= lds_len ? lds_order : hbm_order).push_back(s);
-    }
-    // the longest first: the workgroups of a launch that run last are the short ones
-    std::stable_sort(lds_order.begin(), lds_order.end(), [&](int a, int b) { return qs[a].L > qs[b].L; });
-    // chunks of the HBM class, in input order; a launch takes up to 65535 sequences (gridDim.y)
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE;
-    std::vector<size_t> tab_bytes(hbm_order.size());
-    for (size_t k = 0; k < hbm_order.size(); k++) tab_bytes[k] = 3 * (size_t)qs[hbm_order[k]].L * qs[hbm_order[k]].L * 4;
-    const ChunkPlan plan = plan_chunks(hbm_order.size(), tab_bytes.data(), nullptr, budget, 65535);
-    for (size_t k = 0; k < hbm_order.size(); k++) qs[hbm_order[k]].tab_off = plan.off[k] / 4;
-    const size_t ws_max = plan.max_cost;
+    const MfeLayout y = mfe_layout(pk, lds_len, workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE);
+    const std::vector<MfeSeq> &qs = y.qs;
     DevScratch mem;
     MfeSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr;
-    std::vector<int> order(lds_order);
-    order.insert(order.end(), hbm_order.begin(), hbm_order.end());
     if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSeq))) return rc;
-    if (int rc = mem.alloc(d_stack, n_stack * 4 + 16)) return rc;
-    if (int rc = mem.alloc(d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_stack, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_db, y.n_db + 16)) return rc;
     if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
-    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
-    if (ws_max) if (int rc = mem.alloc(d_ws, ws_max + 16)) return rc;
+    if (int rc = mem.alloc(d_order, y.order.size() * 4)) return rc;
+    if (y.plan.max_cost) if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
     HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, y.order.data(), y.order.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
-    if (!lds_order.empty()) {
+    if (!y.lds_order.empty()) {
         HIPCHK(hipFuncSetAttribute((const void *)mfe_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MFE_LDS_BYTES));
-        hipLaunchKernelGGL(mfe_lds_kernel, dim3((unsigned)lds_order.size()), dim3(MFE_LDS_NT), (size_t)mfe_lds_bytes(qs[lds_order[0]].L), st, g.T, d_qs, d_order,
+        hipLaunchKernelGGL(mfe_lds_kernel, dim3((unsigned)y.lds_order.size()), dim3(MFE_LDS_NT), (size_t)mfe_lds_bytes(qs[y.lds_order[0]].L), st, g.T, d_qs, d_order,
                            d_codes, d_stack, d_db, d_rec);
         HIPCHK(hipGetLastError());
     }
-    for (const ChunkPlan::Range &c : plan.chunks) {
-        const int *ord = d_order + lds_order.size() + c.a;
-        const unsigned ny = (unsigned)(c.b - c.a);
-        int Lmax = 0;
-        for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, qs[hbm_order[k]].L);
-        if (int rc = mfe_fill_chunk(st, d_qs, ord, ny, Lmax, d_codes, d_ws)) return rc;
-        hipLaunchKernelGGL(mfe_traceback_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_stack, d_db, d_rec);
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        const ChunkView v = chunk_view(c, d_order + y.lds_order.size(), y.hbm_order, pk);
+        if (int rc = mfe_fill_chunk(st, d_qs, v, d_codes, d_ws)) return rc;
+        hipLaunchKernelGGL(mfe_traceback_kernel, dim3(v.ny), dim3(64), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d_stack, d_db, d_rec);
         HIPCHK(hipGetLastError());
     }
     std::vector<int4> rec(n_seq);
-    std::vector<char> db(n_db + 16);
+    std::vector<char> db(y.n_db + 16);
     HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int s = 0; s < n_seq; s++) {
         if (seq_out[s].status) continue;
@@ -275,14 +291,10 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
     }
     g_err = pk.first_err;
     if (pk.fold.empty()) return 0;
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    if (int rc = ensure_tables(temp)) return rc;
+    SeqCall sc;
     DevScratch mem;
-    uint8_t *d_codes;
-    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
-    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, sg.stream));
-    if (int rc = mfe_held(sg.stream, pk, d_codes, lds_len, workspace_bytes, seq_out, db_out)) return rc;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    if (int rc = mfe_held(sc.st, pk, sc.d_codes, lds_len, workspace_bytes, seq_out, db_out)) return rc;
     g_err = pk.first_err;
     return 0;
 }
@@ -291,52 +303,43 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
 
 constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
 
-// The front rafft_pf_batch and rafft_sample_batch share, under the caller's guard: the device copy of the bases, the MFE of every
-// sequence (mfe_held: its energy gives the scale; its device buffers are freed before the tables here are allocated), the scales and
-// their powers, and the plan of chunks of whole sequences in input order whose `n_tabs` L x L fp64 tables - and, with cost2, a second
-// cost per sequence - fit the workspace budget (one sequence at least).  Then, per chunk, pf_front_inside: one launch per
-// anti-diagonal upwards and the exterior sums.  The buffers live in the caller's DevScratch.
+// The front rafft_pf_batch and rafft_sample_batch share, under the caller's SeqCall: the MFE of every sequence (mfe_held: its energy
+// gives the scale; its device buffers are freed before the tables here are allocated), the scales and their powers, and the plan of
+// chunks of whole sequences in input order whose `n_tabs` L x L fp64 tables - and, with cost2, a second cost per sequence - fit the
+// workspace budget (one sequence at least; pf_layout).  Then, per chunk, pf_front_inside: one launch per anti-diagonal upwards and
+// the exterior sums.  The buffers live in the caller's DevScratch.
 struct PfFront {
     double kt, beta;
     std::vector<rafft_mfe_seq> mfe;
     std::vector<PfSeq> qs;
     ChunkPlan plan;
     unsigned long long n_db = 0;
-    uint8_t *d_codes; PfSeq *d_qs; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
+    const uint8_t *d_codes; PfSeq *d_qs; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
 };
 
-int pf_front(hipStream_t st, DevScratch &mem, const SeqPack &pk, double temp, double scale_factor, long long workspace_bytes, int n_tabs,
+int pf_front(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp, double scale_factor, long long workspace_bytes, int n_tabs,
              const size_t *cost2, PfFront &f)
 {
     const int n_seq = (int)pk.L.size();
     const std::vector<int> &order = pk.fold;
+    hipStream_t st = sc.st;
+    f.d_codes = sc.d_codes;
     f.mfe.resize(n_seq);
     for (int s = 0; s < n_seq; s++) f.mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
-    if (int rc = mem.alloc(f.d_codes, pk.codes.size())) return rc;
-    HIPCHK(hipMemcpyAsync(f.d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
     if (int rc = mfe_held(st, pk, f.d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, f.mfe.data(), nullptr)) return rc;
     const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
     f.kt = kt; f.beta = beta;
-    std::vector<PfSeq> &qs = f.qs;
-    qs.resize(n_seq);
-    unsigned long long n_aux = 0, n_db = 0;
+    PfLayout y = pf_layout(pk, n_tabs, cost2, workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE);
     for (int s = 0; s < n_seq; s++) {
-        const int L = pk.L[s];
-        const double ln_scale = L ? -sf * ((double)f.mfe[s].dcal / 100.0) / (kt * (double)L) : 0.0;
-        const double scale = std::exp(ln_scale);
-        qs[s] = PfSeq{pk.code_off[s], 0, n_aux, n_db, L, f.mfe[s].dcal, scale, std::log(scale)};
-        if (!L) continue;
-        n_aux += 4 * ((unsigned long long)L + 1); n_db += (unsigned long long)L + 1;
+        PfSeq &q = y.qs[s];
+        const double ln_scale = q.L ? -sf * ((double)f.mfe[s].dcal / 100.0) / (kt * (double)q.L) : 0.0;
+        q.mfe_dcal = f.mfe[s].dcal; q.scale = std::exp(ln_scale); q.ln_scale = std::log(q.scale);
     }
-    f.n_db = n_db;
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE;
-    std::vector<size_t> tab_bytes(order.size());
-    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)n_tabs * qs[order[k]].L * qs[order[k]].L * sizeof(double);
-    f.plan = plan_chunks(order.size(), tab_bytes.data(), cost2, budget, 65535);                       // (gridDim.y, as mfe_held)
-    for (size_t k = 0; k < order.size(); k++) qs[order[k]].tab_off = f.plan.off[k] / sizeof(double);
+    f.qs = std::move(y.qs); f.plan = std::move(y.plan); f.n_db = y.n_db;
+    const std::vector<PfSeq> &qs = f.qs;
     if (int rc = mem.alloc(f.d_qs, qs.size() * sizeof(PfSeq))) return rc;
-    if (int rc = mem.alloc(f.d_aux, n_aux * sizeof(double) + 16)) return rc;
-    if (int rc = mem.alloc(f.d_db, n_db + 16)) return rc;
+    if (int rc = mem.alloc(f.d_aux, y.n_aux * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(f.d_db, y.n_db + 16)) return rc;
     if (int rc = mem.alloc(f.d_rec, qs.size() * sizeof(PfRec))) return rc;
     if (int rc = mem.alloc(f.d_order, order.size() * 4)) return rc;
     if (int rc = mem.alloc(f.d_ws, f.plan.max_cost + 16)) return rc;
@@ -351,17 +354,13 @@ int pf_front(hipStream_t st, DevScratch &mem, const SeqPack &pk, double temp, do
 // launches per anti-diagonal of a chunk whose longest sequence has Lmax positions: four cells per workgroup
 unsigned pf_diag_blocks(int Lmax, int d) { return (unsigned)std::min((Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); }
 
-// the inside tables and the exterior sums of chunk c; Lmax: the chunk's longest sequence
-int pf_front_inside(hipStream_t st, const SeqPack &pk, const PfFront &f, const ChunkPlan::Range &c, int &Lmax)
+// the inside tables and the exterior sums of chunk v
+int pf_front_inside(hipStream_t st, const PfFront &f, const ChunkView &v)
 {
-    const int *ord = f.d_order + c.a;
-    const unsigned ny = (unsigned)(c.b - c.a);
-    Lmax = 0;
-    for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, f.qs[pk.fold[k]].L);
-    for (int d = 0; d < Lmax; d++)
-        hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(Lmax, d), ny), dim3(PF_NT), 0, st, g.T, f.d_qs, ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
+    for (int d = 0; d < v.Lmax; d++)
+        hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(pf_exterior_kernel, dim3(ny), dim3(64), 0, st, g.T, f.d_qs, ord, f.d_codes, f.d_ws, f.d_aux, f.beta, f.kt, f.d_db, f.d_rec);
+    hipLaunchKernelGGL(pf_exterior_kernel, dim3(v.ny), dim3(64), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, f.kt, f.d_db, f.d_rec);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -384,24 +383,21 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
     g_err = pk.first_err;
     const std::vector<int> &order = pk.fold;
     if (order.empty()) return 0;
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    if (int rc = ensure_tables(temp)) return rc;
-    hipStream_t st = sg.stream;
+    SeqCall sc;
     DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
     PfFront f;
-    if (int rc = pf_front(st, mem, pk, temp, scale_factor, workspace_bytes, 6, nullptr, f)) return rc;
+    if (int rc = pf_front(sc, mem, pk, temp, scale_factor, workspace_bytes, 6, nullptr, f)) return rc;
     const std::vector<PfSeq> &qs = f.qs;
     for (int s = 0; s < n_seq; s++) seq_out[s].mfe_dcal = f.mfe[s].dcal;
     for (const ChunkPlan::Range &c : f.plan.chunks) {
-        const int *ord = f.d_order + c.a;
-        const unsigned ny = (unsigned)(c.b - c.a);
-        int Lmax;
-        if (int rc = pf_front_inside(st, pk, f, c, Lmax)) return rc;
-        for (int d = Lmax - 1; d >= 4; d--)
-            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(Lmax, d), ny), dim3(PF_NT), 0, st, g.T, f.d_qs, ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
+        const ChunkView v = chunk_view(c, f.d_order, order, pk);
+        if (int rc = pf_front_inside(st, f, v)) return rc;
+        for (int d = v.Lmax - 1; d >= 4; d--)
+            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(Lmax, 0), ny), dim3(PF_NT), 0, st, f.d_qs, ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
+        hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
         HIPCHK(hipGetLastError());
         if (prob_out)
             for (size_t k = c.a; k < c.b; k++) {
@@ -419,10 +415,7 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
     for (int s = 0; s < n_seq; s++) {
         if (seq_out[s].status) continue;
         if (rec[s].status || rec[s].bad) {
-            // the scaled tables left the fp64 range: no number of this sequence is reported
-            seq_out[s].status = RAFFT_ERR_CAPACITY;
-            if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)qs[s].L * qs[s].L * sizeof(double));
-            if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
+            pf_left_range(s, seq_out[s].status, err, prob_out ? prob_out[s] : nullptr, (size_t)qs[s].L * qs[s].L * sizeof(double));
             continue;
         }
         seq_out[s].n_pairs = rec[s].n_pairs;
@@ -437,83 +430,70 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
 // ---- structures drawn from the ensemble
 
 // rafft_sample_batch (arguments validated by the entry point).  The shared front with three tables a sequence - the inside tables
-// are all a stochastic traceback reads - and the rows of a chunk (n_samples (L + 1) bytes a sequence) as the planner's second cost.
-// Per chunk: the inside pass, sample_kernel over (groups of four samples, sequences), one synchronise, the rows and energies of the
-// sequences that passed the range check straight into the caller's buffers.
+// are all a stochastic traceback reads - and the rows of a chunk (n_samples (L + 1) bytes a sequence) as the planner's second cost
+// (sample_layout).  Per chunk: the inside pass, sample_kernel over (groups of four samples, sequences), one synchronise, the rows and
+// energies of the sequences that passed the range check straight into the caller's buffers.
 int sample_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, int n_samples,
                  const unsigned long long *seeds, rafft_sample_seq *seq_out, char *const *db_out, int *const *dcal_out)
 {
     if (int rc = check_temp(temp)) return rc;
     if (n_seq == 0) return 0;
     const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    auto dot_rows = [&](int s) { for (int k = 0; k < n_samples; k++) dot_row(db_out[s] + (size_t)k * ((size_t)pk.len[s] + 1), pk.len[s]); };
     for (int s = 0; s < n_seq; s++) {
         seq_out[s] = rafft_sample_seq{pk.status[s], pk.len[s], 0, 0, 0.0};
         if (!pk.status[s]) continue;
-        for (int k = 0; k < n_samples; k++) dot_row(db_out[s] + (size_t)k * ((size_t)pk.len[s] + 1), pk.len[s]);
+        dot_rows(s);
         if (dcal_out && dcal_out[s]) memset(dcal_out[s], 0, (size_t)n_samples * sizeof(int));
     }
     g_err = pk.first_err;
     const std::vector<int> &order = pk.fold;
     if (order.empty()) return 0;
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    if (int rc = ensure_tables(temp)) return rc;
-    hipStream_t st = sg.stream;
+    SeqCall sc;
     DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
     PfFront f;
-    std::vector<size_t> row_bytes(order.size());
-    for (size_t k = 0; k < order.size(); k++) row_bytes[k] = (size_t)n_samples * ((size_t)pk.L[order[k]] + 1);
-    if (int rc = pf_front(st, mem, pk, temp, scale_factor, workspace_bytes, 3, row_bytes.data(), f)) return rc;
+    const std::vector<size_t> row_costs = sample_row_costs(pk, n_samples);
+    if (int rc = pf_front(sc, mem, pk, temp, scale_factor, workspace_bytes, 3, row_costs.data(), f)) return rc;
     const std::vector<PfSeq> &qs = f.qs;
-    std::vector<SampleSeq> smp(n_seq, SampleSeq{0, 0, 0});
-    size_t max_seqs = 0;
-    for (const ChunkPlan::Range &c : f.plan.chunks) {
-        unsigned long long at = 0;
-        for (size_t k = c.a; k < c.b; k++) {
-            smp[order[k]] = SampleSeq{seeds ? seeds[order[k]] : 0ull, at, (unsigned long long)(k - c.a) * (unsigned long long)n_samples};
-            at += row_bytes[k];
-        }
-        max_seqs = std::max(max_seqs, c.b - c.a);
-    }
+    const SampleLayout y = sample_layout(pk, f.plan, n_samples, seeds);
     SampleSeq *d_smp; char *d_rows; int *d_dcal, *d_bad;
-    if (int rc = mem.alloc(d_smp, smp.size() * sizeof(SampleSeq))) return rc;
+    if (int rc = mem.alloc(d_smp, y.smp.size() * sizeof(SampleSeq))) return rc;
     if (int rc = mem.alloc(d_rows, f.plan.max_cost2 + 16)) return rc;
-    if (int rc = mem.alloc(d_dcal, max_seqs * (size_t)n_samples * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_dcal, y.max_seqs * (size_t)n_samples * 4 + 16)) return rc;
     if (int rc = mem.alloc(d_bad, (size_t)n_seq * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(d_smp, smp.data(), smp.size() * sizeof(SampleSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_smp, y.smp.data(), y.smp.size() * sizeof(SampleSeq), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_bad, 0, (size_t)n_seq * 4, st));
     std::vector<PfRec> rec(n_seq);
     std::vector<int> bad(n_seq);
     std::string err = pk.first_err;
     for (const ChunkPlan::Range &c : f.plan.chunks) {
-        int Lmax;
-        if (int rc = pf_front_inside(st, pk, f, c, Lmax)) return rc;
+        const ChunkView v = chunk_view(c, f.d_order, order, pk);
+        if (int rc = pf_front_inside(st, f, v)) return rc;
         if (n_samples > 0) {
-            hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n_samples + SAMPLE_NT / 64 - 1) / (SAMPLE_NT / 64)), (unsigned)(c.b - c.a)), dim3(SAMPLE_NT),
-                               (size_t)sample_lds_bytes(Lmax), st, g.T, f.d_qs, f.d_order + c.a, f.d_codes, f.d_ws, f.d_aux, f.beta, f.d_rec, d_smp, n_samples,
-                               Lmax, d_rows, d_dcal, d_bad);
+            hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n_samples + SAMPLE_NT / 64 - 1) / (SAMPLE_NT / 64)), v.ny), dim3(SAMPLE_NT),
+                               (size_t)sample_lds_bytes(v.Lmax), st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, f.d_rec, d_smp, n_samples,
+                               v.Lmax, d_rows, d_dcal, d_bad);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipMemcpyAsync(rec.data(), f.d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(bad.data(), d_bad, (size_t)n_seq * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         for (size_t k = c.a; k < c.b; k++) {
-            const int s = order[k], L = qs[s].L;
+            const int s = order[k];
             seq_out[s].mfe_dcal = f.mfe[s].dcal;
             if (bad[s]) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + (bad[s] == SAMPLE_BAD_STACK ? ": the sampling stack is full" : ": a sampled cell has no candidate"));
             if (rec[s].status) {
-                // the scaled tables left the fp64 range: nothing of this sequence is sampled
-                seq_out[s].status = RAFFT_ERR_CAPACITY;
-                for (int r = 0; r < n_samples; r++) dot_row(db_out[s] + (size_t)r * ((size_t)L + 1), L);
-                if (dcal_out && dcal_out[s]) memset(dcal_out[s], 0, (size_t)n_samples * sizeof(int));
-                if (err.empty()) err = "sequence " + std::to_string(s) + ": the scaled partition function left the fp64 range (another scale_factor may hold it)";
+                dot_rows(s);
+                pf_left_range(s, seq_out[s].status, err, dcal_out ? dcal_out[s] : nullptr, (size_t)n_samples * sizeof(int));
                 continue;
             }
             seq_out[s].energy = rec[s].energy;
             seq_out[s].n_samples = n_samples;
             if (n_samples == 0) continue;
-            HIPCHK(hipMemcpy(db_out[s], d_rows + smp[s].row_off, row_bytes[k], hipMemcpyDeviceToHost));
-            if (dcal_out && dcal_out[s]) HIPCHK(hipMemcpy(dcal_out[s], d_dcal + smp[s].dcal_off, (size_t)n_samples * sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(db_out[s], d_rows + y.smp[s].row_off, y.row_bytes[k], hipMemcpyDeviceToHost));
+            if (dcal_out && dcal_out[s]) HIPCHK(hipMemcpy(dcal_out[s], d_dcal + y.smp[s].dcal_off, (size_t)n_samples * sizeof(int), hipMemcpyDeviceToHost));
         }
     }
     g_err = err;
@@ -541,8 +521,9 @@ long long g_subopt_counters[7];
 // sequences in input order: three L x L int32 tables a sequence as the primary cost, its two frontier buffers of max_structs states
 // and its max_structs counts as the second.  Per chunk: the tables (mfe_fill_chunk), the exterior energies and the first state
 // (subopt_init_kernel), then levels of count / scan / emit until the word read back every SUBOPT_POLL_LEVELS levels says that no
-// sequence goes on; the finished states are packed on the device and copied.  The final order - a stable sort on dcal of rows that
-// arrive in enumeration order - is an index permutation on the host, applied while the result is filled.
+// sequence goes on; the finished states are packed on the device and copied.  Every offset is subopt_layout's.  The final order -
+// a stable sort on dcal of rows that arrive in enumeration order - is an index permutation on the host, applied while the result is
+// filled.
 int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int delta, int max_structs, long long workspace_bytes,
                  rafft_subopt_result **out)
 {
@@ -567,53 +548,29 @@ int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double tem
     };
     const std::vector<int> &order = pk.fold;
     if (order.empty()) return finish(pk.first_err);
-    SeamGuard sg;
-    if (int rc = sg.enter()) return rc;
-    if (int rc = ensure_tables(temp)) return rc;
-    hipStream_t st = sg.stream;
+    SeqCall sc;
     DevScratch mem;
-    // the plan
-    std::vector<MfeSeq> mq(n_seq, MfeSeq{0, 0, 0, 0, 0, 0});
-    std::vector<SuboptSeq> qs(n_seq, SuboptSeq{0, 0, 0, {0, 0}, 0, 0, 0});
-    std::vector<size_t> tab_bytes(order.size()), front_bytes(order.size());
-    unsigned long long n_f = 0;
-    for (size_t k = 0; k < order.size(); k++) {
-        const int L = pk.L[order[k]];
-        tab_bytes[k] = 3 * (size_t)L * L * 4;
-        front_bytes[k] = 2 * (size_t)max_structs * (size_t)subopt_state_bytes(L) + (((size_t)max_structs * 4 + 255) & ~(size_t)255);
-    }
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : SUBOPT_WORKSPACE;
-    const ChunkPlan plan = plan_chunks(order.size(), tab_bytes.data(), front_bytes.data(), budget, 65535);
-    size_t max_seqs = 0;
-    for (const ChunkPlan::Range &c : plan.chunks) {
-        size_t at = 0;
-        for (size_t k = c.a; k < c.b; k++) {
-            const int s = order[k], L = pk.L[s];
-            const size_t one = (size_t)max_structs * (size_t)subopt_state_bytes(L);
-            mq[s] = MfeSeq{pk.code_off[s], plan.off[k] / 4, 0, 0, L, 0};
-            qs[s] = SuboptSeq{pk.code_off[s], plan.off[k] / 4, n_f, {at, at + one}, (at + 2 * one) / 4, L, 0};
-            n_f += (unsigned long long)L + 1;
-            at += front_bytes[k];
-        }
-        max_seqs = std::max(max_seqs, c.b - c.a);
-    }
-    uint8_t *d_codes; MfeSeq *d_mq; SuboptSeq *d_qs; SuboptRec *d_rec; int *d_order, *d_ws, *d_f, *d_open; unsigned char *d_front;
-    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
-    if (int rc = mem.alloc(d_mq, mq.size() * sizeof(MfeSeq))) return rc;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    const uint8_t *d_codes = sc.d_codes;
+    const SuboptLayout y = subopt_layout(pk, max_structs, workspace_bytes > 0 ? (size_t)workspace_bytes : SUBOPT_WORKSPACE);
+    const std::vector<SuboptSeq> &qs = y.qs;
+    const ChunkPlan &plan = y.plan;
+    MfeSeq *d_mq; SuboptSeq *d_qs; SuboptRec *d_rec; int *d_order, *d_ws, *d_f, *d_open; unsigned char *d_front;
+    if (int rc = mem.alloc(d_mq, y.mq.size() * sizeof(MfeSeq))) return rc;
     if (int rc = mem.alloc(d_qs, qs.size() * sizeof(SuboptSeq))) return rc;
     if (int rc = mem.alloc(d_rec, qs.size() * sizeof(SuboptRec))) return rc;
     if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
-    if (int rc = mem.alloc(d_f, n_f * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_f, y.n_f * 4 + 16)) return rc;
     if (int rc = mem.alloc(d_open, 16)) return rc;
     if (int rc = mem.alloc(d_ws, plan.max_cost + 16)) return rc;
     if (int rc = mem.alloc(d_front, plan.max_cost2 + 16)) return rc;
-    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_mq, mq.data(), mq.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mq, y.mq.data(), y.mq.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(SuboptSeq), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(SuboptRec), st));
     const unsigned nx = (unsigned)std::min((max_structs + SUBOPT_NT / 64 - 1) / (SUBOPT_NT / 64), 1024);
-    std::vector<SuboptRec> rec(max_seqs);
+    std::vector<SuboptRec> rec(y.max_seqs);
     std::vector<char> rows;
     std::vector<int> dc, perm;
     std::string err = pk.first_err;
@@ -621,37 +578,34 @@ int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double tem
     auto us = [](clk::time_point a, clk::time_point b) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
     g_subopt_counters[3] = (long long)plan.chunks.size();
     for (const ChunkPlan::Range &c : plan.chunks) {
-        const int *ord = d_order + c.a;
-        const unsigned ny = (unsigned)(c.b - c.a);
-        int Lmax = 0;
-        for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, pk.L[order[k]]);
+        const ChunkView v = chunk_view(c, d_order, order, pk);
         const clk::time_point t0 = clk::now();
-        if (int rc = mfe_fill_chunk(st, d_mq, ord, ny, Lmax, d_codes, d_ws)) return rc;
-        hipLaunchKernelGGL(subopt_init_kernel, dim3(ny), dim3(64), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_f, d_front, d_rec);
+        if (int rc = mfe_fill_chunk(st, d_mq, v, d_codes, d_ws)) return rc;
+        hipLaunchKernelGGL(subopt_init_kernel, dim3(v.ny), dim3(64), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d_f, d_front, d_rec);
         HIPCHK(hipGetLastError());
-        int open = (int)ny;
+        int open = (int)v.ny;
         HIPCHK(hipMemcpyAsync(d_open, &open, 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
         const clk::time_point t1 = clk::now();
-        g_subopt_counters[2] += Lmax + 1;
+        g_subopt_counters[2] += v.Lmax + 1;
         g_subopt_counters[5] += us(t0, t1);
         // a step fixes a pair, an unpaired base or a split: fewer than 3 L + 8 of them lead to any structure
-        const int max_levels = 3 * Lmax + 8;
+        const int max_levels = 3 * v.Lmax + 8;
         int level = 0;
         while (open > 0) {
             if (level > max_levels) return fail(RAFFT_ERR_HIP, "internal: the enumeration did not end after " + std::to_string(level) + " levels");
             for (int r = 0; r < SUBOPT_POLL_LEVELS; r++, level++) {
                 const int src = level & 1;
-                hipLaunchKernelGGL(subopt_level_kernel<false>, dim3(nx, ny), dim3(SUBOPT_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_f, d_front, (int *)d_front, d_rec, src, delta);
-                hipLaunchKernelGGL(subopt_scan_kernel, dim3(ny), dim3(SUBOPT_SCAN_NT), 0, st, d_qs, ord, (int *)d_front, d_rec, src, max_structs, d_open);
-                hipLaunchKernelGGL(subopt_level_kernel<true>, dim3(nx, ny), dim3(SUBOPT_NT), 0, st, g.T, d_qs, ord, d_codes, d_ws, d_f, d_front, (int *)d_front, d_rec, src, delta);
+                hipLaunchKernelGGL(subopt_level_kernel<false>, dim3(nx, v.ny), dim3(SUBOPT_NT), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d_f, d_front, (int *)d_front, d_rec, src, delta);
+                hipLaunchKernelGGL(subopt_scan_kernel, dim3(v.ny), dim3(SUBOPT_SCAN_NT), 0, st, d_qs, v.ord, (int *)d_front, d_rec, src, max_structs, d_open);
+                hipLaunchKernelGGL(subopt_level_kernel<true>, dim3(nx, v.ny), dim3(SUBOPT_NT), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d_f, d_front, (int *)d_front, d_rec, src, delta);
             }
             HIPCHK(hipGetLastError());
             g_subopt_counters[1] += 3 * SUBOPT_POLL_LEVELS;
             HIPCHK(hipMemcpyAsync(&open, d_open, 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
         }
-        hipLaunchKernelGGL(subopt_pack_kernel, dim3(nx, ny), dim3(SUBOPT_NT), 0, st, d_qs, ord, d_front, d_rec);
+        hipLaunchKernelGGL(subopt_pack_kernel, dim3(nx, v.ny), dim3(SUBOPT_NT), 0, st, d_qs, v.ord, d_front, d_rec);
         HIPCHK(hipGetLastError());
         g_subopt_counters[1] += 1;
         // (the records of a chunk's sequences are not contiguous in d_rec: one copy each)

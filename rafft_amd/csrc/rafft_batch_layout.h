@@ -1,0 +1,82 @@
+// rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
+// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip and rafft_subopt.hip read and write, and the sizes both sides compute (the LDS
+// of the MFE and sampling kernels, a state of the enumeration, its packed copy).  The layouts that fill the records are in
+// rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
+#pragma once
+
+#ifdef __HIPCC__
+#define RAFFT_HD __host__ __device__
+#else
+#define RAFFT_HD
+#endif
+
+// ---- minimum-free-energy folds (rafft_mfe.hip)
+
+#define MFE_LDS_BYTES (128 << 10)
+// LDS class: three triangular int32 tables of L (L + 1) / 2 cells, F (L + 1 ints) and the bases (L bytes, padded to 16) in 128 KiB
+#define RAFFT_MFE_LDS_LEN 146
+RAFFT_HD constexpr int mfe_lds_bytes(int L) { return (3 * (L * (L + 1) / 2) + L + 1) * 4 + ((L + 15) & ~15); }
+static_assert(mfe_lds_bytes(RAFFT_MFE_LDS_LEN) <= MFE_LDS_BYTES && mfe_lds_bytes(RAFFT_MFE_LDS_LEN + 1) > MFE_LDS_BYTES, "RAFFT_MFE_LDS_LEN is what 128 KiB hold");
+
+struct MfeSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long tab_off;     // HBM class: first int of the sequence's three L x L tables in the workspace
+    unsigned long long stack_off;   // first word of its traceback stack (L + 8 words)
+    unsigned long long db_off;      // its row in the output (L + 1 bytes)
+    int L, pad;
+};
+
+// ---- partition function and pair probabilities (rafft_pf.hip)
+
+struct PfSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long tab_off;     // first double of the sequence's six L x L tables in the workspace
+    unsigned long long aux_off;     // first double of ps, pb, F, Fr (L + 1 each)
+    unsigned long long db_off;      // its row in the output (L + 1 bytes)
+    int L, mfe_dcal;
+    double scale, ln_scale;
+};
+struct PfRec {
+    int status, n_pairs, bad, pad;  // bad: a probability that is not finite
+    double energy, mfe_frequency;
+};
+
+// ---- structures drawn from the ensemble (rafft_sample.hip)
+
+#define SAMPLE_NT 256               // four wavefronts: four samples of one sequence per workgroup
+#define RAFFT_SAMPLE_STACK(L) ((L) / 5 + 2)
+
+struct SampleSeq {
+    unsigned long long seed;
+    unsigned long long row_off;     // first byte of the sequence's n_samples rows (L + 1 bytes each) in the chunk's row buffer
+    unsigned long long dcal_off;    // first int of its n_samples energies
+};
+
+// a row (L + 1 bytes, padded to 16) and a stack of pending segments, as the sampling kernel's waves and the enumeration's states hold them
+RAFFT_HD constexpr int row_bytes16(int L) { return (L + 1 + 15) & ~15; }
+RAFFT_HD constexpr int seg_stack_words(int L) { return (RAFFT_SAMPLE_STACK(L) + 3) & ~3; }
+// per-wave LDS of the sampling kernel for the longest sequence of a launch: the row and the stack
+RAFFT_HD constexpr int sample_lds_bytes(int L) { return (SAMPLE_NT / 64) * (row_bytes16(L) + 4 * seg_stack_words(L)); }
+
+// ---- every structure within an energy band (rafft_subopt.hip)
+
+// a state of a sequence of L: e_fixed, e_pending, the number of pending segments, a spare word; the stack; the row and its NUL
+RAFFT_HD constexpr int subopt_state_bytes(int L) { return 16 + 4 * seg_stack_words(L) + row_bytes16(L); }
+
+struct SuboptSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long tab_off;     // first int of the sequence's three L x L tables in the table workspace
+    unsigned long long f_off;       // first int of its exterior energies (L + 1)
+    unsigned long long buf_off[2];  // first byte of its two frontier buffers (max_structs states each)
+    unsigned long long cnt_off;     // first int of its counts / offsets (max_structs)
+    int L, pad;
+};
+struct SuboptRec {
+    int n[2];                       // states in buffer 0 / 1
+    int state, bad;                 // SUBOPT_*; SUBOPT_BAD_*
+    int final_buf, levels, mfe, pad;
+    long long n_reached;
+};
+
+// the packed copy of n finished states, in the buffer that is not the final one: n rows of L + 1 bytes, then at this offset n energies
+RAFFT_HD inline unsigned long long subopt_pack_dcal_off(int n, int L) { return ((unsigned long long)n * (unsigned long long)(L + 1) + 15ull) & ~15ull; }

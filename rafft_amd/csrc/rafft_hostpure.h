@@ -1,10 +1,12 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
 // that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
-// (chunks within a budget, the sequence pack, the graph pack, the solve order).  Plain C++ (g++ compiles it alone:
+// (chunks within a budget, the sequence pack, the graph pack, the solve order, and the layouts of the four sequence drivers: every
+// offset their kernels dereference, as records of rafft_batch_layout.h).  Plain C++ (g++ compiles it alone:
 // tests/hostcheck/hostpure_check.cpp).  Part of the single translation unit of rafft_api.hip (included there, before the kernels).
 #pragma once
 
 #include "../../include/rafft_hip.h"
+#include "rafft_batch_layout.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -240,6 +242,146 @@ static SeqPack pack_sequences(int n_seq, const char *const *seqs, const int *len
     for (int s : p.fold)
         for (int x = 0; x < p.L[s]; x++) p.codes[p.code_off[s] + x] = (uint8_t)(kBaseCode[(unsigned char)seqs[s][x]] & 7);
     return p;
+}
+
+// ---- layouts of the sequence drivers: from a pack, the call's parameters and the workspace budget to the records the kernels read.
+// A sequence with an error (L 0) takes no room anywhere.  Chunks hold up to 65535 sequences (gridDim.y of a launch).
+
+// the longest of the sequences order[a .. b) of a chunk
+static int chunk_lmax(const ChunkPlan::Range &c, const std::vector<int> &order, const std::vector<int> &L)
+{
+    int Lmax = 0;
+    for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, L[order[k]]);
+    return Lmax;
+}
+
+// rafft_mfe_batch: sequences up to lds_len in the LDS class, the longest first (the workgroups of a launch that run last are the
+// short ones), the others in the HBM class in input order, in chunks (plan: over hbm_order) of three L x L int32 tables a sequence;
+// order: the LDS class, then the HBM class.  n_stack words of traceback stacks, n_db bytes of rows.
+struct MfeLayout {
+    std::vector<MfeSeq> qs;
+    std::vector<int> lds_order, hbm_order, order;
+    ChunkPlan plan;
+    unsigned long long n_stack = 0, n_db = 0;
+};
+static MfeLayout mfe_layout(const SeqPack &pk, int lds_len, size_t budget)
+{
+    MfeLayout y;
+    const int n_seq = (int)pk.L.size();
+    y.qs.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.L[s];
+        y.qs[s] = MfeSeq{pk.code_off[s], 0, y.n_stack, y.n_db, len, 0};
+        if (!len) continue;
+        y.n_stack += (unsigned long long)len + 8; y.n_db += (unsigned long long)len + 1;
+        (len <= lds_len ? y.lds_order : y.hbm_order).push_back(s);
+    }
+    std::stable_sort(y.lds_order.begin(), y.lds_order.end(), [&](int a, int b) { return pk.L[a] > pk.L[b]; });
+    std::vector<size_t> tab_bytes(y.hbm_order.size());
+    for (size_t k = 0; k < y.hbm_order.size(); k++) tab_bytes[k] = 3 * (size_t)pk.L[y.hbm_order[k]] * pk.L[y.hbm_order[k]] * 4;
+    y.plan = plan_chunks(y.hbm_order.size(), tab_bytes.data(), nullptr, budget, 65535);
+    for (size_t k = 0; k < y.hbm_order.size(); k++) y.qs[y.hbm_order[k]].tab_off = y.plan.off[k] / 4;
+    y.order = y.lds_order;
+    y.order.insert(y.order.end(), y.hbm_order.begin(), y.hbm_order.end());
+    return y;
+}
+
+// rafft_pf_batch / rafft_sample_batch: chunks (plan: over pk.fold) of n_tabs L x L fp64 tables a sequence and, with cost2, a second
+// cost per sequence.  n_aux doubles of ps, pb, F, Fr, n_db bytes of rows.  mfe_dcal, scale and ln_scale of qs are left 0: they
+// need the MFE, which the driver gets from the device.
+struct PfLayout {
+    std::vector<PfSeq> qs;
+    ChunkPlan plan;
+    unsigned long long n_aux = 0, n_db = 0;
+};
+static PfLayout pf_layout(const SeqPack &pk, int n_tabs, const size_t *cost2, size_t budget)
+{
+    PfLayout y;
+    const int n_seq = (int)pk.L.size();
+    y.qs.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) {
+        const int L = pk.L[s];
+        y.qs[s] = PfSeq{pk.code_off[s], 0, y.n_aux, y.n_db, L, 0, 0.0, 0.0};
+        if (!L) continue;
+        y.n_aux += 4 * ((unsigned long long)L + 1); y.n_db += (unsigned long long)L + 1;
+    }
+    const std::vector<int> &order = pk.fold;
+    std::vector<size_t> tab_bytes(order.size());
+    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)n_tabs * pk.L[order[k]] * pk.L[order[k]] * sizeof(double);
+    y.plan = plan_chunks(order.size(), tab_bytes.data(), cost2, budget, 65535);
+    for (size_t k = 0; k < order.size(); k++) y.qs[order[k]].tab_off = y.plan.off[k] / sizeof(double);
+    return y;
+}
+
+// rafft_sample_batch.  The rows of pk.fold[k], n_samples of L + 1 bytes: the second cost of its plan
+static std::vector<size_t> sample_row_costs(const SeqPack &pk, int n_samples)
+{
+    std::vector<size_t> row_bytes(pk.fold.size());
+    for (size_t k = 0; k < pk.fold.size(); k++) row_bytes[k] = (size_t)n_samples * ((size_t)pk.L[pk.fold[k]] + 1);
+    return row_bytes;
+}
+// ... and, the plan being made: per chunk the rows back to back from byte 0 of the row buffer, the energies of the chunk's k-th
+// sequence from int k n_samples; max_seqs: the sequences of the largest chunk.  seeds may be null (every seed 0).
+struct SampleLayout {
+    std::vector<size_t> row_bytes;
+    std::vector<SampleSeq> smp;
+    size_t max_seqs = 0;
+};
+static SampleLayout sample_layout(const SeqPack &pk, const ChunkPlan &plan, int n_samples, const unsigned long long *seeds)
+{
+    SampleLayout y;
+    y.row_bytes = sample_row_costs(pk, n_samples);
+    y.smp.assign(pk.L.size(), SampleSeq{0, 0, 0});
+    for (const ChunkPlan::Range &c : plan.chunks) {
+        unsigned long long at = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = pk.fold[k];
+            y.smp[s] = SampleSeq{seeds ? seeds[s] : 0ull, at, (unsigned long long)(k - c.a) * (unsigned long long)n_samples};
+            at += y.row_bytes[k];
+        }
+        y.max_seqs = std::max(y.max_seqs, c.b - c.a);
+    }
+    return y;
+}
+
+// rafft_subopt_batch: chunks (plan: over pk.fold) of three L x L int32 tables a sequence as the primary cost, its two frontier
+// buffers of max_structs states and its max_structs counts (rounded up to 256 bytes) as the second.  Per chunk the frontiers back to
+// back from byte 0 of the frontier buffer; n_f ints of exterior energies over the whole call.  mq: what mfe_diag_kernel reads of a
+// sequence (code_off, tab_off, L), for the table fill the enumeration shares with the MFE.
+struct SuboptLayout {
+    std::vector<size_t> tab_bytes, front_bytes;
+    ChunkPlan plan;
+    std::vector<SuboptSeq> qs;
+    std::vector<MfeSeq> mq;
+    unsigned long long n_f = 0;
+    size_t max_seqs = 0;
+};
+static SuboptLayout subopt_layout(const SeqPack &pk, int max_structs, size_t budget)
+{
+    SuboptLayout y;
+    const std::vector<int> &order = pk.fold;
+    y.tab_bytes.resize(order.size()); y.front_bytes.resize(order.size());
+    for (size_t k = 0; k < order.size(); k++) {
+        const int L = pk.L[order[k]];
+        y.tab_bytes[k] = 3 * (size_t)L * L * 4;
+        y.front_bytes[k] = 2 * (size_t)max_structs * (size_t)subopt_state_bytes(L) + (((size_t)max_structs * 4 + 255) & ~(size_t)255);
+    }
+    y.plan = plan_chunks(order.size(), y.tab_bytes.data(), y.front_bytes.data(), budget, 65535);
+    y.qs.assign(pk.L.size(), SuboptSeq{0, 0, 0, {0, 0}, 0, 0, 0});
+    y.mq.assign(pk.L.size(), MfeSeq{0, 0, 0, 0, 0, 0});
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        size_t at = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = order[k], L = pk.L[s];
+            const size_t one = (size_t)max_structs * (size_t)subopt_state_bytes(L);
+            y.mq[s] = MfeSeq{pk.code_off[s], y.plan.off[k] / 4, 0, 0, L, 0};
+            y.qs[s] = SuboptSeq{pk.code_off[s], y.plan.off[k] / 4, y.n_f, {at, at + one}, (at + 2 * one) / 4, L, 0};
+            y.n_f += (unsigned long long)L + 1;
+            at += y.front_bytes[k];
+        }
+        y.max_seqs = std::max(y.max_seqs, c.b - c.a);
+    }
+    return y;
 }
 
 // the step a step of a folding graph is compared with: the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)

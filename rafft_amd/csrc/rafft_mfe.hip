@@ -17,17 +17,14 @@
 // is the synchronisation; mfe_traceback_kernel).
 #pragma once
 
+#include "rafft_batch_layout.h"     // MfeSeq, RAFFT_MFE_LDS_LEN, MFE_LDS_BYTES, mfe_lds_bytes
+
 #define MFE_INF 1000000000          // "no structure"; two of them still add up inside an int
 #define MFE_INFH 500000000          // every real energy lies below, every sum with an MFE_INF above
 #define MFE_MAXLOOP 30              // unpaired positions of an interior loop (RNA.fold's default)
 #define MFE_NIL 496                 // pairs (n1, n2) with n1 + n2 <= 30
 #define MFE_LDS_NT 512
 #define MFE_HBM_NT 256
-#define MFE_LDS_BYTES (128 << 10)
-// LDS class: three triangular int32 tables of L (L + 1) / 2 cells, F (L + 1 ints) and the bases (L bytes, padded to 16) in 128 KiB
-#define RAFFT_MFE_LDS_LEN 146
-__host__ __device__ constexpr int mfe_lds_bytes(int L) { return (3 * (L * (L + 1) / 2) + L + 1) * 4 + ((L + 15) & ~15); }
-static_assert(mfe_lds_bytes(RAFFT_MFE_LDS_LEN) <= MFE_LDS_BYTES && mfe_lds_bytes(RAFFT_MFE_LDS_LEN + 1) > MFE_LDS_BYTES, "RAFFT_MFE_LDS_LEN is what 128 KiB hold");
 
 // (n1 << 8 | n2) of interior-loop candidate x: n1 ascending, then n2 ascending - p ascending, then q descending
 struct MfeIlTable {
@@ -40,14 +37,6 @@ struct MfeIlTable {
     }
 };
 __constant__ MfeIlTable mfe_il = MfeIlTable();
-
-struct MfeSeq {
-    unsigned long long code_off;    // bases in `codes`
-    unsigned long long tab_off;     // HBM class: first int of the sequence's three L x L tables in the workspace
-    unsigned long long stack_off;   // first word of its traceback stack (L + 8 words)
-    unsigned long long db_off;      // its row in the output (L + 1 bytes)
-    int L, pad;
-};
 
 // table views: c / m / m1 are cell (i, j), i <= j.  The split loops read M along a row (k - 1 varies) and M1 along a column
 // (k varies), so M is stored by rows and M1 by columns: the 64 lanes of a split read 64 consecutive words of each.

@@ -27,22 +27,11 @@
 // one wavefront per cell, candidates over the 64 lanes, summed by a butterfly of fixed order.
 #pragma once
 
+#include "rafft_batch_layout.h"     // PfSeq, PfRec
+
 #define PF_NT 256
 #define PF_GAS 1.98717e-3           // kcal / (mol K)
 #define PF_NCLOSE 175               // (pair type, base before the 3' end, base after the 5' end) of a closing pair
-
-struct PfSeq {
-    unsigned long long code_off;    // bases in `codes`
-    unsigned long long tab_off;     // first double of the sequence's six L x L tables in the workspace
-    unsigned long long aux_off;     // first double of ps, pb, F, Fr (L + 1 each)
-    unsigned long long db_off;      // its row in the output (L + 1 bytes)
-    int L, mfe_dcal;
-    double scale, ln_scale;
-};
-struct PfRec {
-    int status, n_pairs, bad, pad;  // bad: a probability that is not finite
-    double energy, mfe_frequency;
-};
 
 // C, M and their outside twins by rows, M1 and M1o by columns (as MfeTabHbm)
 struct PfTab {

@@ -25,20 +25,8 @@
 #pragma once
 
 #include "rafft_rng.h"
+#include "rafft_batch_layout.h"     // SampleSeq, SAMPLE_NT, RAFFT_SAMPLE_STACK, row_bytes16, seg_stack_words, sample_lds_bytes
 
-#define SAMPLE_NT 256               // four wavefronts: four samples of one sequence per workgroup
-#define RAFFT_SAMPLE_STACK(L) ((L) / 5 + 2)
-
-struct SampleSeq {
-    unsigned long long seed;
-    unsigned long long row_off;     // first byte of the sequence's n_samples rows (L + 1 bytes each) in the chunk's row buffer
-    unsigned long long dcal_off;    // first int of its n_samples energies
-};
-
-// per-wave LDS of the sampling kernel for the longest sequence of a launch: the row (L + 1 bytes, padded to 16) and the stack
-__host__ __device__ constexpr int sample_row_bytes(int L) { return (L + 1 + 15) & ~15; }
-__host__ __device__ constexpr int sample_stack_words(int L) { return (RAFFT_SAMPLE_STACK(L) + 3) & ~3; }
-__host__ __device__ constexpr int sample_lds_bytes(int L) { return (SAMPLE_NT / 64) * (sample_row_bytes(L) + 4 * sample_stack_words(L)); }
 static_assert(sample_lds_bytes(RAFFT_MFE_MAX_LEN) <= 64 << 10, "the sampling kernel's LDS fits the default limit");
 
 // inclusive sum over the lanes of a wavefront (all of them active), partner distance 1 .. 32: lane l holds x[0] + ... + x[l], every
@@ -142,8 +130,8 @@ __global__ __launch_bounds__(SAMPLE_NT) void sample_kernel(const EnergyTables *E
     const BigT *B = &ET->b;
     const uint8_t *S = codes + q.code_off;
     const double *ps = aux + q.aux_off, *pb = ps + L + 1, *F = pb + L + 1;      // F[x]: exterior sum of 0..x-1
-    unsigned char *row = sample_lds + (size_t)wave * (sample_row_bytes(lds_len) + 4 * sample_stack_words(lds_len));
-    uint32_t *stack = (uint32_t *)(row + sample_row_bytes(lds_len));
+    unsigned char *row = sample_lds + (size_t)wave * (row_bytes16(lds_len) + 4 * seg_stack_words(lds_len));
+    uint32_t *stack = (uint32_t *)(row + row_bytes16(lds_len));
     const int cap = RAFFT_SAMPLE_STACK(L), mlb = T->ml_base;
     for (int x = lane; x < L; x += 64) row[x] = '.';
     if (lane == 0) row[L] = 0;

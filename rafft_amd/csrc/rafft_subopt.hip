@@ -23,6 +23,8 @@
 // states of a sequence are its structures in the left-to-right order of the leaves of the decision tree.
 #pragma once
 
+#include "rafft_batch_layout.h"     // SuboptSeq, SuboptRec, subopt_state_bytes, seg_stack_words, subopt_pack_dcal_off
+
 #define SUBOPT_NT 256               // four wavefronts: four states per workgroup and round
 #define SUBOPT_SCAN_NT 1024
 #define SUBOPT_SCAN_ITEMS 4
@@ -30,26 +32,6 @@
 enum { SUBOPT_K_F = 3 };            // beside MFE_K_C, MFE_K_M, MFE_K_M1: the exterior loop of 0..j
 enum { SUBOPT_ACTIVE = 0, SUBOPT_DONE = 1, SUBOPT_OVER = 2, SUBOPT_BROKEN = 3 };
 enum { SUBOPT_BAD_STACK = 1, SUBOPT_BAD_CELL = 2 };
-
-// a state of a sequence of L: e_fixed, e_pending, the number of pending segments, a spare word; the stack; the row and its NUL
-__host__ __device__ constexpr int subopt_stack_words(int L) { return (RAFFT_SAMPLE_STACK(L) + 3) & ~3; }
-__host__ __device__ constexpr int subopt_row_bytes(int L) { return (L + 1 + 15) & ~15; }
-__host__ __device__ constexpr int subopt_state_bytes(int L) { return 16 + 4 * subopt_stack_words(L) + subopt_row_bytes(L); }
-
-struct SuboptSeq {
-    unsigned long long code_off;    // bases in `codes`
-    unsigned long long tab_off;     // first int of the sequence's three L x L tables in the table workspace
-    unsigned long long f_off;       // first int of its exterior energies (L + 1)
-    unsigned long long buf_off[2];  // first byte of its two frontier buffers (max_structs states each)
-    unsigned long long cnt_off;     // first int of its counts / offsets (max_structs)
-    int L, pad;
-};
-struct SuboptRec {
-    int n[2];                       // states in buffer 0 / 1
-    int state, bad;                 // SUBOPT_*; SUBOPT_BAD_*
-    int final_buf, levels, mfe, pad;
-    long long n_reached;
-};
 
 struct SuboptCand { int e, pend; uint32_t w1, w2; };     // loop terms fixed; table minima of what is pushed; the pushes, in order
 struct SuboptCtx {
@@ -162,7 +144,7 @@ __global__ __launch_bounds__(64) void subopt_init_kernel(const EnergyTables *ET,
         wave_sync();
     }
     for (int x = lane; x <= L; x += 64) Fg[q.f_off + x] = F[x];
-    const int words = subopt_state_bytes(L) / 4, rw0 = 4 + subopt_stack_words(L);
+    const int words = subopt_state_bytes(L) / 4, rw0 = 4 + seg_stack_words(L);
     uint32_t *st = (uint32_t *)(front + q.buf_off[0]);
     const uint32_t first = subopt_f_word(L - 1);
     for (int x = lane; x < words; x += 64) {
@@ -199,7 +181,7 @@ __global__ __launch_bounds__(SUBOPT_NT) void subopt_level_kernel(const EnergyTab
     int *t0 = tabs + q.tab_off;
     const size_t LL = (size_t)L * L;
     const SuboptCtx cx{MfeTabHbm{t0, t0 + LL, t0 + 2 * LL, L}, &ET->s, &ET->b, codes + q.code_off, Fg + q.f_off, L};
-    const int words = subopt_state_bytes(L) / 4, rw0 = 4 + subopt_stack_words(L), cap = RAFFT_SAMPLE_STACK(L);
+    const int words = subopt_state_bytes(L) / 4, rw0 = 4 + seg_stack_words(L), cap = RAFFT_SAMPLE_STACK(L);
     const uint32_t *in = (const uint32_t *)(front + q.buf_off[src]);
     uint32_t *out = (uint32_t *)(front + q.buf_off[src ^ 1]);
     int *cn = cnt + q.cnt_off;
@@ -334,14 +316,13 @@ __global__ __launch_bounds__(SUBOPT_SCAN_NT) void subopt_scan_kernel(const Subop
 
 // The finished states of a sequence, packed for the copy to the host: rows (L + 1 bytes apart) from byte 0 of the buffer the last
 // level did not write, the energies behind them (at the next multiple of 16).  One wavefront per state.
-__host__ __device__ inline unsigned long long subopt_pack_dcal_off(int n, int L) { return ((unsigned long long)n * (unsigned long long)(L + 1) + 15ull) & ~15ull; }
 __global__ __launch_bounds__(SUBOPT_NT) void subopt_pack_kernel(const SuboptSeq *seqs, const int *order, unsigned char *front, const SuboptRec *rec)
 {
     const int s = order[blockIdx.y], lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const SuboptRec r = rec[s];
     if (r.state != SUBOPT_DONE) return;
     const SuboptSeq q = seqs[s];
-    const int L = q.L, n = r.final_buf ? r.n[1] : r.n[0], words = subopt_state_bytes(L) / 4, rw0 = 4 + subopt_stack_words(L);
+    const int L = q.L, n = r.final_buf ? r.n[1] : r.n[0], words = subopt_state_bytes(L) / 4, rw0 = 4 + seg_stack_words(L);
     const uint32_t *in = (const uint32_t *)(front + (r.final_buf ? q.buf_off[1] : q.buf_off[0]));
     unsigned char *rows = front + (r.final_buf ? q.buf_off[0] : q.buf_off[1]);
     int *dcal = (int *)(rows + subopt_pack_dcal_off(n, L));

@@ -8,8 +8,8 @@ import numpy as np
 
 from . import _native as N
 from . import params as _params_mod
-from .rafft import _raise_like_reference
-from .utils import Structure, energies_from_dcal
+from .rafft import raise_for_status
+from .utils import structures_from_rows
 
 
 class PfResult:
@@ -56,11 +56,7 @@ def pf_batch(sequences, temp=37.0, probs=True, raise_errors=True):
         st = recs[k]["status"]
         if st != N.OK:
             if raise_errors:
-                if st == N.ERR_TOO_LONG:
-                    raise ValueError(f"sequence of {len(s)} nt: pf_batch takes up to {N.PF_MAX_LEN} nt (RAFFT_PF_MAX_LEN)")
-                if st == N.ERR_CAPACITY:
-                    raise N.RafftError(st, f"sequence {k}: the scaled partition function left the fp64 range")
-                _raise_like_reference(st, s)
+                raise_for_status(st, s, k, "pf_batch", "RAFFT_PF_MAX_LEN", "the scaled partition function left the fp64 range")
             out.append(None)
         else:
             out.append(PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None))
@@ -118,17 +114,10 @@ def sample_batch(sequences, n_samples, seeds=None, temp=37.0, raise_errors=True)
         st = recs[k]["status"]
         if st != N.OK:
             if raise_errors:
-                if st == N.ERR_TOO_LONG:
-                    raise ValueError(f"sequence of {len(s)} nt: sample_batch takes up to {N.PF_MAX_LEN} nt (RAFFT_PF_MAX_LEN)")
-                if st == N.ERR_CAPACITY:
-                    raise N.RafftError(st, f"sequence {k}: the scaled partition function left the fp64 range")
-                _raise_like_reference(st, s)
+                raise_for_status(st, s, k, "sample_batch", "RAFFT_PF_MAX_LEN", "the scaled partition function left the fp64 range")
             out.append(None)
-            continue
-        en = energies_from_dcal(dcal[k]).tolist()
-        text = rows[k][:, :-1].tobytes().decode("ascii")
-        n = len(s)
-        out.append([Structure(text[r * n:(r + 1) * n], int(dcal[k][r]), en[r]) for r in range(len(en))])
+        else:
+            out.append(structures_from_rows(rows[k], dcal[k], len(s)))
     return out
 
 

@@ -34,6 +34,17 @@ def _raise_like_reference(status, sequence):
     raise N.RafftError(status, "per-sequence failure")
 
 
+def raise_for_status(status, sequence, index, call, limit, capacity=None):
+    """What the batch call `call` raises for sequence number `index` with a status other than RAFFT_OK: over its length limit (the
+    constant `limit` of include/rafft_hip.h) a ValueError that names both, for RAFFT_ERR_CAPACITY a RafftError with the text
+    `capacity` (where the call has one), else what fold_batch raises."""
+    if status == N.ERR_TOO_LONG:
+        raise ValueError(f"sequence of {len(sequence)} nt: {call} takes up to {getattr(N, limit[len('RAFFT_'):])} nt ({limit})")
+    if status == N.ERR_CAPACITY and capacity is not None:
+        raise N.RafftError(status, f"sequence {index}: {capacity}")
+    _raise_like_reference(status, sequence)
+
+
 class _Owner:
     """keeps a rafft_result alive while any view of it exists; frees it with the last one"""
     __slots__ = ("res", "lib")

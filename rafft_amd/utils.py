@@ -31,6 +31,14 @@ def energies_from_dcal(dcal):
     return (d.astype(np.float32).astype(np.float64) / 100.0).astype(np.float32).astype(np.float64)
 
 
+def structures_from_rows(rows_k, dcal_k, n):
+    """The Structure list of one sequence of n nt from its (rows, n + 1) uint8 array - a row is the dot-bracket text and its NUL -
+    and the int32 array of the rows' energies in dcal/mol (what sample_batch_raw and subopt_batch_raw return per sequence)."""
+    en = energies_from_dcal(dcal_k).tolist()
+    text = rows_k[:, :-1].tobytes().decode("ascii")
+    return [Structure(text[r * n:(r + 1) * n], int(dcal_k[r]), en[r]) for r in range(len(en))]
+
+
 def dot_bracket(pair_list, len_seq, SEQ=None):
     """rafft/utils.py:42-50"""
     s = ["."] * len_seq

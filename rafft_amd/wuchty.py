@@ -7,8 +7,8 @@ import numpy as np
 
 from . import _native as N
 from . import params as _params_mod
-from .rafft import _raise_like_reference
-from .utils import Structure, energies_from_dcal
+from .rafft import raise_for_status
+from .utils import structures_from_rows
 
 
 def subopt_batch_raw(sequences, delta_dcal, max_structs=100000, temp=37.0, workspace_bytes=0):
@@ -52,17 +52,11 @@ def subopt_batch(sequences, delta=1.0, max_structs=100000, temp=37.0, raise_erro
         st = recs[k]["status"]
         if st != N.OK:
             if raise_errors:
-                if st == N.ERR_TOO_LONG:
-                    raise ValueError(f"sequence of {len(s)} nt: subopt_batch takes up to {N.MFE_MAX_LEN} nt (RAFFT_SUBOPT_MAX_LEN)")
-                if st == N.ERR_CAPACITY:
-                    raise N.RafftError(st, f"sequence {k}: at least {recs[k]['n_reached']} structures within {delta} kcal/mol, max_structs is {max_structs}")
-                _raise_like_reference(st, s)
+                raise_for_status(st, s, k, "subopt_batch", "RAFFT_SUBOPT_MAX_LEN",
+                                 f"at least {recs[k]['n_reached']} structures within {delta} kcal/mol, max_structs is {max_structs}")
             out.append(None)
-            continue
-        en = energies_from_dcal(dcal[k]).tolist()
-        text = rows[k][:, :-1].tobytes().decode("ascii")
-        n = len(s)
-        out.append([Structure(text[r * n:(r + 1) * n], int(dcal[k][r]), en[r]) for r in range(len(en))])
+        else:
+            out.append(structures_from_rows(rows[k], dcal[k], len(s)))
     return out
 
 

@@ -4,7 +4,7 @@ import numpy as np
 
 from . import _native as N
 from . import params as _params_mod
-from .rafft import _raise_like_reference
+from .rafft import raise_for_status
 from .utils import Structure, energies_from_dcal
 
 
@@ -29,9 +29,7 @@ def mfe_batch(sequences, temp=37.0, raise_errors=True):
     for k, s in enumerate(sequences):
         if status[k] != N.OK:
             if raise_errors:
-                if status[k] == N.ERR_TOO_LONG:
-                    raise ValueError(f"sequence of {len(s)} nt: mfe_batch takes up to {N.MFE_MAX_LEN} nt (RAFFT_MFE_MAX_LEN)")
-                _raise_like_reference(status[k], s)
+                raise_for_status(status[k], s, k, "mfe_batch", "RAFFT_MFE_MAX_LEN")
             out.append(None)
         else:
             out.append(Structure(rows[k], dcal[k], en[k]))

@@ -1,6 +1,7 @@
 // Host-side check of rafft_amd/csrc/rafft_hostpure.h: the lane cut of a batch, the dot-bracket parsers, the base codes, the
 // enclosing-loop walk, the row layout of the scoring calls and the planning of the batch drivers (chunk planner, sequence pack,
-// graph pack, solve order), against values derived by hand from the rules.  Plain C++, no HIP, no GPU.  Test infrastructure.
+// graph pack, solve order, and the layouts of the four sequence drivers with the sizes of rafft_batch_layout.h), against values
+// derived by hand from the rules.  Plain C++, no HIP, no GPU.  Test infrastructure.
 #include <cstdio>
 #include "../../rafft_amd/csrc/rafft_hostpure.h"
 static int fails = 0;
@@ -303,6 +304,179 @@ static void check_solve_order()
     CHECK(c.n_small == 0 && c.n_big == 0 && part[5] == -1);
 }
 
+// ---- the layouts of the sequence drivers
+
+typedef std::vector<int> Ints;
+typedef std::vector<unsigned long long> Offs;
+
+// a pack of sequences of these lengths (all A); a length of 0 is an empty sequence, an error between the others
+static SeqPack pack_of(const Ints &lens)
+{
+    std::vector<std::string> text;
+    for (int n : lens) text.push_back(std::string((size_t)n, 'A'));
+    std::vector<const char *> seqs;
+    for (const std::string &s : text) seqs.push_back(s.c_str());
+    return pack_sequences((int)lens.size(), seqs.data(), lens.data(), 4096);
+}
+template <class Q> static Offs tab_offs(const std::vector<Q> &qs) { Offs v; for (const Q &q : qs) v.push_back(q.tab_off); return v; }
+
+static void check_chunk_lmax()
+{
+    const Ints L = {5, 2, 7, 9}, order = {3, 0, 2, 1};              // lengths in the order of the plan: 9, 5, 7, 2
+    CHECK(chunk_lmax(ChunkPlan::Range{0, 3}, order, L) == 9);       // the longest is the first
+    CHECK(chunk_lmax(ChunkPlan::Range{1, 3}, order, L) == 7);       // ... the last
+    CHECK(chunk_lmax(ChunkPlan::Range{3, 4}, order, L) == 2);       // ... the only one
+    CHECK(chunk_lmax(ChunkPlan::Range{0, 4}, order, L) == 9);
+    CHECK(chunk_lmax(ChunkPlan::Range{2, 2}, order, L) == 0);
+}
+
+static void check_mfe_layout()
+{
+    // mfe_lds_bytes: 3 triangles, F and the padded bases.  146: (3 * 10731 + 147) * 4 + 160 = 129520 <= 131072 < 131288 = (3 * 10878 + 148) * 4 + 160
+    CHECK(mfe_lds_bytes(146) == 129520 && mfe_lds_bytes(147) == 131288 && MFE_LDS_BYTES == 131072 && RAFFT_MFE_LDS_LEN == 146);
+    const SeqPack pk = pack_of({0, 5, 146, 147, 5});
+    CHECK(pk.code_off == (Offs{0, 0, 5, 151, 298}));
+    {
+        const MfeLayout y = mfe_layout(pk, 146, 1 << 30);
+        // 146 is the last length of the LDS class, 147 the first of the other; the two 5s keep their input order behind 146
+        CHECK(y.lds_order == (Ints{2, 1, 4}) && y.hbm_order == (Ints{3}) && y.order == (Ints{2, 1, 4, 3}));
+        // stacks of L + 8 words, rows of L + 1 bytes, in input order; the error takes nothing: 0 | 13 | 13 + 154 | 167 + 155 | 322 + 13
+        Offs stack, db, code;
+        Ints L;
+        for (const MfeSeq &q : y.qs) { stack.push_back(q.stack_off); db.push_back(q.db_off); code.push_back(q.code_off); L.push_back(q.L); CHECK(q.pad == 0); }
+        CHECK(stack == (Offs{0, 0, 13, 167, 322}) && y.n_stack == 335);
+        CHECK(db == (Offs{0, 0, 6, 153, 301}) && y.n_db == 307);
+        CHECK(code == pk.code_off && L == (Ints{0, 5, 146, 147, 5}));
+        CHECK(flat(y.plan) == (Sizes{0, 1}) && y.plan.max_cost == 3 * 147 * 147 * 4 && tab_offs(y.qs) == (Offs{0, 0, 0, 0, 0}));
+    }
+    {   // lds_len 4: everything in the HBM class, in input order; tables of 3 L^2 ints: 300, 255792, 259308, 300 bytes
+        MfeLayout y = mfe_layout(pk, 4, 1 << 30);
+        CHECK(y.lds_order.empty() && y.hbm_order == (Ints{1, 2, 3, 4}) && y.order == y.hbm_order);
+        CHECK(flat(y.plan) == (Sizes{0, 4}) && y.plan.off == (Sizes{0, 300, 256092, 515400}) && y.plan.max_cost == 515700);
+        CHECK(tab_offs(y.qs) == (Offs{0, 0, 75, 64023, 128850}));
+        y = mfe_layout(pk, 4, 259608);                              // the last two, not the first three: the tables start again in the second chunk
+        CHECK(flat(y.plan) == (Sizes{0, 2, 2, 4}) && y.plan.max_cost == 259608 && tab_offs(y.qs) == (Offs{0, 0, 75, 0, 64827}));
+        CHECK(y.qs[3].stack_off == 167 && y.qs[4].db_off == 301);  // ... the stacks and rows do not
+        y = mfe_layout(pk, 5, 1 << 30);                             // a length equal to lds_len is in the LDS class
+        CHECK(y.lds_order == (Ints{1, 4}) && y.hbm_order == (Ints{2, 3}) && y.order == (Ints{1, 4, 2, 3}) && tab_offs(y.qs) == (Offs{0, 0, 0, 63948, 0}));
+    }
+    {   // an error between two sequences stands where the next one starts
+        const MfeLayout y = mfe_layout(pack_of({5, 0, 5}), 146, 1 << 30);
+        CHECK(y.qs[1].stack_off == 13 && y.qs[2].stack_off == 13 && y.qs[1].db_off == 6 && y.qs[2].db_off == 6 && y.qs[1].L == 0);
+        CHECK(y.n_stack == 26 && y.n_db == 12 && y.lds_order == (Ints{0, 2}));
+        const MfeLayout none = mfe_layout(pack_of({0, 0}), 146, 1 << 30);
+        CHECK(none.order.empty() && none.plan.chunks.empty() && none.plan.max_cost == 0 && none.n_stack == 0 && none.n_db == 0 && none.qs.size() == 2);
+    }
+}
+
+static void check_pf_layout()
+{
+    const SeqPack pk = pack_of({0, 5, 7, 0, 6});
+    CHECK(pk.fold == (Ints{1, 2, 4}));
+    // ps, pb, F, Fr of L + 1 doubles each: 24, 32, 28; rows of L + 1 bytes: 6, 8, 7; the errors take nothing
+    PfLayout y = pf_layout(pk, 3, nullptr, 1 << 30);
+    Offs aux, db;
+    for (const PfSeq &q : y.qs) { aux.push_back(q.aux_off); db.push_back(q.db_off); CHECK(q.mfe_dcal == 0 && q.scale == 0.0 && q.ln_scale == 0.0); }
+    CHECK(aux == (Offs{0, 0, 24, 56, 56}) && y.n_aux == 84 && db == (Offs{0, 0, 6, 14, 14}) && y.n_db == 21);
+    CHECK(y.qs[0].L == 0 && y.qs[1].L == 5 && y.qs[2].L == 7 && y.qs[3].L == 0 && y.qs[4].L == 6 && y.qs[4].code_off == 12);
+    // three tables of L^2 doubles: 600, 1176, 864 bytes; tab_off counts doubles
+    CHECK(flat(y.plan) == (Sizes{0, 3}) && y.plan.off == (Sizes{0, 600, 1776}) && y.plan.max_cost == 2640 && tab_offs(y.qs) == (Offs{0, 0, 75, 0, 222}));
+    y = pf_layout(pk, 6, nullptr, 1 << 30);                          // six: 1200, 2352, 1728
+    CHECK(flat(y.plan) == (Sizes{0, 3}) && y.plan.max_cost == 5280 && tab_offs(y.qs) == (Offs{0, 0, 150, 0, 444}) && y.n_aux == 84 && y.n_db == 21);
+    y = pf_layout(pk, 3, nullptr, 1776);                             // 600 + 1176 is not over 1776
+    CHECK(flat(y.plan) == (Sizes{0, 2, 2, 3}) && tab_offs(y.qs) == (Offs{0, 0, 75, 0, 0}) && y.plan.max_cost == 1776);
+    y = pf_layout(pk, 6, nullptr, 1776);                             // ... 1200 + 2352 is
+    CHECK(flat(y.plan) == (Sizes{0, 1, 1, 2, 2, 3}) && tab_offs(y.qs) == (Offs{0, 0, 0, 0, 0}) && y.plan.max_cost == 2352);
+    const size_t cost2[3] = {2000, 1000, 10};                        // the tables of all three fit 2640, 2000 + 1000 does not: the second cost cuts
+    y = pf_layout(pk, 3, cost2, 2640);
+    CHECK(flat(y.plan) == (Sizes{0, 1, 1, 3}) && tab_offs(y.qs) == (Offs{0, 0, 0, 0, 147}) && y.plan.max_cost == 2040 && y.plan.max_cost2 == 2000);
+    CHECK(y.qs[4].aux_off == 56 && y.qs[4].db_off == 14);         // (aux and rows are the whole call's, not a chunk's)
+}
+
+static void check_sample_layout()
+{
+    const SeqPack pk = pack_of({0, 5, 7, 0, 6});
+    const unsigned long long seeds[5] = {10, 11, 12, 13, 14};
+    CHECK(sample_row_costs(pk, 3) == (Sizes{18, 24, 21}));           // three rows of L + 1 bytes
+    auto fields = [](const SampleLayout &y) { Offs v; for (const SampleSeq &q : y.smp) { v.push_back(q.seed); v.push_back(q.row_off); v.push_back(q.dcal_off); } return v; };
+    // one chunk of three: rows back to back, the energies of the chunk's k-th sequence from int 3 k; the errors keep zeros
+    SampleLayout y = sample_layout(pk, pf_layout(pk, 3, nullptr, 1 << 30).plan, 3, seeds);
+    CHECK(y.row_bytes == (Sizes{18, 24, 21}) && y.max_seqs == 3);
+    CHECK(fields(y) == (Offs{0, 0, 0, 11, 0, 0, 12, 18, 3, 0, 0, 0, 14, 42, 6}));
+    // chunks [0, 2) and [2, 3) (the tables cut, as in check_pf_layout): rows and energies start again at 0
+    const ChunkPlan two = pf_layout(pk, 3, y.row_bytes.data(), 1776).plan;
+    CHECK(flat(two) == (Sizes{0, 2, 2, 3}) && two.max_cost2 == 42);
+    y = sample_layout(pk, two, 3, seeds);
+    CHECK(y.max_seqs == 2 && fields(y) == (Offs{0, 0, 0, 11, 0, 0, 12, 18, 3, 0, 0, 0, 14, 0, 0}));
+    y = sample_layout(pk, two, 3, nullptr);                          // no seeds: every seed 0
+    CHECK(fields(y) == (Offs{0, 0, 0, 0, 0, 0, 0, 18, 3, 0, 0, 0, 0, 0, 0}));
+    y = sample_layout(pk, two, 0, seeds);                            // no samples: no bytes
+    CHECK(y.row_bytes == (Sizes{0, 0, 0}) && y.max_seqs == 2 && fields(y) == (Offs{0, 0, 0, 11, 0, 0, 12, 0, 0, 0, 0, 0, 14, 0, 0}));
+    y = sample_layout(pack_of({0}), ChunkPlan{}, 3, seeds);
+    CHECK(y.row_bytes.empty() && y.max_seqs == 0 && y.smp.size() == 1);
+}
+
+static void check_subopt_layout()
+{
+    // a state: 16 bytes of numbers, a stack of L / 5 + 2 words rounded up to 4, a row of L + 1 bytes rounded up to 16
+    //   L = 80: 16 + 4 * 20 (18 -> 20) + 96 (81 -> 96) = 192      L = 9: 16 + 4 * 4 (3 -> 4) + 16 (10 -> 16) = 48
+    //   L = 79: 16 + 4 * 20 (17 -> 20) + 80 (80 -> 80) = 176      L = 1, 4, 5: 16 + 4 * 4 (2, 2, 3 -> 4) + 16 (2, 5, 6 -> 16) = 48
+    CHECK(subopt_state_bytes(80) == 192 && subopt_state_bytes(9) == 48 && subopt_state_bytes(79) == 176);
+    CHECK(subopt_state_bytes(1) == 48 && subopt_state_bytes(4) == 48 && subopt_state_bytes(5) == 48);
+    CHECK(seg_stack_words(80) == 20 && row_bytes16(80) == 96 && row_bytes16(79) == 80 && row_bytes16(15) == 16 && row_bytes16(16) == 32);
+    CHECK(sample_lds_bytes(80) == 4 * (96 + 80));
+    const Ints lens = {1, 4, 5, 0, 79, 80};                          // an error between them
+    const size_t state[6] = {48, 48, 48, 0, 176, 192};
+    const SeqPack pk = pack_of(lens);
+    CHECK(pk.fold == (Ints{0, 1, 2, 4, 5}));
+    for (int M : {1, 63, 64, 65}) {
+        const size_t cnt = M <= 64 ? 256 : 512;                      // M counts of 4 bytes, rounded up to 256
+        // tables of 3 L^2 ints: 12, 192, 300, 74892, 76800 bytes.  Everything in one chunk; then a budget that holds the first four
+        // tables (75396) but not the fifth, the frontiers (at most 3 * 6752 + 23392 = 43648) staying below it
+        for (size_t budget : {(size_t)1 << 30, (size_t)80000}) {
+            const bool cut = budget == 80000;
+            const SuboptLayout y = subopt_layout(pk, M, budget);
+            CHECK(y.tab_bytes == (Sizes{12, 192, 300, 74892, 76800}));
+            CHECK(flat(y.plan) == (cut ? Sizes{0, 4, 4, 5} : Sizes{0, 5}) && y.max_seqs == (cut ? 4u : 5u));
+            CHECK(tab_offs(y.qs) == (cut ? Offs{0, 3, 51, 0, 126, 0} : Offs{0, 3, 51, 0, 126, 18849}));
+            CHECK(y.qs.size() == 6 && y.mq.size() == 6 && y.n_f == 174);
+            size_t at = 0, total = 0;
+            unsigned long long f = 0;
+            for (size_t k = 0; k < pk.fold.size(); k++) {
+                const int s = pk.fold[k];
+                const SuboptSeq &q = y.qs[s];
+                if (cut && k == 4) at = 0;                           // the frontiers of a chunk start at byte 0 ...
+                CHECK(y.front_bytes[k] == 2 * (size_t)M * state[s] + cnt);
+                CHECK(q.buf_off[0] == at && q.buf_off[1] - q.buf_off[0] == (size_t)M * state[s]);
+                CHECK(q.cnt_off * 4 == q.buf_off[1] + (size_t)M * state[s]);          // the counts lie exactly behind the second buffer
+                CHECK(q.cnt_off * 4 + 4 * (size_t)M <= at + y.front_bytes[k]);        // ... and end before the next sequence starts
+                CHECK(q.f_off == f && q.L == lens[s] && q.code_off == pk.code_off[s] && q.pad == 0);     // ... the exterior energies go on
+                const MfeSeq &m = y.mq[s];                           // what the table fill reads is the same sequence
+                CHECK(m.code_off == q.code_off && m.tab_off == q.tab_off && m.L == q.L && m.stack_off == 0 && m.db_off == 0 && m.pad == 0);
+                at += y.front_bytes[k]; f += (unsigned long long)lens[s] + 1;
+                total = std::max(total, at);
+            }
+            CHECK(y.plan.max_cost2 == total);
+            const SuboptSeq &e = y.qs[3];
+            CHECK(e.L == 0 && e.code_off == 0 && e.tab_off == 0 && e.f_off == 0 && e.buf_off[0] == 0 && e.buf_off[1] == 0 && e.cnt_off == 0 && y.mq[3].L == 0);
+        }
+        // the packed copy of n <= M finished states - n rows, then n energies - fits the buffer of M states it is written into
+        for (int L : {1, 4, 5, 79, 80})
+            for (int n = 0; n <= M; n++) {
+                CHECK(subopt_pack_dcal_off(n, L) >= (unsigned long long)n * (L + 1) && subopt_pack_dcal_off(n, L) % 16 == 0);
+                CHECK(subopt_pack_dcal_off(n, L) + 4ull * n <= (unsigned long long)M * subopt_state_bytes(L));
+            }
+    }
+    CHECK(subopt_pack_dcal_off(1, 1) == 16 && subopt_pack_dcal_off(64, 80) == 5184 && subopt_pack_dcal_off(63, 79) == 5040);
+    {   // the frontiers cut a chunk the tables would not: 2 * 64 * 48 + 256 = 6400 each, 192 + 300 bytes of tables
+        const SuboptLayout y = subopt_layout(pack_of({4, 5}), 64, 12000);
+        CHECK(flat(y.plan) == (Sizes{0, 1, 1, 2}) && y.max_seqs == 1 && y.plan.max_cost == 300 && y.plan.max_cost2 == 6400);
+        CHECK(y.qs[1].buf_off[0] == 0 && y.qs[1].buf_off[1] == 3072 && y.qs[1].cnt_off == 1536 && y.qs[1].tab_off == 0 && y.qs[1].f_off == 5);
+        const SuboptLayout z = subopt_layout(pack_of({4, 5}), 64, 12800);
+        CHECK(flat(z.plan) == (Sizes{0, 2}) && z.qs[1].buf_off[0] == 6400 && z.qs[1].cnt_off == 3136 && z.qs[1].tab_off == 48);
+    }
+}
+
 int main()
 {
     check_lanes();
@@ -313,6 +487,11 @@ int main()
     check_sequence_pack();
     check_graph_pack();
     check_solve_order();
+    check_chunk_lmax();
+    check_mfe_layout();
+    check_pf_layout();
+    check_sample_layout();
+    check_subopt_layout();
     printf("hostpure: %d failures\n", fails);
     return fails ? 1 : 0;
 }

@@ -1,12 +1,19 @@
-"""The three batch drivers (rafft_mfe_batch, rafft_pf_batch, rafft_kin_batch) on a real MI355X (`-m gpu`), where an offset out of the
-planning they share (rafft_hostpure.h: chunk planner, sequence pack, graph pack, solve order) would show and no other test looks:
-sequences with errors BETWEEN the good ones while the good ones are cut into chunks of two, and a kinetics chunk that holds exactly
-two solvable graphs with an unsolved one between them.  Every comparison is bit for bit against the same call in one chunk."""
+"""The five batch drivers (rafft_mfe_batch, rafft_pf_batch, rafft_sample_batch, rafft_subopt_batch, rafft_kin_batch) on a real
+MI355X (`-m gpu`), where an offset out of the planning they share (rafft_hostpure.h: chunk planner, sequence pack, the layouts of the
+sequence drivers, graph pack, solve order) would show and no other test looks: sequences with errors BETWEEN the good ones while the
+good ones are cut into chunks of two, and a kinetics chunk that holds exactly two solvable graphs with an unsolved one between them.
+Every comparison is bit for bit against the same call in one chunk."""
+import ctypes
+
 import numpy as np
 import pytest
 
 import _kin_graphs as K
-from rafft_amd import _native as N, mccaskill, rafft_kin, zuker
+import _loops as LP
+import _mfe_np as MF
+import _par_reader as PR
+import _subopt_np as SB
+from rafft_amd import _native as N, mccaskill, params, rafft_kin, wuchty, zuker
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +75,75 @@ def test_gpu_pf_errors_between_chunks_of_two():
     assert rows == ["." * len(b) for b in BAD] and [r["status"] for r in recs] == BAD_STATUS
     assert all((r["mfe_dcal"], r["n_pairs"], r["energy"], r["mfe_frequency"]) == (0, 0, 0.0, 0.0) for r in recs)
     assert not probs[1].any()
+
+
+def sample_bits(recs, rows, dcal, k):
+    """everything rafft_sample_batch returns for sequence k, as bytes and integers"""
+    r = recs[k]
+    return (r["status"], r["length"], r["mfe_dcal"], r["n_samples"], np.float64(r["energy"]).tobytes(), rows[k].tobytes(), dcal[k].tobytes())
+
+
+def test_gpu_sample_errors_between_chunks_of_two():
+    """the same mix and the same cuts (three fp64 tables: 3 * 8 * (33^2 + 58^2 + 71^2) > 2 * 3 * 8 * 64^2 and so on; the rows of a
+    chunk, 8 (L + 1) bytes a sequence, are far below the budget), eight samples a sequence, a seed of its own for each: rows and
+    energies of a chunk come back from the chunk's own row and energy offsets, whatever stands between its sequences"""
+    seqs, good, keep = mixed()
+    n, seeds = len(seqs), [1000 + 17 * k for k in range(len(seqs))]
+    whole = mccaskill.sample_batch_raw(seqs, 8, seeds)
+    recs, rows, dcal = whole
+    assert [recs[k]["status"] for k in range(n)] == [BAD_STATUS[BAD_AT.index(k)] if k in BAD_AT else N.OK for k in range(n)]
+    assert [recs[k]["mfe_dcal"] for k in range(n)] == zuker.mfe_batch_raw(seqs)[1]
+    for k, b in zip(BAD_AT, BAD):
+        assert rows[k].shape == (8, len(b) + 1) and (rows[k][:, :-1] == ord(".")).all() and not rows[k][:, -1].any() and not dcal[k].any(), k
+        assert (recs[k]["length"], recs[k]["mfe_dcal"], recs[k]["n_samples"], recs[k]["energy"]) == (len(b), 0, 0, 0.0), k
+    for k in keep:
+        assert recs[k]["n_samples"] == 8 and not rows[k][:, -1].any() and set(rows[k][:, :-1].tobytes()) <= set(b"(.)"), k
+    alone = mccaskill.sample_batch_raw(good, 8, [seeds[k] for k in keep])
+    assert [sample_bits(*whole, k) for k in keep] == [sample_bits(*alone, j) for j in range(len(good))]
+    for budget in (2 * 3 * 64 * 64 * 8, 1):
+        got = mccaskill.sample_batch_raw(seqs, 8, seeds, workspace_bytes=budget)
+        assert [sample_bits(*got, k) for k in range(n)] == [sample_bits(*whole, k) for k in range(n)], budget
+
+
+def subopt_bits(recs, rows, dcal, k):
+    """everything rafft_subopt_batch returns for sequence k, as bytes and integers"""
+    r = recs[k]
+    return (r["status"], r["length"], r["mfe_dcal"], r["n_structs"], r["n_reached"], rows[k].tobytes(), dcal[k].tobytes())
+
+
+def subopt_chunks():
+    c = (ctypes.c_longlong * 7)()
+    N.check(N.lib().rafft_subopt_counters(ctypes.byref(c)))
+    return c[3]
+
+
+def test_gpu_subopt_errors_between_chunks_of_two():
+    """the same mix, max_structs 128 and a budget for the tables of two 64-nt sequences (three int32 tables, the cuts of the MFE
+    test).  The frontiers do not cut earlier: two buffers of 128 states and 512 bytes of counts a sequence are 25088, 37376, 41472,
+    20992, 41472, 29184, 49664 and 12800 bytes for the eight lengths (states of 96, 144, 160, 80, 160, 112, 192 and 48 bytes), at
+    most 41472 + 29184 = 70656 for a pair, below the 98304 of the budget - so the counter of chunks is 4, and 8 with a budget of 1.
+    delta is 150 dcal/mol: the walk of tests/_subopt_np.py finds 15, 13, 37, 2, 50, 2, 16 and 1 structures in that band, every
+    count within max_structs and seven of them above 1, so that second states are read from their buffer offsets"""
+    seqs, good, keep = mixed()
+    n, delta, counts = len(seqs), 150, [15, 13, 37, 2, 50, 2, 16, 1]
+    params.reset_params()                                       # the built-in tables, which the mirror reads
+    mirror = MF.Mirror(PR.tables_at(LP.builtin_par(), 37.0))
+    band = [SB.band(mirror, s, delta) for s in good]
+    assert [len(b) for b in band] == counts and max(counts) <= 128 and sum(c > 1 for c in counts) == 7
+    whole = wuchty.subopt_batch_raw(seqs, delta, max_structs=128)
+    assert subopt_chunks() == 1
+    recs, rows, dcal = whole
+    assert [recs[k]["status"] for k in range(n)] == [BAD_STATUS[BAD_AT.index(k)] if k in BAD_AT else N.OK for k in range(n)]
+    assert [recs[k]["n_structs"] for k in keep] == counts and all(recs[k]["n_structs"] == 0 and rows[k].shape[0] == 0 for k in BAD_AT)
+    for j, k in enumerate(keep):
+        assert [(rows[k][r, :-1].tobytes().decode("ascii"), int(dcal[k][r])) for r in range(counts[j])] == band[j], k
+    alone = wuchty.subopt_batch_raw(good, delta, max_structs=128)
+    assert [subopt_bits(*whole, k) for k in keep] == [subopt_bits(*alone, j) for j in range(len(good))]
+    for budget, chunks in ((2 * 3 * 64 * 64 * 4, 4), (1, 8)):
+        got = wuchty.subopt_batch_raw(seqs, delta, max_structs=128, workspace_bytes=budget)
+        assert subopt_chunks() == chunks, budget
+        assert "sequence 2" in N.lib().rafft_last_error().decode(), budget
+        assert [subopt_bits(*got, k) for k in range(n)] == [subopt_bits(*whole, k) for k in range(n)], budget
 
 
 def test_gpu_kin_batch_chunk_of_exactly_two():

@@ -354,8 +354,9 @@ def test_config_struct_is_the_only_reader_of_the_environment(tmp_path):
 def test_hostpure_helpers_against_hand_derived_values(tmp_path):
     """rafft_hostpure.h - the lane cut of a batch (RAFFT_SPLIT rule, lanes, estimate), the two host dot-bracket parsers, the base codes, the
     enclosing-loop walk of rafft_expand_node, the row layout of the scoring calls and the planning of the batch drivers (the chunk planner
-    of all three, the sequence pack of rafft_mfe_batch / rafft_pf_batch, the graph pack and the solve order of rafft_kin_batch) - compiled
-    alone with g++ (no HIP, no GPU) and checked against values derived by hand from the rules; then the same program under
+    of all five, the sequence pack and the layouts of rafft_mfe_batch / rafft_pf_batch / rafft_sample_batch / rafft_subopt_batch - every
+    offset their kernels dereference, with the sizes of rafft_batch_layout.h - the graph pack and the solve order of rafft_kin_batch) -
+    compiled alone with g++ (no HIP, no GPU) and checked against values derived by hand from the rules; then the same program under
     AddressSanitizer + UBSan, run directly"""
     src = os.path.join(ROOT, "tests", "hostcheck", "hostpure_check.cpp")
     for tag, flags in (("plain", ["-O1"]), ("san", ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
