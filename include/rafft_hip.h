@@ -468,6 +468,56 @@ void rafft_subopt_free(rafft_subopt_result *r);
  * copying */
 int  rafft_subopt_counters(long long out[7]);
 
+/* Folding barriers between pairs of structures (direct paths).  Replaces: RNA.fold_compound(seq).path_findpath(A, B,
+ * width) / ViennaRNA's `findpath` (Flamm et al. 2001), what a user of the reference takes from ViennaRNA to ask how high the
+ * way from one structure of a fast-folding graph to another, or to the MFE structure, climbs.
+ * One call, n_paths independent problems: sequence seqs[p] (lens[p] characters), start row starts[p] and end row ends[p] (NUL
+ * terminated dot-brackets of ( ) . with lens[p] characters), widths[p] partial paths kept per step.
+ * A direct path removes the pairs of A that are not in B and adds the pairs of B that are not in A, one pair per step, every
+ * intermediate being a secondary structure: d = |A \ B| + |B \ A| <= lens[p] moves, d + 1 structures.
+ * The search is defined exactly, so same input, same bits.  Moves are numbered removals first (ascending 5' end), then additions
+ * (ascending 5' end).  A removal is always legal; an addition is legal once every removal that crosses it or shares a base with it
+ * is applied.  A state is the set of applied moves with its energy and its saddle so far (the highest energy on its way, both
+ * ends included).  Level 0 holds A.  The candidates of the next level are every (state of the beam, legal unapplied move), sorted
+ * ascending by (saddle, energy, rank of the parent in its beam, move number); they are taken in that order, a candidate whose set
+ * of applied moves equals that of one already taken is skipped (sets are compared, not hashes), and the level is full at
+ * widths[p] states.  After d levels every state is B; the first one is the result.  The energy of a candidate is its parent's plus
+ * the change of the loops the move touches, from the loop energies rafft_eval_structure uses: rafft_eval_structure of any row of
+ * the path gives the path's energy at that step.
+ * Outputs (host): rec_out[p]; moves_out may be NULL and so may moves_out[p], else 2 * dist ints (room for 2 * lens[p]): move k is
+ * (moves_out[p][2k], moves_out[p][2k+1]) = (i, j) 0-based for an added pair, (-i-1, -j-1) for a removed one; dcal_out may be NULL
+ * and so may dcal_out[p], else dist + 1 ints (room for lens[p] + 1): the energy of A, then after every move.
+ * dist = 0 (A equals B) is valid: no moves, one energy, saddle = start.
+ * Errors of that problem only - the call returns RAFFT_OK, the record has length 0, nothing is written to its path and
+ * rafft_last_error() names the first such problem: RAFFT_ERR_EMPTY, RAFFT_ERR_BAD_CHAR (the sequence), RAFFT_ERR_TOO_LONG (above
+ * RAFFT_FINDPATH_MAX_LEN), RAFFT_ERR_STRUCT (a malformed row, a row of another length than the sequence, a non-canonical pair in A
+ * or B), RAFFT_ERR_CAPACITY (widths[p] x dist above RAFFT_FINDPATH_MAX_CANDIDATES - dist is reported - or an energy that the
+ * 22-bit fields of the sort key cannot hold, |energy| >= 2^21 dcal: a hairpin of fewer than 3, for instance; never a silently
+ * wrong order).  RAFFT_ERR_PARAM, before anything is launched: a null argument, a negative n_paths or workspace_bytes, a width
+ * outside [1, RAFFT_FINDPATH_MAX_WIDTH].  RAFFT_ERR_TEMP as for the fold.  A batch of nothing but erroneous problems never touches
+ * the device.  A problem's bits depend on its sequence, A, B, width, temp and the energy tables only - not on the batch, its order,
+ * the chunking or the workspace.
+ * Device memory: problems are taken in chunks of whole problems in input order whose work areas fit workspace_bytes (0: 512 MiB),
+ * one problem at least; a problem's work area is 16 x width x dist bytes and its two beams. */
+#define RAFFT_FINDPATH_MAX_LEN        RAFFT_MFE_MAX_LEN
+#define RAFFT_FINDPATH_MAX_WIDTH      1024
+#define RAFFT_FINDPATH_MAX_CANDIDATES (1 << 20)
+typedef struct {
+    int32_t status;
+    int32_t length;        /* moves of the returned path: dist, or 0 when status != 0 */
+    int32_t dist;          /* d = |A \ B| + |B \ A| (also set with RAFFT_ERR_CAPACITY) */
+    int32_t start_dcal;    /* energy of A */
+    int32_t end_dcal;      /* energy of B */
+    int32_t saddle_dcal;   /* the highest energy over the dist + 1 structures of the path, both ends included */
+    int32_t saddle_step;   /* the first structure of the path that reaches it: 0 is A, k the structure after move k - 1 */
+    int32_t _pad;
+} rafft_findpath_rec;      /* 32 bytes */
+int rafft_findpath_batch(int n_paths, const char *const *seqs, const int *lens, const char *const *starts, const char *const *ends,
+                         const int *widths, double temp, long long workspace_bytes /* 0: 512 MiB */,
+                         rafft_findpath_rec *rec_out, int *const *moves_out, int *const *dcal_out);
+/* of the last rafft_findpath_batch: chunks, levels over all chunks, kernel launches, problems that ran */
+int rafft_findpath_counters(long long out[4]);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

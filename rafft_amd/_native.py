@@ -90,13 +90,24 @@ SUBOPT_MAX_LEN = MFE_MAX_LEN     # RAFFT_SUBOPT_MAX_LEN
 SUBOPT_MAX_STRUCTS = 1 << 24     # RAFFT_SUBOPT_MAX_STRUCTS
 SUBOPT_MAX_DELTA = 1000000       # RAFFT_SUBOPT_MAX_DELTA (dcal)
 
+class FindpathRec(C.Structure):
+    """rafft_findpath_rec: one record per problem of rafft_findpath_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("dist", C.c_int32), ("start_dcal", C.c_int32), ("end_dcal", C.c_int32),
+                ("saddle_dcal", C.c_int32), ("saddle_step", C.c_int32), ("_pad", C.c_int32)]
+
+
+FINDPATH_MAX_LEN = MFE_MAX_LEN           # RAFFT_FINDPATH_MAX_LEN
+FINDPATH_MAX_WIDTH = 1024                # RAFFT_FINDPATH_MAX_WIDTH
+FINDPATH_MAX_CANDIDATES = 1 << 20        # RAFFT_FINDPATH_MAX_CANDIDATES
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
            "rafft_param_value", "rafft_kin_rate_matrix", "rafft_shutdown", "rafft_alloc_counters", "rafft_eval_structures_info", "rafft_params_unpinned",
            "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
            "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
-           "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters"]
+           "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
+           "rafft_findpath_counters"]
 
 _lib = None
 
@@ -196,6 +207,10 @@ def lib():
     L.rafft_subopt_free.argtypes = [C.POINTER(SuboptResult)]
     L.rafft_subopt_free.restype = None
     L.rafft_subopt_counters.argtypes = [C.POINTER(C.c_longlong * 7)]
+    L.rafft_findpath_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                       C.POINTER(C.c_int), C.c_double, C.c_longlong, C.POINTER(FindpathRec), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p)]
+    L.rafft_findpath_counters.argtypes = [C.POINTER(C.c_longlong * 4)]
     _lib = L
     return L
 

@@ -70,6 +70,17 @@ _OPTIONS = [
                                                            "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --pf, --sample, --kin or --traj")),
     (("--max-structs",), dict(type=int, default=100000, metavar="N", help="with --subopt: a sequence with more than N structures in the band is an error\n"
                                                                           "(default 100000)")),
+    (("--findpath",), dict(action="store_true", help="no RAFFT fold: with -sf FILE, a folding path with a low energy barrier between two structures of every\n"
+                                                     "record on the GPU (rafft_amd.findpath_batch; the direct-path search of ViennaRNA's findpath: only the\n"
+                                                     "pairs in which the two structures differ are removed or added).  A record of FILE is an optional\n"
+                                                     "`>name` line, then three lines: the sequence, the start structure, the end structure (dot-brackets of\n"
+                                                     "the sequence's length); empty lines are skipped.  Per record the output is the `>name` line if there was\n"
+                                                     "one, the sequence, one line `structure energy` per structure of the path from start to end, and a\n"
+                                                     "line `saddle S barrier B kcal/mol` - S the highest energy of the path, B = S minus the start's energy.\n"
+                                                     "Not with any of the other modes")),
+    (("--width",), dict(type=int, default=16, metavar="W", help="with --findpath: partial paths kept per step, 1 .. 1024 (default 16); more finds lower\n"
+                                                                 "barriers and takes longer")),
+    (("--both",), dict(action="store_true", help="with --findpath: search from the end to the start as well and report the path with the lower saddle")),
     (("--seed",), dict(type=int, default=0, help="with --sample: the seed (default 0); the same seed gives the same structures")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
@@ -316,6 +327,56 @@ def main_subopt(args, seqs, known, names, subopt_batch=None, scorer=None):
         sys.stdout.write(text)
 
 
+def read_findpath_records(path):
+    """(names, sequences, starts, ends) of a --findpath file: per record an optional `>name` line, then sequence, start, end"""
+    names, seqs, starts, ends = [], [], [], []
+    name, cur = None, []
+    for ln in open(path):
+        ln = ln.strip()
+        if not ln:
+            continue
+        if ln.startswith(">"):
+            if cur:
+                raise SystemExit(f"{path}: `{ln}` inside a record (a record is sequence, start, end)")
+            name = ln
+            continue
+        cur.append(ln)
+        if len(cur) == 3:
+            names.append(name); seqs.append(cur[0].replace("T", "U")); starts.append(cur[1]); ends.append(cur[2])
+            name, cur = None, []
+    if cur:
+        raise SystemExit(f"{path}: the last record is incomplete (a record is sequence, start, end)")
+    return names, seqs, starts, ends
+
+
+def main_findpath(args, findpath_batch=None):
+    """--findpath: a low-barrier direct path between the two structures of every record instead of the fold"""
+    if args.mfe or args.pf or args.sample is not None or args.subopt is not None or args.kin or args.traj or args.scores:
+        raise SystemExit("--findpath gives a folding path between two given structures: no --mfe, no --pf, no --sample, no --subopt, no --kin, no --traj, no --scores")
+    if args.seq_file is None:
+        raise SystemExit("--findpath needs -sf FILE with records of sequence, start structure, end structure")
+    if not 1 <= args.width <= 1024:
+        raise SystemExit("--width is 1 .. 1024")
+    names, seqs, starts, ends = read_findpath_records(args.seq_file)
+    from .findpath import path_rows
+    if findpath_batch is None:
+        from .findpath import findpath_batch
+    recs, moves, dcal = findpath_batch(seqs, starts, ends, args.width, args.both, args.temp)
+    lines = []
+    for k, s in enumerate(seqs):
+        if names[k]:
+            lines.append(names[k])
+        lines.append(s)
+        lines += [f"{row} {e / 100.0:7.2f}" for row, e in zip(path_rows(starts[k], moves[k]), dcal[k].tolist())]
+        lines.append(f"saddle {recs[k]['saddle_dcal'] / 100.0:.2f} barrier {(recs[k]['saddle_dcal'] - recs[k]['start_dcal']) / 100.0:.2f} kcal/mol")
+    text = "".join(ln + "\n" for ln in lines)
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def _table_note():
     """one line on stderr when the fold used rule / model values of the built-in tables (never with ViennaRNA's own tables loaded)"""
     try:
@@ -338,6 +399,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch, and the callable (sequences, delta,
     max_structs, temp) that stands in for wuchty.subopt_batch)."""
     args = parse_arguments(argv)
+    if args.findpath:
+        return main_findpath(args)
     seqs, known, names = read_records(args)
     if args.subopt is not None and (args.mfe or args.pf or args.sample is not None or args.kin or args.traj):
         raise SystemExit(SUBOPT_EXCLUSIVE)

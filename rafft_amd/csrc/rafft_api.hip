@@ -31,7 +31,7 @@
 #include <pthread.h>
 
 // kernels (rafft_kernels.hip - the shared device helpers, which in turn includes one file per fold kernel: rafft_expand.hip,
-// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip - is compiled into the same translation
+// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip - is compiled into the same translation
 // unit so the templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
@@ -50,7 +50,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -392,6 +392,28 @@ int rafft_subopt_batch(int n_seq, const char *const *seqs, const int *lens, doub
 void rafft_subopt_free(rafft_subopt_result *r)
 {
     if (r && r->_owner) delete (SuboptOwner *)r->_owner;
+}
+
+int rafft_findpath_batch(int n_paths, const char *const *seqs, const int *lens, const char *const *starts, const char *const *ends, const int *widths,
+                         double temp, long long workspace_bytes, rafft_findpath_rec *rec_out, int *const *moves_out, int *const *dcal_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_paths < 0 || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_paths > 0 && (!seqs || !lens || !starts || !ends || !widths || !rec_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int p = 0; p < n_paths; p++) {
+        if (!starts[p] || !ends[p] || (lens[p] > 0 && !seqs[p])) return fail(RAFFT_ERR_PARAM, "problem " + std::to_string(p) + ": null pointer");
+        if (widths[p] < 1 || widths[p] > RAFFT_FINDPATH_MAX_WIDTH)
+            return fail(RAFFT_ERR_PARAM, "problem " + std::to_string(p) + ": width outside 1.." + std::to_string(RAFFT_FINDPATH_MAX_WIDTH));
+    }
+    return findpath_batch(n_paths, seqs, lens, starts, ends, widths, temp, workspace_bytes, rec_out, moves_out, dcal_out);
+}
+
+int rafft_findpath_counters(long long out[4])
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = g_findpath_counters[k];
+    return 0;
 }
 
 int rafft_subopt_counters(long long out[7])

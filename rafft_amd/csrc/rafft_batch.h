@@ -1,7 +1,7 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
-// function and pair probabilities), sample_batch (structures drawn from the ensemble) and subopt_batch (every structure within an
-// energy band), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
+// function and pair probabilities), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
+// energy band) and findpath_batch (folding barriers between structure pairs), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
 // sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
 // the launches.  The sequence drivers share their opening (SeqCall) and their view of a chunk (ChunkView).
@@ -648,6 +648,124 @@ int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double tem
         g_subopt_counters[6] += us(t1, clk::now());
     }
     return finish(err);
+}
+
+// ---- folding barriers between structure pairs
+
+constexpr size_t FINDPATH_WORKSPACE = (size_t)512 << 20;
+
+// of the last call: chunks, levels over all chunks, kernel launches, problems that ran
+long long g_findpath_counters[4];
+
+// rafft_findpath_batch (arguments validated by the entry point).  One pack of the sequences; per problem without a sequence error
+// the moves and conflict masks (findpath_moves), then the capacity check; the problems that are left are laid out in chunks
+// (findpath_layout).  Per chunk: one upload of the inputs, findpath_init_kernel, per level of the chunk's largest d
+// findpath_expand_kernel over (states, problems) and findpath_select_kernel over problems, findpath_trace_kernel, one download of the
+// outputs and of the records, one synchronise.
+int findpath_batch(int n_paths, const char *const *seqs, const int *lens, const char *const *starts, const char *const *ends, const int *widths,
+                   double temp, long long workspace_bytes, rafft_findpath_rec *rec_out, int *const *moves_out, int *const *dcal_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    for (long long &c : g_findpath_counters) c = 0;
+    if (n_paths == 0) return 0;
+    const SeqPack pk = pack_sequences(n_paths, seqs, lens, RAFFT_FINDPATH_MAX_LEN);
+    std::string err = pk.first_err.empty() ? std::string() : "problem " + pk.first_err.substr(9);      // ("sequence N: ..." of the pack)
+    std::vector<FpMoves> mv(n_paths);
+    std::vector<int> run, d(n_paths, 0), n_rem(n_paths, 0);
+    for (int p = 0; p < n_paths; p++) {
+        rec_out[p] = rafft_findpath_rec{pk.status[p], 0, 0, 0, 0, 0, 0, 0};
+        if (pk.status[p]) continue;
+        const std::string who = "problem " + std::to_string(p);
+        if (int st = findpath_moves(pk.codes.data() + pk.code_off[p], pk.L[p], starts[p], ends[p], mv[p])) {
+            rec_out[p].status = st;
+            if (err.empty()) err = who + ": a row is malformed, of another length than the sequence, or holds a non-canonical pair";
+            continue;
+        }
+        d[p] = rec_out[p].dist = mv[p].d; n_rem[p] = mv[p].n_rem;
+        if ((long long)widths[p] * d[p] > RAFFT_FINDPATH_MAX_CANDIDATES) {
+            rec_out[p].status = RAFFT_ERR_CAPACITY;
+            if (err.empty())
+                err = who + ": width " + std::to_string(widths[p]) + " x " + std::to_string(d[p]) + " moves is above RAFFT_FINDPATH_MAX_CANDIDATES";
+            continue;
+        }
+        run.push_back(p);
+    }
+    g_err = err;
+    if (run.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    const FpLayout y = findpath_layout(n_paths, run, pk.L.data(), d.data(), n_rem.data(), widths, pk.code_off.data(),
+                                       workspace_bytes > 0 ? (size_t)workspace_bytes : FINDPATH_WORKSPACE);
+    FpProb *d_ps; FpRec *d_rec; int *d_order; unsigned char *d_in, *d_out, *d_ws;
+    if (int rc = mem.alloc(d_ps, y.ps.size() * sizeof(FpProb))) return rc;
+    if (int rc = mem.alloc(d_rec, y.ps.size() * sizeof(FpRec))) return rc;
+    if (int rc = mem.alloc(d_order, run.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_in, y.max_in + 16)) return rc;
+    if (int rc = mem.alloc(d_out, y.max_out + 16)) return rc;
+    if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_ps, y.ps.data(), y.ps.size() * sizeof(FpProb), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, run.data(), run.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, y.ps.size() * sizeof(FpRec), st));
+    std::vector<unsigned char> in(y.max_in + 16), out(y.max_out + 16);
+    std::vector<FpRec> rec(n_paths);
+    g_findpath_counters[0] = (long long)y.plan.chunks.size();
+    g_findpath_counters[3] = (long long)run.size();
+    for (size_t ci = 0; ci < y.plan.chunks.size(); ci++) {
+        const ChunkPlan::Range &c = y.plan.chunks[ci];
+        const unsigned ny = (unsigned)(c.b - c.a);
+        int Lmax = 0, Wmax = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            const int p = run[k], L = pk.L[p];
+            const FpProb &q = y.ps[p];
+            const FpMoves &m = mv[p];
+            unsigned char *at = in.data() + q.in_off;
+            memset(at, 0, (size_t)fp_in_conf_off(L, q.d));
+            memcpy(at, m.pt_a.data(), (size_t)L * 2);
+            memcpy(at + fp_in_pt_bytes(L), m.pt_b.data(), (size_t)L * 2);
+            if (q.d) memcpy(at + fp_in_moves_off(L), m.moves.data(), (size_t)q.d * 4);
+            if (!m.conf.empty()) memcpy(at + fp_in_conf_off(L, q.d), m.conf.data(), m.conf.size() * 8);
+            Lmax = std::max(Lmax, L);
+            Wmax = std::max(Wmax, q.d < 30 ? std::min(widths[p], 1 << q.d) : widths[p]);      // (a level holds at most 2^d states)
+        }
+        const int *ord = d_order + c.a;
+        const int dmax = y.chunk_dmax[ci], lds_pt = fp_expand_lds_pt(Lmax);
+        HIPCHK(hipMemcpyAsync(d_in, in.data(), y.chunk_in[ci], hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(findpath_init_kernel<0>, dim3(ny), dim3(64), 0, st, g.T, d_ps, ord, sc.d_codes, d_in, d_ws, d_rec);
+        HIPCHK(hipGetLastError());
+        for (int level = 0; level < dmax; level++) {
+            hipLaunchKernelGGL(findpath_expand_kernel<0>, dim3((unsigned)Wmax, ny), dim3(64), (size_t)fp_expand_lds_bytes(Lmax, dmax), st, g.T, d_ps, ord, sc.d_codes,
+                               d_in, d_ws, d_rec, level, lds_pt);
+            hipLaunchKernelGGL(findpath_select_kernel<0>, dim3(ny), dim3(FP_SEL_NT), 0, st, d_ps, ord, d_ws, d_rec, level);
+        }
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(findpath_trace_kernel<0>, dim3((ny + 63) / 64), dim3(64), 0, st, (int)ny, d_ps, ord, d_in, d_ws, d_out, d_rec);
+        HIPCHK(hipGetLastError());
+        g_findpath_counters[1] += dmax;
+        g_findpath_counters[2] += 2 + 2 * (long long)dmax;
+        HIPCHK(hipMemcpyAsync(out.data(), d_out, y.chunk_out[ci], hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rec.data(), d_rec, y.ps.size() * sizeof(FpRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = c.a; k < c.b; k++) {
+            const int p = run[k];
+            const FpProb &q = y.ps[p];
+            const FpRec &r = rec[p];
+            const std::string who = "problem " + std::to_string(p);
+            if (r.flags & (FP_BAD_PAIR | FP_STUCK)) return fail(RAFFT_ERR_HIP, "internal: " + who + ((r.flags & FP_STUCK) ? ": a level without a candidate" : ": a non-canonical pair on the device"));
+            if (r.flags & FP_RANGE) {
+                rec_out[p].status = RAFFT_ERR_CAPACITY;
+                if (err.empty()) err = who + ": an energy of the path is outside what the sort key holds (|energy| >= " + std::to_string(FINDPATH_BIAS) + " dcal)";
+                continue;
+            }
+            if (r.end != r.end_eval) return fail(RAFFT_ERR_HIP, "internal: " + who + ": the path ends at another energy than the end structure has");
+            rec_out[p] = rafft_findpath_rec{0, q.d, q.d, r.start, r.end, r.saddle, r.saddle_step, 0};
+            if (moves_out && moves_out[p] && q.d) memcpy(moves_out[p], out.data() + q.out_off, (size_t)q.d * 8);
+            if (dcal_out && dcal_out[p]) memcpy(dcal_out[p], out.data() + q.out_off + fp_out_dcal_off(q.d), ((size_t)q.d + 1) * 4);
+        }
+    }
+    g_err = err;
+    return 0;
 }
 
 } // namespace

@@ -1,6 +1,6 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip and rafft_subopt.hip read and write, and the sizes both sides compute (the LDS
-// of the MFE and sampling kernels, a state of the enumeration, its packed copy).  The layouts that fill the records are in
+// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip and rafft_findpath.hip read and write, and the sizes both sides
+// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
 
@@ -80,3 +80,50 @@ struct SuboptRec {
 
 // the packed copy of n finished states, in the buffer that is not the final one: n rows of L + 1 bytes, then at this offset n energies
 RAFFT_HD inline unsigned long long subopt_pack_dcal_off(int n, int L) { return ((unsigned long long)n * (unsigned long long)(L + 1) + 15ull) & ~15ull; }
+
+// ---- folding barriers between structure pairs (rafft_findpath.hip)
+
+#define FINDPATH_KEY_BITS 22                                // of the biased saddle and of the biased energy in a candidate's key
+#define FINDPATH_BIAS (1 << (FINDPATH_KEY_BITS - 1))        // an energy e is held when -FINDPATH_BIAS < e < FINDPATH_BIAS
+#define FINDPATH_INDEX_BITS 20                              // parent rank * d + move number: below RAFFT_FINDPATH_MAX_CANDIDATES
+
+RAFFT_HD constexpr unsigned long long fp_align16(unsigned long long x) { return (x + 15ull) & ~15ull; }
+// 64-bit words of a mask over d moves (one at least)
+RAFFT_HD constexpr int fp_mask_words(int d) { return d > 64 ? (d + 63) / 64 : 1; }
+
+// What a problem of L positions, d moves of which n_rem are removals, and width W has on the device.  Its inputs, in the chunk's
+// input buffer from in_off: the pair tables of A and B (int16, -1 = unpaired), the moves as (i | j << 16), removals first, and per
+// addition its conflict mask.  Its outputs, in the chunk's output buffer from out_off: d moves as (i, j) ints, d + 1 energies.
+// Its work area, in the chunk's workspace from ws_off: two beams of W masks and W (energy, saddle) pairs, W d candidate keys,
+// and per level W records (parent rank | move << 16, energy) of the kept states.
+RAFFT_HD constexpr unsigned long long fp_in_pt_bytes(int L) { return fp_align16(2ull * (unsigned long long)L); }
+RAFFT_HD constexpr unsigned long long fp_in_moves_off(int L) { return 2 * fp_in_pt_bytes(L); }
+RAFFT_HD constexpr unsigned long long fp_in_conf_off(int L, int d) { return fp_in_moves_off(L) + fp_align16(4ull * (unsigned long long)d); }
+RAFFT_HD constexpr unsigned long long fp_in_bytes(int L, int d, int n_rem)
+{
+    return fp_in_conf_off(L, d) + (unsigned long long)(d - n_rem) * (unsigned long long)fp_mask_words(d) * 8ull;
+}
+RAFFT_HD constexpr unsigned long long fp_out_dcal_off(int d) { return fp_align16(8ull * (unsigned long long)d); }
+RAFFT_HD constexpr unsigned long long fp_out_bytes(int d) { return fp_out_dcal_off(d) + fp_align16(4ull * ((unsigned long long)d + 1)); }
+RAFFT_HD constexpr unsigned long long fp_ws_mask_bytes(int d, int W) { return (unsigned long long)W * (unsigned long long)fp_mask_words(d) * 8ull; }
+RAFFT_HD constexpr unsigned long long fp_ws_es_off(int d, int W) { return 2 * fp_ws_mask_bytes(d, W); }                 // two beams of W (energy, saddle)
+RAFFT_HD constexpr unsigned long long fp_ws_keys_off(int d, int W) { return fp_ws_es_off(d, W) + 2ull * (unsigned long long)W * 8ull; }
+RAFFT_HD constexpr unsigned long long fp_ws_back_off(int d, int W) { return fp_ws_keys_off(d, W) + (unsigned long long)W * (unsigned long long)d * 8ull; }
+RAFFT_HD constexpr unsigned long long fp_ws_bytes(int d, int W) { return fp_ws_back_off(d, W) + (unsigned long long)W * (unsigned long long)d * 8ull; }
+
+struct FpProb {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long in_off;      // first byte of its inputs in the chunk's input buffer
+    unsigned long long out_off;     // first byte of its outputs in the chunk's output buffer
+    unsigned long long ws_off;      // first byte of its work area in the chunk's workspace
+    int L, d, n_rem, W;
+};
+struct FpRec {
+    int n_cur, n_keys;              // states of the current beam; candidate keys written in this level
+    int flags;                      // FP_*
+    int start, end, end_eval;       // energies of A and of survivor 0; of B as eval_kernel sums it (they must agree)
+    int saddle, saddle_step;
+};
+#define FP_RANGE 1                  // an energy outside what a key holds
+#define FP_BAD_PAIR 2               // a non-canonical pair met on the device (the host refuses them: cannot happen)
+#define FP_STUCK 4                  // a level without a candidate (cannot happen: a legal move always exists)

@@ -1,8 +1,9 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
 // that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
-// (chunks within a budget, the sequence pack, the graph pack, the solve order, and the layouts of the four sequence drivers: every
-// offset their kernels dereference, as records of rafft_batch_layout.h).  Plain C++ (g++ compiles it alone:
-// tests/hostcheck/hostpure_check.cpp).  Part of the single translation unit of rafft_api.hip (included there, before the kernels).
+// (chunks within a budget, the sequence pack, the graph pack, the solve order, the layouts of the four sequence drivers: every
+// offset their kernels dereference, as records of rafft_batch_layout.h - and the moves, conflict masks and layout of findpath).
+// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp).  Part of the single translation unit
+// of rafft_api.hip (included there, before the kernels).
 #pragma once
 
 #include "../../include/rafft_hip.h"
@@ -380,6 +381,85 @@ static SuboptLayout subopt_layout(const SeqPack &pk, int max_structs, size_t bud
             at += y.front_bytes[k];
         }
         y.max_seqs = std::max(y.max_seqs, c.b - c.a);
+    }
+    return y;
+}
+
+// ---- rafft_findpath_batch: a problem from its rows, and the layout of a call
+
+// The moves of a direct path from row a to row b over the bases `codes` (kBaseCode, L of them): the pairs of A not in B, ascending
+// 5' end, then the pairs of B not in A, ascending 5' end, as (i | j << 16); per addition the mask of the removals that cross it or
+// share a base with it (fp_mask_words(d) words, bit m = move m) - the addition is legal once they are all applied.  Returns
+// RAFFT_ERR_STRUCT for a row of another length than L, a character outside ( ) . , an unbalanced row or a non-canonical pair.
+struct FpMoves {
+    std::vector<int16_t> pt_a, pt_b;
+    std::vector<uint32_t> moves;
+    std::vector<uint64_t> conf;         // (d - n_rem) x fp_mask_words(d)
+    int n_rem = 0, d = 0;
+};
+static bool fp_canonical(int a, int b) { return (a == 2 && b == 3) || (a == 3 && b == 2) || (a == 3 && b == 4) || (a == 4 && b == 3) || (a == 1 && b == 4) || (a == 4 && b == 1); }
+static int findpath_moves(const uint8_t *codes, int L, const char *a, const char *b, FpMoves &o)
+{
+    o = FpMoves{};
+    if (!a || !b || strlen(a) != (size_t)L || strlen(b) != (size_t)L) return RAFFT_ERR_STRUCT;
+    if (!parse_db(a, L, o.pt_a) || !parse_db(b, L, o.pt_b)) return RAFFT_ERR_STRUCT;
+    for (int i = 0; i < L; i++) {
+        if (o.pt_a[i] > i && !fp_canonical(codes[i], codes[o.pt_a[i]])) return RAFFT_ERR_STRUCT;
+        if (o.pt_b[i] > i && !fp_canonical(codes[i], codes[o.pt_b[i]])) return RAFFT_ERR_STRUCT;
+    }
+    for (int i = 0; i < L; i++) if (o.pt_a[i] > i && o.pt_b[i] != o.pt_a[i]) o.moves.push_back((uint32_t)i | ((uint32_t)o.pt_a[i] << 16));
+    o.n_rem = (int)o.moves.size();
+    for (int i = 0; i < L; i++) if (o.pt_b[i] > i && o.pt_a[i] != o.pt_b[i]) o.moves.push_back((uint32_t)i | ((uint32_t)o.pt_b[i] << 16));
+    o.d = (int)o.moves.size();
+    const int mw = fp_mask_words(o.d);
+    o.conf.assign((size_t)(o.d - o.n_rem) * mw, 0);
+    for (int m = o.n_rem; m < o.d; m++) {
+        const int i = (int)(o.moves[m] & 0xffffu), j = (int)(o.moves[m] >> 16);
+        for (int r = 0; r < o.n_rem; r++) {
+            const int p = (int)(o.moves[r] & 0xffffu), q = (int)(o.moves[r] >> 16);
+            const bool share = p == i || p == j || q == i || q == j;
+            const bool cross = (p < i && i < q && q < j) || (i < p && p < j && j < q);
+            if (share || cross) o.conf[(size_t)(m - o.n_rem) * mw + (r >> 6)] |= 1ull << (r & 63);
+        }
+    }
+    return 0;
+}
+
+// The problems `run` (those without an error, in input order) of a call: chunks of whole problems whose work areas (primary cost)
+// and whose inputs and outputs together (second cost) fit the budget each, one problem at least.  Per chunk the inputs lie back to
+// back from byte 0 of the input buffer, the outputs from byte 0 of the output buffer, the work areas from byte 0 of the workspace.
+struct FpLayout {
+    std::vector<FpProb> ps;             // one per problem of the call (zeros for a problem with an error)
+    std::vector<size_t> ws_bytes, io_bytes;         // per problem of `run`
+    ChunkPlan plan;                     // over `run`
+    std::vector<size_t> chunk_in, chunk_out;        // bytes of a chunk's inputs / outputs
+    std::vector<int> chunk_dmax;        // the levels of a chunk
+    size_t max_in = 0, max_out = 0;
+};
+static FpLayout findpath_layout(int n_paths, const std::vector<int> &run, const int *L, const int *d, const int *n_rem, const int *W,
+                                const unsigned long long *code_off, size_t budget)
+{
+    FpLayout y;
+    y.ps.assign((size_t)n_paths, FpProb{0, 0, 0, 0, 0, 0, 0, 0});
+    y.ws_bytes.resize(run.size()); y.io_bytes.resize(run.size());
+    for (size_t k = 0; k < run.size(); k++) {
+        const int p = run[k];
+        y.ws_bytes[k] = (size_t)fp_ws_bytes(d[p], W[p]);
+        y.io_bytes[k] = (size_t)(fp_in_bytes(L[p], d[p], n_rem[p]) + fp_out_bytes(d[p]));
+    }
+    y.plan = plan_chunks(run.size(), y.ws_bytes.data(), y.io_bytes.data(), budget, 65535);
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        size_t in = 0, out = 0;
+        int dmax = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            const int p = run[k];
+            y.ps[p] = FpProb{code_off[p], in, out, y.plan.off[k], L[p], d[p], n_rem[p], W[p]};
+            in += (size_t)fp_in_bytes(L[p], d[p], n_rem[p]);
+            out += (size_t)fp_out_bytes(d[p]);
+            dmax = std::max(dmax, d[p]);
+        }
+        y.chunk_in.push_back(in); y.chunk_out.push_back(out); y.chunk_dmax.push_back(dmax);
+        y.max_in = std::max(y.max_in, in); y.max_out = std::max(y.max_out, out);
     }
     return y;
 }

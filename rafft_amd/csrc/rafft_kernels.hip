@@ -24,6 +24,8 @@
 //                       expansion (no counterpart in the reference, which recomputes)
 //   output_kernel       (rafft_io_kernels.hip, with stage_in_kernel and init_roots_kernel) gathers dot-bracket rows (rafft/utils.py:42-50)
 //   eval_kernel         (rafft_io_kernels.hip) whole-structure energy (rafft/utils.py:135-138), C-ABI hook
+//   findpath_*_kernel   (rafft_findpath.hip) folding barriers between structure pairs: not part of the fold, but built on
+//                       loop_energy, PlainView's kin and the radix select below
 //
 // This is bandwidth/latency-bound small-FFT + integer table work: no MFMA.
 #include "rafft_kernels.h"
@@ -173,3 +175,4 @@ struct PlainView {
 #include "rafft_beam.hip"               // beam_step_kernel, the seen table
 #include "rafft_materialize.hip"        // materialize_kernel, materialize_team_kernel, dedupe_kernel
 #include "rafft_io_kernels.hip"         // stage_in_kernel, init_roots_kernel, output_kernel, eval_kernel
+#include "rafft_findpath.hip"           // findpath_init_kernel, findpath_expand_kernel, findpath_select_kernel, findpath_trace_kernel

@@ -138,6 +138,51 @@ def rate_matrix_gpu(fast_paths, kt=KT):
     return rate, struct_list, energy
 
 
+def barrier_rates(rate, energy, saddle, kt=KT):
+    """The rate matrix with Arrhenius rates over the saddles instead of Metropolis rates: the Metropolis rate min(1, exp(-dE/kt)) of
+    an edge assumes that its saddle is max(E_i, E_j); with the saddle S_ij of a folding path between the two structures
+    (findpath_batch), rate[i][j] and rate[j][i] are both multiplied by exp(-(max(S_ij, E_i, E_j) - max(E_i, E_j)) / kt) and the diagonal
+    is recomputed as minus the row sums.  The clamp keeps a rate from rising when `energy` comes from other tables than the saddles;
+    the factor is symmetric (the upper triangle of `saddle` is used for both directions), so detailed balance with respect to
+    `energy` is kept and every solver of solve_master_equation stays valid.  numpy arrays, kcal/mol; entries of `saddle` where
+    `rate` is 0 are not looked at."""
+    rate = np.array(rate, dtype=np.float64)
+    energy = np.asarray(energy, dtype=np.float64)
+    sad = np.triu(np.asarray(saddle, dtype=np.float64), 1)
+    sad = sad + sad.T
+    top = np.maximum(energy[:, None], energy[None, :])
+    off = rate != 0.0
+    np.fill_diagonal(off, False)
+    excess = np.where(off, np.maximum(sad, top) - top, 0.0)
+    out = np.where(off, rate * np.exp(-excess / kt), 0.0)
+    np.fill_diagonal(out, -out.sum(axis=1))
+    return out
+
+
+def edge_saddles(sequence, struct_list, rate, width=16, temp=37.0):
+    """S x S saddles in kcal/mol of the edges of a graph: one findpath_batch call (both directions, the lower saddle) over the pairs
+    i < j with a non-zero rate; 0 elsewhere"""
+    from .findpath import findpath_batch
+    rate = np.asarray(rate)
+    ii, jj = np.nonzero(np.triu((rate != 0.0) | (rate.T != 0.0), 1))
+    sad = np.zeros(rate.shape, dtype=np.float64)
+    if len(ii):
+        recs, _, _ = findpath_batch([sequence] * len(ii), [struct_list[i].str_struct for i in ii], [struct_list[j].str_struct for j in jj],
+                                    width, both=True, temp=temp)
+        for i, j, r in zip(ii.tolist(), jj.tolist(), recs):
+            sad[i, j] = sad[j, i] = r["saddle_dcal"] / 100.0
+    return sad
+
+
+def barrier_graph(fast_paths, sequence, width=16, kt=KT):
+    """dict(rate, barrier_rate, energy, saddle, struct_list) of a graph: the Metropolis matrix of rate_matrix_gpu, the saddles of its
+    edges and the matrix barrier_rates makes of them (numpy)"""
+    rate, struct_list, energy = rate_matrix_gpu(fast_paths, kt)
+    rate = rate.cpu().numpy()
+    saddle = edge_saddles(sequence, struct_list, rate, width)
+    return dict(rate=rate, barrier_rate=barrier_rates(rate, energy, saddle, kt), energy=energy, saddle=saddle, struct_list=struct_list)
+
+
 def kinetics_schedule(max_time=None, n_steps=None, substeps=32, sample_times=None):
     """-> (sample_times, m, h): the output times and the TR-BDF2 schedule between them, the one place both come from
     (solve_master_equation, kinetics_gpu, kinetics_batch).  sample_times: exp(k * max_time / n_steps - 4), k < n_steps
@@ -228,14 +273,20 @@ def solve_master_equation(rate, energy, p0, sample_times, method="auto", substep
     return np.stack(out)
 
 
-def kinetics_gpu(fast_paths, max_time, n_steps, initial_pop=None, method="auto", substeps=32, kt=KT):
+def kinetics_gpu(fast_paths, max_time, n_steps, initial_pop=None, method="auto", substeps=32, kt=KT, barriers=0, sequence=None):
     """Same contract as `kinetics` (rafft_kin.py:94-150).  The rate matrix (inclusion search + Metropolis rates) is computed on
     the MI355X; the master equation is solved on the device (spectral, implicit-dense) or - the sparse TR-BDF2 integrator that
     `implicit` and, beyond 30 KT of energy span, `auto` use - on the host from the non-zeros (see solve_master_equation).  Returns
     (trajectory, times, struct_list, str_equi_pop); trajectory rows are float64 numpy arrays.  `kt` goes to the rate matrix and
-    to the solver alike."""
+    to the solver alike.  barriers=W > 0 (needs `sequence`): the rates go over the saddles of folding paths of width W between the
+    structures of every edge (barrier_rates) instead of max(E_i, E_j)."""
     import torch
     rate, struct_list, energy = rate_matrix_gpu(fast_paths, kt)
+    if barriers:
+        if not sequence:
+            raise ValueError("barriers needs the sequence of the graph")
+        host = rate.cpu().numpy()
+        rate = torch.as_tensor(barrier_rates(host, energy, edge_saddles(sequence, struct_list, host, barriers), kt), device=rate.device)
     S = len(struct_list)
     p0 = torch.zeros(S, dtype=torch.float64, device=rate.device)
     if initial_pop is None:
@@ -413,7 +464,15 @@ def main(argv=None):
                         help="with --gpu: spectral = the reference's formula (device, rocSOLVER syevd; valid up to ~30 KT of energy span),\n"
                              "implicit = TR-BDF2 with sparse LU of the generator's non-zeros (host, SciPy SuperLU; dense device path\n"
                              "without SciPy), implicit-dense = the same with dense getrf on the device, auto = whichever is valid")
+    parser.add_argument('--barriers', type=int, default=0, metavar="W",
+                        help="with --gpu: the rate of every edge of the graph goes over the saddle of a folding path between its two\n"
+                             "structures (rafft_amd.findpath_batch, width W, both directions) instead of max(E_i, E_j): both directions\n"
+                             "of the edge are multiplied by exp(-(max(S, E_i, E_j) - max(E_i, E_j)) / KT).  0 (default): Metropolis rates")
     args = parser.parse_args(argv)
+    if args.barriers and not args.gpu:
+        raise SystemExit("--barriers needs --gpu")
+    if args.barriers < 0 or args.barriers > 1024:
+        raise SystemExit("--barriers is a width of 1 .. 1024")
     init_population = None
     if args.init_pop is not None:     # the reference crashes here (None += ...); we accept the documented syntax
         init_population = [(int(el.split(":")[0]), float(el.split(":")[1])) for el in args.init_pop]
@@ -422,7 +481,8 @@ def main(argv=None):
     else:
         fast_paths, seq = parse_rafft_output(args.rafft_out)
     if args.gpu:
-        trajectory, times, struct_list, equi_pop = kinetics_gpu(fast_paths, args.max_time, args.n_steps, init_population, args.method)
+        trajectory, times, struct_list, equi_pop = kinetics_gpu(fast_paths, args.max_time, args.n_steps, init_population, args.method,
+                                                                barriers=args.barriers, sequence=seq)
     else:
         trajectory, times, struct_list, equi_pop = kinetics(fast_paths, args.max_time, args.n_steps, init_population)
     equi_pop.sort(key=lambda el: el[2])
