@@ -518,6 +518,56 @@ int rafft_findpath_batch(int n_paths, const char *const *seqs, const int *lens, 
 /* of the last rafft_findpath_batch: chunks, levels over all chunks, kernel launches, problems that ran */
 int rafft_findpath_counters(long long out[4]);
 
+/* Gradient walks to local minima.  Replaces: RNA.fold_compound(seq).path_gradient(pt) / ViennaRNA's
+ * vrna_path_gradient, RNAlocmin and the flooding of `barriers`, what a user of the reference takes from ViennaRNA to ask which
+ * basin of the energy landscape a structure belongs to.
+ * One call, n_seq sequences with n_rows[s] start rows each, in the shape of rafft_score_rows: rows[s] holds the rows of sequence s,
+ * lens[s] characters of ( ) . each, row_stride[s] >= lens[s] bytes apart - as rafft_sample_batch, rafft_subopt_seq.db and
+ * rafft_seq_result.db leave them.  Every row is walked on its own.
+ * The walk is defined exactly, so same input, same bits.  The neighbours of a structure (ViennaRNA's default move set: insertion
+ * and deletion, lonely pairs allowed) are the removal of any of its pairs and the addition of any (i, j), i < j, whose positions are
+ * both unpaired and lie in the same loop (nothing present crosses the new pair), with j - i > 3 and a canonical pair of bases (AU,
+ * UA, GC, CG, GU, UG; N pairs with nothing).  The change dE of a neighbour is formed from the loop energies rafft_eval_structure
+ * uses - the enclosing loop before and after the move and the moved pair's own loop - so whatever rafft_eval_structure allows is
+ * allowed on the way (interior loops above 30 among it).  A step takes, among the neighbours with dE < 0, the one with the smallest
+ * (dE, i, j); a position pair is either a removal or an addition, so the key is unique.  With no neighbour below 0 the structure is
+ * the end: a local minimum.  Plateaus (dE = 0) are not walked; the energy strictly falls, so the walk ends.
+ * max_steps: a walk that has taken max_steps steps and could take another stops with RAFFT_ERR_CAPACITY; the row it reached, its
+ * energy and n_steps are returned and the caller may continue from there.  0 means 2 * lens[s] + 16.
+ * Outputs (host): seq_out[s]; row_out[seq_out[s].row0 + r]; db_out[s] = n_rows[s] rows, lens[s] + 1 bytes apart, NUL terminated;
+ * moves_out may be NULL and so may moves_out[s] (then no device buffer for moves exists), else n_rows[s] blocks of 2 * bound ints,
+ * bound = max_steps or 2 * lens[s] + 16: step k of row r is (block[2k], block[2k+1]) = (i, j) 0-based for an added pair,
+ * (-i-1, -j-1) for a removed one.  rafft_eval_structure of the start row gives start_dcal, of the end row end_dcal, of any row of
+ * the path the running sum.
+ * Errors of that sequence only (status in seq_out[s] and in each of its row records, its rows all dots): RAFFT_ERR_BAD_CHAR,
+ * RAFFT_ERR_EMPTY, RAFFT_ERR_TOO_LONG (above RAFFT_DESCEND_MAX_LEN).  Errors of that row only: RAFFT_ERR_STRUCT (a character
+ * outside ( ) . - a NUL before lens[s] among them - an unbalanced row, a non-canonical pair, a hairpin of fewer than 3; the row
+ * comes back as it went in) and RAFFT_ERR_CAPACITY as above.  For these the call returns RAFFT_OK, the neighbours are untouched and
+ * rafft_last_error() names the first such item.  RAFFT_ERR_PARAM, before anything is launched: a null argument, a negative count, a
+ * stride below the length, a negative max_steps or workspace_bytes.  RAFFT_ERR_TEMP as for the fold.  A batch of nothing but
+ * erroneous items never touches the device.  A row's result depends on the sequence, the row, temp, max_steps and the energy tables
+ * only - not on the batch, its order, the chunking or the workspace.
+ * Device memory: walks are taken in chunks of whole walks in input order whose rows (2 * lens[s] bytes) and move buffers fit
+ * workspace_bytes (0: 512 MiB), one walk at least. */
+#define RAFFT_DESCEND_MAX_LEN RAFFT_MFE_MAX_LEN
+typedef struct {
+    int32_t status;
+    int32_t length;        /* lens[s] as reported (0 for a negative one) */
+    int32_t n_rows;
+    int32_t row0;          /* index of the sequence's first record in row_out */
+} rafft_descend_seq;       /* 16 bytes */
+typedef struct {
+    int32_t status;
+    int32_t n_steps;       /* steps taken */
+    int32_t start_dcal;    /* energy of the start row */
+    int32_t end_dcal;      /* energy of the row returned */
+} rafft_descend_row;       /* 16 bytes */
+int rafft_descend_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows,
+                        const int *row_stride, double temp, int max_steps, long long workspace_bytes /* 0: 512 MiB */,
+                        rafft_descend_seq *seq_out, rafft_descend_row *row_out, char *const *db_out, int *const *moves_out);
+/* of the last rafft_descend_batch: chunks, kernel launches, walks that ran, steps over all walks */
+int rafft_descend_counters(long long out[4]);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

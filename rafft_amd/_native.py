@@ -100,6 +100,18 @@ FINDPATH_MAX_LEN = MFE_MAX_LEN           # RAFFT_FINDPATH_MAX_LEN
 FINDPATH_MAX_WIDTH = 1024                # RAFFT_FINDPATH_MAX_WIDTH
 FINDPATH_MAX_CANDIDATES = 1 << 20        # RAFFT_FINDPATH_MAX_CANDIDATES
 
+class DescendSeq(C.Structure):
+    """rafft_descend_seq: one record per sequence of rafft_descend_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("n_rows", C.c_int32), ("row0", C.c_int32)]
+
+
+class DescendRow(C.Structure):
+    """rafft_descend_row: one record per start row of rafft_descend_batch"""
+    _fields_ = [("status", C.c_int32), ("n_steps", C.c_int32), ("start_dcal", C.c_int32), ("end_dcal", C.c_int32)]
+
+
+DESCEND_MAX_LEN = MFE_MAX_LEN            # RAFFT_DESCEND_MAX_LEN
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
@@ -107,7 +119,7 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
            "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
            "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
-           "rafft_findpath_counters"]
+           "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters"]
 
 _lib = None
 
@@ -211,6 +223,10 @@ def lib():
                                        C.POINTER(C.c_int), C.c_double, C.c_longlong, C.POINTER(FindpathRec), C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_void_p)]
     L.rafft_findpath_counters.argtypes = [C.POINTER(C.c_longlong * 4)]
+    L.rafft_descend_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_int), C.c_double, C.c_int, C.c_longlong, C.POINTER(DescendSeq), C.c_void_p,
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_descend_counters.argtypes = [C.POINTER(C.c_longlong * 4)]
     _lib = L
     return L
 

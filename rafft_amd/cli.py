@@ -81,6 +81,15 @@ _OPTIONS = [
     (("--width",), dict(type=int, default=16, metavar="W", help="with --findpath: partial paths kept per step, 1 .. 1024 (default 16); more finds lower\n"
                                                                  "barriers and takes longer")),
     (("--both",), dict(action="store_true", help="with --findpath: search from the end to the start as well and report the path with the lower saddle")),
+    (("--descend",), dict(action="store_true", help="gradient walks to local minima on the GPU (rafft_amd.descend_batch; insertion and deletion of single pairs,\n"
+                                                    "steepest descent, as ViennaRNA's path_gradient).  With --sample N or --subopt DELTA every structure walks down\n"
+                                                    "to its local minimum and the one-step graph holds the distinct minima, energy ascending, each followed by\n"
+                                                    "the number of structures in its basin (`rafft_landscape OUT` draws it).  Alone, with -sf FILE: a record of\n"
+                                                    "FILE is an optional `>name` line, the sequence and one or more dot-bracket lines; per record the output\n"
+                                                    "is the `>name` line if there was one, the sequence and one line `structure energy count` per distinct\n"
+                                                    "minimum its structures walk down to, energy ascending.  Not with --scores, --mfe, --pf, --findpath, --kin, --traj")),
+    (("--max-steps",), dict(type=int, default=0, metavar="N", help="with --descend: a walk that is not at a minimum after N steps is an error (default 0: twice the\n"
+                                                                    "sequence's length + 16, which no walk of the tests came near)")),
     (("--seed",), dict(type=int, default=0, help="with --sample: the seed (default 0); the same seed gives the same structures")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
@@ -283,14 +292,74 @@ def main_sample(args, seqs, known, names, sample_batch=None, scorer=None):
     if sample_batch is None:
         from .mccaskill import sample_batch
     samples = sample_batch(seqs, args.sample, args.seed, args.temp)
-    if args.scores:
+    if args.descend:
+        text = descend_steps(args, seqs, samples)
+    elif args.scores:
         if scorer is None:
             from .scoring import score_rows_gpu as scorer
         write_scores(args.scores, seqs, names, samples, scorer(samples, known), args.select)
         if not args.output:
             return
-    from .utils import format_trajectory
-    text = "".join(format_trajectory(s, [sampled_step(sm)]) for s, sm in zip(seqs, samples))
+    if not args.descend:
+        from .utils import format_trajectory
+        text = "".join(format_trajectory(s, [sampled_step(sm)]) for s, sm in zip(seqs, samples))
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
+def descend_steps(args, seqs, lists, minima_batch=None):
+    """with --descend: per sequence the text of a one-step graph of the distinct minima the structures of lists[s] walk down to,
+    energy ascending (then by first appearance), each with the number of structures in its basin"""
+    if args.scores:
+        raise SystemExit("--descend gives the local minima of the structures: no --scores")
+    if minima_batch is None:
+        from .descend import minima_batch
+    got = minima_batch(seqs, [[st.str_struct for st in sm] for sm in lists], args.temp, args.max_steps)
+    out = []
+    for s, (minima, counts, _) in zip(seqs, got):
+        out.append("".join([s + "\n", "# {:-^20}\n".format(0)] + [f"{m.str_struct} {m.energy:6.1f} {c}\n" for m, c in zip(minima, counts)]))
+    return "".join(out)
+
+
+def read_descend_records(path):
+    """(names, sequences, rows) of a --descend file: per record an optional `>name` line, the sequence, one or more dot-bracket lines"""
+    names, seqs, rows = [], [], []
+    name = None
+    for ln in open(path):
+        ln = ln.strip()
+        if not ln:
+            continue
+        if ln.startswith(">"):
+            name = ln
+        elif set(ln) <= set("().") and seqs and name is None:
+            rows[-1].append(ln)
+        else:
+            names.append(name); seqs.append(ln.replace("T", "U")); rows.append([])
+            name = None
+    if name is not None or any(not r for r in rows):
+        raise SystemExit(f"{path}: a record is an optional `>name` line, the sequence and one or more dot-bracket lines")
+    return names, seqs, rows
+
+
+def main_descend(args, minima_batch=None):
+    """--descend alone: the local minima the structures of every record walk down to"""
+    if args.mfe or args.pf or args.kin or args.traj or args.scores:
+        raise SystemExit("--descend gives the local minima of given structures: no --mfe, no --pf, no --kin, no --traj, no --scores")
+    if args.seq_file is None:
+        raise SystemExit("--descend needs -sf FILE with records of a sequence and its structures, or --sample N / --subopt DELTA")
+    names, seqs, rows = read_descend_records(args.seq_file)
+    if minima_batch is None:
+        from .descend import minima_batch
+    lines = []
+    for k, (minima, counts, _) in enumerate(minima_batch(seqs, rows, args.temp, args.max_steps)):
+        if names[k]:
+            lines.append(names[k])
+        lines.append(seqs[k])
+        lines += [f"{m.str_struct} {m.dcal / 100.0:7.2f} {c}" for m, c in zip(minima, counts)]
+    text = "".join(ln + "\n" for ln in lines)
     if args.output:
         with open(args.output, "w") as out:
             out.write(text)
@@ -312,14 +381,17 @@ def main_subopt(args, seqs, known, names, subopt_batch=None, scorer=None):
     if subopt_batch is None:
         from .wuchty import subopt_batch
     bands = subopt_batch(seqs, args.subopt, args.max_structs, args.temp)
-    if args.scores:
+    if args.descend:
+        text = descend_steps(args, seqs, bands)
+    elif args.scores:
         if scorer is None:
             from .scoring import score_rows_gpu as scorer
         write_scores(args.scores, seqs, names, bands, scorer(bands, known), args.select)
         if not args.output:
             return
-    from .utils import format_trajectory
-    text = "".join(format_trajectory(s, [list(band)]) for s, band in zip(seqs, bands))          # (the library's order)
+    if not args.descend:
+        from .utils import format_trajectory
+        text = "".join(format_trajectory(s, [list(band)]) for s, band in zip(seqs, bands))          # (the library's order)
     if args.output:
         with open(args.output, "w") as out:
             out.write(text)
@@ -400,7 +472,13 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     max_structs, temp) that stands in for wuchty.subopt_batch)."""
     args = parse_arguments(argv)
     if args.findpath:
+        if args.descend:
+            raise SystemExit("--findpath and --descend are two modes")
         return main_findpath(args)
+    if args.max_steps < 0:
+        raise SystemExit("--max-steps is 0 or more")
+    if args.descend and args.sample is None and args.subopt is None:
+        return main_descend(args)
     seqs, known, names = read_records(args)
     if args.subopt is not None and (args.mfe or args.pf or args.sample is not None or args.kin or args.traj):
         raise SystemExit(SUBOPT_EXCLUSIVE)

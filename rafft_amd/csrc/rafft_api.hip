@@ -31,7 +31,7 @@
 #include <pthread.h>
 
 // kernels (rafft_kernels.hip - the shared device helpers, which in turn includes one file per fold kernel: rafft_expand.hip,
-// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip - is compiled into the same translation
+// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip, rafft_descend.hip - is compiled into the same translation
 // unit so the templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
@@ -50,7 +50,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch, descend_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -413,6 +413,37 @@ int rafft_findpath_counters(long long out[4])
     std::lock_guard<std::mutex> lk(g.mu);
     if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
     for (int k = 0; k < 4; k++) out[k] = g_findpath_counters[k];
+    return 0;
+}
+
+int rafft_descend_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                        double temp, int max_steps, long long workspace_bytes, rafft_descend_seq *seq_out, rafft_descend_row *row_out,
+                        char *const *db_out, int *const *moves_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || max_steps < 0 || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_seq > 0 && (!seqs || !lens || !n_rows || !rows || !row_stride || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    long long total = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const std::string who = "sequence " + std::to_string(s);
+        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative row count");
+        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+        if (n_rows[s] > 0) {
+            if (!rows[s] || !db_out[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+            if (row_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
+        }
+        total += n_rows[s];
+    }
+    if (total > 0x7fffffffll) return fail(RAFFT_ERR_PARAM, "more than 2^31 - 1 rows");
+    if (total > 0 && !row_out) return fail(RAFFT_ERR_PARAM, "null argument");
+    return descend_batch(n_seq, seqs, lens, n_rows, rows, row_stride, temp, max_steps, workspace_bytes, seq_out, row_out, db_out, moves_out);
+}
+
+int rafft_descend_counters(long long out[4])
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = g_descend_counters[k];
     return 0;
 }
 

@@ -1,7 +1,7 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
 // function and pair probabilities), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
-// energy band) and findpath_batch (folding barriers between structure pairs), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
+// energy band), findpath_batch (folding barriers between structure pairs) and descend_batch (gradient walks to local minima), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
 // sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
 // the launches.  The sequence drivers share their opening (SeqCall) and their view of a chunk (ChunkView).
@@ -762,6 +762,118 @@ int findpath_batch(int n_paths, const char *const *seqs, const int *lens, const 
             rec_out[p] = rafft_findpath_rec{0, q.d, q.d, r.start, r.end, r.saddle, r.saddle_step, 0};
             if (moves_out && moves_out[p] && q.d) memcpy(moves_out[p], out.data() + q.out_off, (size_t)q.d * 8);
             if (dcal_out && dcal_out[p]) memcpy(dcal_out[p], out.data() + q.out_off + fp_out_dcal_off(q.d), ((size_t)q.d + 1) * 4);
+        }
+    }
+    g_err = err;
+    return 0;
+}
+
+// ---- gradient walks to local minima
+
+constexpr size_t DESCEND_WORKSPACE = (size_t)512 << 20;
+
+// of the last call: chunks, kernel launches, walks that ran, steps over all walks
+long long g_descend_counters[4];
+
+// rafft_descend_batch (arguments validated by the entry point).  One pack of the sequences; every row of a sequence without an
+// error is checked (descend_parse_row; its pair table is formed again when its chunk is staged); the walks that are left are laid out in chunks (descend_layout).  Per chunk: one upload of
+// the pair tables, one launch of descend_kernel (one wavefront per walk), one download of the end rows, of the records and - when
+// any walk of the chunk has a move buffer - of the moves, one synchronise.
+int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                  double temp, int max_steps, long long workspace_bytes, rafft_descend_seq *seq_out, rafft_descend_row *row_out,
+                  char *const *db_out, int *const *moves_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    for (long long &c : g_descend_counters) c = 0;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_DESCEND_MAX_LEN);
+    // the call's error text names the first erroneous item in input order: (sequence, row), row -1 for the sequence itself
+    std::string err = pk.first_err;
+    long long err_at = -1;
+    for (int s = 0; s < n_seq && err_at < 0; s++) if (pk.status[s]) err_at = ((long long)s << 32);
+    auto note = [&](int s, int r, const std::string &msg) {
+        const long long at = ((long long)s << 32) + r + 1;
+        if (err_at < 0 || at < err_at) { err_at = at; err = msg; }
+    };
+    struct Where { int s, r; };
+    std::vector<Where> run;
+    std::vector<int> wL, wbound;
+    std::vector<unsigned long long> wcode;
+    std::vector<unsigned char> wmoves;
+    std::vector<int16_t> pt;            // (one table, filled again per row: a call of millions of rows keeps none)
+    int row0 = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.len[s], L = pk.L[s];
+        seq_out[s] = rafft_descend_seq{pk.status[s], len, n_rows[s], row0};
+        for (int r = 0; r < n_rows[s]; r++) {
+            rafft_descend_row &o = row_out[row0 + r];
+            char *db = db_out[s] + (size_t)r * ((size_t)len + 1);
+            o = rafft_descend_row{pk.status[s], 0, 0, 0};
+            if (pk.status[s]) { dot_row(db, len); continue; }
+            const char *row = rows[s] + (size_t)r * (size_t)row_stride[s];
+            if (int st = descend_parse_row(pk.codes.data() + pk.code_off[s], L, row, pt)) {
+                o.status = st;
+                const size_t n = strnlen(row, (size_t)L);        // (the row comes back as it went in)
+                memcpy(db, row, n);
+                db[n] = 0;
+                note(s, r, "sequence " + std::to_string(s) + " row " + std::to_string(r) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3");
+                continue;
+            }
+            run.push_back(Where{s, r});
+            wL.push_back(L); wbound.push_back(descend_bound(L, max_steps)); wcode.push_back(pk.code_off[s]);
+            wmoves.push_back(moves_out && moves_out[s] ? 1 : 0);
+        }
+        row0 += n_rows[s];
+    }
+    g_err = err;
+    if (run.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    const DsLayout y = descend_layout(run.size(), wL.data(), wbound.data(), wcode.data(), wmoves.data(),
+                                      workspace_bytes > 0 ? (size_t)workspace_bytes : DESCEND_WORKSPACE);
+    DsWalk *d_ws; DsRec *d_rec; unsigned char *d_io, *d_mv = nullptr;
+    if (int rc = mem.alloc(d_ws, run.size() * sizeof(DsWalk))) return rc;
+    if (int rc = mem.alloc(d_rec, run.size() * sizeof(DsRec))) return rc;
+    if (int rc = mem.alloc(d_io, y.max_io + 16)) return rc;
+    if (y.max_mv) if (int rc = mem.alloc(d_mv, y.max_mv + 16)) return rc;      // (no caller asked for moves: no buffer)
+    HIPCHK(hipMemcpyAsync(d_ws, y.ws.data(), run.size() * sizeof(DsWalk), hipMemcpyHostToDevice, st));
+    std::vector<unsigned char> io(y.max_io + 16), mv(y.max_mv + 16);
+    std::vector<DsRec> rec(run.size());
+    g_descend_counters[0] = (long long)y.plan.chunks.size();
+    g_descend_counters[2] = (long long)run.size();
+    for (size_t ci = 0; ci < y.plan.chunks.size(); ci++) {
+        const ChunkPlan::Range &c = y.plan.chunks[ci];
+        const size_t nw = c.b - c.a;
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = run[k].s;
+            if (descend_parse_row(pk.codes.data() + pk.code_off[s], wL[k], rows[s] + (size_t)run[k].r * (size_t)row_stride[s], pt))
+                return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+            memcpy(io.data() + y.ws[k].io_off, pt.data(), (size_t)wL[k] * 2);
+        }
+        HIPCHK(hipMemcpyAsync(d_io, io.data(), y.chunk_io[ci], hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(descend_kernel<0>, dim3((unsigned)nw), dim3(64), (size_t)descend_lds_bytes(y.chunk_lmax[ci]), st, g.T, d_ws + c.a, sc.d_codes,
+                           d_io, d_mv, d_rec + c.a);
+        HIPCHK(hipGetLastError());
+        g_descend_counters[1]++;
+        HIPCHK(hipMemcpyAsync(io.data(), d_io, y.chunk_io[ci], hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rec.data() + c.a, d_rec + c.a, nw * sizeof(DsRec), hipMemcpyDeviceToHost, st));
+        if (y.chunk_mv[ci]) HIPCHK(hipMemcpyAsync(mv.data(), d_mv, y.chunk_mv[ci], hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = run[k].s, r = run[k].r, L = wL[k];
+            const DsRec &d = rec[k];
+            const std::string who = "sequence " + std::to_string(s) + " row " + std::to_string(r);
+            if (d.flags & DS_BAD_PAIR) return fail(RAFFT_ERR_HIP, "internal: " + who + ": a non-canonical pair on the device");
+            if (d.n_steps < 0 || d.n_steps > wbound[k]) return fail(RAFFT_ERR_HIP, "internal: " + who + ": more steps than the bound");
+            rafft_descend_row &o = row_out[seq_out[s].row0 + r];
+            o = rafft_descend_row{(d.flags & DS_MORE) ? RAFFT_ERR_CAPACITY : 0, d.n_steps, d.start, d.end};
+            if (d.flags & DS_MORE) note(s, r, who + ": not at a minimum after " + std::to_string(d.n_steps) + " steps (max_steps)");
+            memcpy(db_out[s] + (size_t)r * ((size_t)L + 1), io.data() + y.ws[k].io_off, (size_t)L + 1);
+            if (wmoves[k] && d.n_steps)
+                memcpy(moves_out[s] + (size_t)r * 2 * (size_t)wbound[k], mv.data() + y.ws[k].mv_off, (size_t)d.n_steps * 8);
+            g_descend_counters[3] += d.n_steps;
         }
     }
     g_err = err;

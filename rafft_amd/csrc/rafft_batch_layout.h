@@ -1,6 +1,6 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip and rafft_findpath.hip read and write, and the sizes both sides
-// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem).  The layouts that fill the records are in
+// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip and rafft_descend.hip read and write, and the sizes both sides
+// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
 
@@ -127,3 +127,30 @@ struct FpRec {
 #define FP_RANGE 1                  // an energy outside what a key holds
 #define FP_BAD_PAIR 2               // a non-canonical pair met on the device (the host refuses them: cannot happen)
 #define FP_STUCK 4                  // a level without a candidate (cannot happen: a legal move always exists)
+
+// ---- gradient walks to local minima (rafft_descend.hip)
+
+// What a walk over L positions has on the device.  Its row, in the chunk's row buffer from io_off: on the way in the pair table
+// (int16, -1 = unpaired), on the way out the end row as L characters of ( ) . and a NUL, over the same bytes (L + 1 <= 2 L).  Its
+// moves, when the caller asked for them, in the chunk's move buffer from mv_off: 2 x bound ints, (i, j) added, (-i-1, -j-1) removed.
+#define DESCEND_NO_MOVES (~0ull)
+RAFFT_HD constexpr unsigned long long descend_io_bytes(int L) { return fp_align16(2ull * (unsigned long long)L); }
+RAFFT_HD constexpr unsigned long long descend_moves_bytes(int bound) { return fp_align16(8ull * (unsigned long long)bound); }
+// the steps a walk may take: max_steps, or 2 L + 16 when max_steps is 0
+RAFFT_HD constexpr int descend_bound(int L, int max_steps) { return max_steps > 0 ? max_steps : 2 * L + 16; }
+// dynamic LDS of the kernel for the longest walk of a chunk: the pair table
+RAFFT_HD constexpr int descend_lds_bytes(int L) { return (2 * L + 15) & ~15; }
+
+struct DsWalk {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long io_off;      // first byte of its row in the chunk's row buffer
+    unsigned long long mv_off;      // first byte of its moves in the chunk's move buffer, or DESCEND_NO_MOVES
+    int L, bound;
+};
+struct DsRec {
+    int flags;                      // DS_*
+    int n_steps;
+    int start, end;                 // energies of the start row and of the row the walk reached
+};
+#define DS_MORE 1                   // the walk took `bound` steps and could take another
+#define DS_BAD_PAIR 2               // a non-canonical pair met on the device (the host refuses them: cannot happen)

@@ -1,8 +1,8 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
 // that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
 // (chunks within a budget, the sequence pack, the graph pack, the solve order, the layouts of the four sequence drivers: every
-// offset their kernels dereference, as records of rafft_batch_layout.h - and the moves, conflict masks and layout of findpath).
-// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp).  Part of the single translation unit
+// offset their kernels dereference, as records of rafft_batch_layout.h - the moves, conflict masks and layout of findpath, and the rows and layout of descend).
+// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp, descend_check.cpp).  Part of the single translation unit
 // of rafft_api.hip (included there, before the kernels).
 #pragma once
 
@@ -460,6 +460,55 @@ static FpLayout findpath_layout(int n_paths, const std::vector<int> &run, const 
         }
         y.chunk_in.push_back(in); y.chunk_out.push_back(out); y.chunk_dmax.push_back(dmax);
         y.max_in = std::max(y.max_in, in); y.max_out = std::max(y.max_out, out);
+    }
+    return y;
+}
+
+// ---- rafft_descend_batch: a walk's start from its row, and the layout of a call
+
+// The pair table of a start row over the bases `codes` (kBaseCode, L of them); the row is the L bytes at `row` (it need not end
+// in a NUL).  Returns RAFFT_ERR_STRUCT for a character outside ( ) . (a NUL before L among them: a row of the wrong length), an
+// unbalanced row, a non-canonical pair (N pairs with nothing) or a pair (i, j) with j - i <= 3 - every hairpin of fewer than 3
+// positions is one, and every such pair is or holds one.
+static int descend_parse_row(const uint8_t *codes, int L, const char *row, std::vector<int16_t> &pt)
+{
+    if (!row || !parse_db(row, L, pt)) return RAFFT_ERR_STRUCT;
+    for (int i = 0; i < L; i++)
+        if (pt[i] > i && (pt[i] - i <= 3 || !fp_canonical(codes[i], codes[pt[i]]))) return RAFFT_ERR_STRUCT;
+    return 0;
+}
+
+// The walks that run (those without an error, in input order; walk k is over L[k] positions, may take bound[k] steps, its bases
+// lie at code_off[k], want_moves[k]: the caller asked for its moves): chunks of whole walks whose rows and move buffers together fit
+// the budget, one walk at least, DESCEND_CHUNK_WALKS at most.  Per chunk the rows lie back to back from byte 0 of the row buffer,
+// the moves from byte 0 of the move buffer.
+constexpr size_t DESCEND_CHUNK_WALKS = (size_t)1 << 22;
+struct DsLayout {
+    std::vector<DsWalk> ws;             // one per walk that runs
+    std::vector<size_t> bytes;          // per walk: row and moves
+    ChunkPlan plan;
+    std::vector<size_t> chunk_io, chunk_mv;         // bytes of a chunk's rows / moves
+    std::vector<int> chunk_lmax;
+    size_t max_io = 0, max_mv = 0;
+};
+static DsLayout descend_layout(size_t n, const int *L, const int *bound, const unsigned long long *code_off, const unsigned char *want_moves,
+                               size_t budget)
+{
+    DsLayout y;
+    y.ws.resize(n); y.bytes.resize(n);
+    for (size_t k = 0; k < n; k++) y.bytes[k] = (size_t)(descend_io_bytes(L[k]) + (want_moves[k] ? descend_moves_bytes(bound[k]) : 0ull));
+    y.plan = plan_chunks(n, y.bytes.data(), nullptr, budget, DESCEND_CHUNK_WALKS);
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        size_t io = 0, mv = 0;
+        int lmax = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            y.ws[k] = DsWalk{code_off[k], io, want_moves[k] ? mv : DESCEND_NO_MOVES, L[k], bound[k]};
+            io += (size_t)descend_io_bytes(L[k]);
+            if (want_moves[k]) mv += (size_t)descend_moves_bytes(bound[k]);
+            lmax = std::max(lmax, L[k]);
+        }
+        y.chunk_io.push_back(io); y.chunk_mv.push_back(mv); y.chunk_lmax.push_back(lmax);
+        y.max_io = std::max(y.max_io, io); y.max_mv = std::max(y.max_mv, mv);
     }
     return y;
 }

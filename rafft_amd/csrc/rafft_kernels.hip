@@ -26,6 +26,7 @@
 //   eval_kernel         (rafft_io_kernels.hip) whole-structure energy (rafft/utils.py:135-138), C-ABI hook
 //   findpath_*_kernel   (rafft_findpath.hip) folding barriers between structure pairs: not part of the fold, but built on
 //                       loop_energy, PlainView's kin and the radix select below
+//   descend_kernel      (rafft_descend.hip) gradient walks to local minima, on loop_energy and findpath's view
 //
 // This is bandwidth/latency-bound small-FFT + integer table work: no MFMA.
 #include "rafft_kernels.h"
@@ -176,3 +177,4 @@ struct PlainView {
 #include "rafft_materialize.hip"        // materialize_kernel, materialize_team_kernel, dedupe_kernel
 #include "rafft_io_kernels.hip"         // stage_in_kernel, init_roots_kernel, output_kernel, eval_kernel
 #include "rafft_findpath.hip"           // findpath_init_kernel, findpath_expand_kernel, findpath_select_kernel, findpath_trace_kernel
+#include "rafft_descend.hip"            // descend_kernel

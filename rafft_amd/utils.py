@@ -84,7 +84,7 @@ def parse_rafft_output(infile):
             if line.startswith("# --"):
                 results.append([])
             else:
-                str_struct, nrj = line.strip().split()
+                str_struct, nrj = line.split()[:2]          # (a third column - the count of a basin, `rafft --descend` - is not read)
                 st = Structure(str_struct, 0)
                 st.energy = float(nrj)
                 st.dcal = int(round(float(nrj) * 100))
