@@ -568,6 +568,57 @@ int rafft_descend_batch(int n_seq, const char *const *seqs, const int *lens, con
 /* of the last rafft_descend_batch: chunks, kernel launches, walks that ran, steps over all walks */
 int rafft_descend_counters(long long out[4]);
 
+/* Exact barrier trees of energy bands.  Replaces: `RNAsubopt -e D -s | barriers`, what a user of the
+ * reference takes from ViennaRNA to ask for the local minima of a band, the exact saddle that joins each to a deeper one, the
+ * basin of every structure, and the tree treekin starts from.
+ * Input, per sequence s: the sequence; n_rows[s] rows of ( ) . , lens[s] characters each, row_stride[s] >= lens[s] bytes apart (the
+ * shape of rafft_descend_batch; what rafft_subopt_seq.db holds); dcal[s][0 .. n_rows[s]), their energies, non-decreasing (what
+ * rafft_subopt_seq.dcal holds).  The RANK of a row is its index.  The landscape is exactly the rows handed over: no energy is
+ * evaluated again, and the list need not be a complete band - a deduplicated, sorted sample is a valid input whose missing
+ * structures simply are not there.
+ * The result is defined exactly, so same input, same bits:
+ *   Neighbours: two rows whose pair sets differ by exactly one pair, under rafft_descend_batch's rule - an added pair (i, j) has
+ *     both ends unpaired and in the same loop, j - i > 3 and a canonical pair of bases; N pairs with nothing.
+ *   Minimum: a row with no neighbour of lower rank.  Equal energies are ordered by rank (as `barriers` orders them: by the list),
+ *     so rank 0 is always a minimum.  Minima are numbered by ascending rank.
+ *   Gradient basin: down[x] is the lowest-ranked neighbour of x if its rank is below x, else x; basin[x] is the (index of the)
+ *     minimum the chain of down reaches; basin_size[m] the number of rows with basin[x] == m.
+ *   Tree: for a minimum m let t be the smallest rank such that, in the graph of the rows of rank <= t, the component of m holds a
+ *     row of rank below m's.  No such t: father = saddle_rank = -1, a root (minimum 0 is one, and so is whatever the rows do not
+ *     connect).  Otherwise saddle_rank = t and father is the minimum index of the lowest-ranked row of that component; father < m,
+ *     the barrier is dcal[t] - dcal[rank of m]; saddle_dcal = dcal[t], 0 for a root.  This is what the flooding of `barriers` gives.
+ *   Edges: for every unordered pair of distinct gradient basins a < b (minimum indices) with a row x in one that has a neighbour
+ *     of lower rank in the other, one edge (a, b, the smallest such x), sorted by (saddle_rank, a, b): the direct saddles between
+ *     adjacent basins.  The tree is the minimax closure over them.
+ * Identity of a row is the 128-bit commutative hash of its pair set, as for the fold's `seen` table (section 5): two rows of one
+ * sequence with the same hash are reported as a duplicate.
+ * max_edges: the distinct edges a sequence may have; 0 means 4 * n_rows[s]; values below 1024 count as 1024, above 2^30 as 2^30.  workspace_bytes (0:
+ * 512 MiB): sequences are taken in chunks of whole sequences in input order whose work areas (pair tables, keys, the row table,
+ * down, basin and the edge table; DESIGN.md section 15 states the bytes) fit it together, one sequence at least.
+ * The library owns the result (the number of minima is not known before the call): free it with rafft_barriers_free.
+ * Errors of that sequence only (status in seq[s], no minima; the call returns RAFFT_OK, the neighbours are untouched,
+ * rafft_last_error() names the first): RAFFT_ERR_BAD_CHAR, RAFFT_ERR_EMPTY (n_rows[s] == 0 too), RAFFT_ERR_TOO_LONG (above
+ * RAFFT_BARRIERS_MAX_LEN); RAFFT_ERR_STRUCT for a malformed row (rafft_descend_batch's verdict), a dcal that decreases, a duplicate
+ * row (the message names both ranks); RAFFT_ERR_CAPACITY for more than RAFFT_BARRIERS_MAX_ROWS rows, more than max_edges edges
+ * (raise max_edges) and a work area above the workspace (the message states the bytes).  RAFFT_ERR_PARAM, before anything is
+ * launched: a null argument, a negative count, a stride below the length, a negative max_edges or workspace_bytes.  A batch of
+ * nothing but erroneous sequences never touches the device.  A sequence's result depends on its rows and dcal only - not on the
+ * batch, its order, the chunking, the workspace, or max_edges when it is large enough.  On any error of the call *out is NULL. */
+#define RAFFT_BARRIERS_MAX_LEN  RAFFT_MFE_MAX_LEN
+#define RAFFT_BARRIERS_MAX_ROWS RAFFT_SUBOPT_MAX_STRUCTS
+typedef struct { int32_t rank, father, saddle_rank, dcal, saddle_dcal, basin_size; } rafft_barriers_min;   /* 24 bytes */
+typedef struct { int32_t a, b, saddle_rank; } rafft_barriers_edge;                                          /* 12 bytes */
+typedef struct { int32_t status, length, n_rows, n_minima, n_edges, _pad;
+                 const rafft_barriers_min *minima; const rafft_barriers_edge *edges; const int32_t *basin /* [n_rows]: minimum index */; } rafft_barriers_seq;
+typedef struct { int32_t n_seq, n_failed; rafft_barriers_seq *seq; void *_owner; } rafft_barriers_result;
+int  rafft_barriers_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows,
+                          const int *row_stride, const int *const *dcal, int max_edges, long long workspace_bytes,
+                          rafft_barriers_result **out);
+void rafft_barriers_free(rafft_barriers_result *r);
+/* of the last rafft_barriers_batch: chunks, kernel launches, rows that ran, neighbour probes that hit (of the pass that finds
+ * down), minima, edges */
+int  rafft_barriers_counters(long long out[6]);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

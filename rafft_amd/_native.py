@@ -112,6 +112,30 @@ class DescendRow(C.Structure):
 
 DESCEND_MAX_LEN = MFE_MAX_LEN            # RAFFT_DESCEND_MAX_LEN
 
+class BarriersMin(C.Structure):
+    """rafft_barriers_min: one record per local minimum of a rafft_barriers_seq"""
+    _fields_ = [("rank", C.c_int32), ("father", C.c_int32), ("saddle_rank", C.c_int32), ("dcal", C.c_int32), ("saddle_dcal", C.c_int32),
+                ("basin_size", C.c_int32)]
+
+
+class BarriersEdge(C.Structure):
+    """rafft_barriers_edge: the direct saddle between two adjacent gradient basins"""
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("saddle_rank", C.c_int32)]
+
+
+class BarriersSeq(C.Structure):
+    """rafft_barriers_seq: one record per sequence of a rafft_barriers_result"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("n_rows", C.c_int32), ("n_minima", C.c_int32), ("n_edges", C.c_int32),
+                ("_pad", C.c_int32), ("minima", C.POINTER(BarriersMin)), ("edges", C.POINTER(BarriersEdge)), ("basin", C.POINTER(C.c_int32))]
+
+
+class BarriersResult(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("n_failed", C.c_int32), ("seq", C.POINTER(BarriersSeq)), ("_owner", C.c_void_p)]
+
+
+BARRIERS_MAX_LEN = MFE_MAX_LEN           # RAFFT_BARRIERS_MAX_LEN
+BARRIERS_MAX_ROWS = SUBOPT_MAX_STRUCTS   # RAFFT_BARRIERS_MAX_ROWS
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
@@ -119,7 +143,8 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_landscape_distances", "rafft_landscape_mds", "rafft_landscape_surface", "rafft_landscape_counters",
            "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
            "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
-           "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters"]
+           "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters", "rafft_barriers_batch",
+           "rafft_barriers_free", "rafft_barriers_counters"]
 
 _lib = None
 
@@ -227,6 +252,11 @@ def lib():
                                       C.POINTER(C.c_int), C.c_double, C.c_int, C.c_longlong, C.POINTER(DescendSeq), C.c_void_p,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_descend_counters.argtypes = [C.POINTER(C.c_longlong * 4)]
+    L.rafft_barriers_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(C.POINTER(BarriersResult))]
+    L.rafft_barriers_free.argtypes = [C.POINTER(BarriersResult)]
+    L.rafft_barriers_free.restype = None
+    L.rafft_barriers_counters.argtypes = [C.POINTER(C.c_longlong * 6)]
     _lib = L
     return L
 

@@ -90,6 +90,11 @@ _OPTIONS = [
                                                     "minimum its structures walk down to, energy ascending.  Not with --scores, --mfe, --pf, --findpath, --kin, --traj")),
     (("--max-steps",), dict(type=int, default=0, metavar="N", help="with --descend: a walk that is not at a minimum after N steps is an error (default 0: twice the\n"
                                                                     "sequence's length + 16, which no walk of the tests came near)")),
+    (("--barriers",), dict(action="store_true", help="with --subopt DELTA: the exact barrier tree of every sequence's band on the GPU (rafft_amd.barrier_trees; as\n"
+                                                     "`RNAsubopt -e DELTA -s | barriers`): per sequence the `>name` line if there was one, the sequence and one\n"
+                                                     "line `index structure energy father barrier` per local minimum, energy ascending (father 0: a root).\n"
+                                                     "Not with --descend or --scores")),
+    (("--minh",), dict(type=float, default=0.0, metavar="H", help="with --barriers: minima whose barrier is below H kcal/mol are folded into their fathers (default 0)")),
     (("--seed",), dict(type=int, default=0, help="with --sample: the seed (default 0); the same seed gives the same structures")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
@@ -380,6 +385,8 @@ def main_subopt(args, seqs, known, names, subopt_batch=None, scorer=None):
         raise SystemExit("--max-structs needs a positive number of structures")
     if subopt_batch is None:
         from .wuchty import subopt_batch
+    if args.barriers:
+        return main_barriers(args, seqs, names)
     bands = subopt_batch(seqs, args.subopt, args.max_structs, args.temp)
     if args.descend:
         text = descend_steps(args, seqs, bands)
@@ -392,6 +399,28 @@ def main_subopt(args, seqs, known, names, subopt_batch=None, scorer=None):
     if not args.descend:
         from .utils import format_trajectory
         text = "".join(format_trajectory(s, [list(band)]) for s, band in zip(seqs, bands))          # (the library's order)
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
+def main_barriers(args, seqs, names, barrier_trees=None):
+    """--subopt DELTA --barriers: the barrier tree of every sequence's band instead of the band"""
+    if args.descend or args.scores:
+        raise SystemExit("--barriers gives the barrier tree of every band: no --descend, no --scores")
+    if not args.minh >= 0.0:
+        raise SystemExit("--minh needs a barrier height of 0 kcal/mol or more")
+    if barrier_trees is None:
+        from .barriers import barrier_trees
+    trees = barrier_trees(seqs, args.subopt, args.max_structs, args.temp)
+    text = []
+    for k, (s, t) in enumerate(zip(seqs, trees)):
+        if names is not None and names[k]:
+            text.append(f">{names[k]}\n")
+        text.append(s + "\n" + (t.prune(args.minh) if args.minh > 0 else t).format())
+    text = "".join(text)
     if args.output:
         with open(args.output, "w") as out:
             out.write(text)
@@ -477,6 +506,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
         return main_findpath(args)
     if args.max_steps < 0:
         raise SystemExit("--max-steps is 0 or more")
+    if args.barriers and args.subopt is None:
+        raise SystemExit("--barriers needs --subopt DELTA: the tree is that of the band")
     if args.descend and args.sample is None and args.subopt is None:
         return main_descend(args)
     seqs, known, names = read_records(args)

@@ -31,7 +31,7 @@
 #include <pthread.h>
 
 // kernels (rafft_kernels.hip - the shared device helpers, which in turn includes one file per fold kernel: rafft_expand.hip,
-// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip, rafft_descend.hip - is compiled into the same translation
+// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip - is compiled into the same translation
 // unit so the templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
@@ -50,7 +50,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch, descend_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -444,6 +444,39 @@ int rafft_descend_counters(long long out[4])
     std::lock_guard<std::mutex> lk(g.mu);
     if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
     for (int k = 0; k < 4; k++) out[k] = g_descend_counters[k];
+    return 0;
+}
+
+int rafft_barriers_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                         const int *const *dcal, int max_edges, long long workspace_bytes, rafft_barriers_result **out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    *out = nullptr;
+    if (n_seq < 0 || max_edges < 0 || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (n_seq > 0 && (!seqs || !lens || !n_rows || !rows || !row_stride || !dcal)) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int s = 0; s < n_seq; s++) {
+        const std::string who = "sequence " + std::to_string(s);
+        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative row count");
+        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+        if (n_rows[s] > 0) {
+            if (!rows[s] || !dcal[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+            if (row_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
+        }
+    }
+    return barriers_batch(n_seq, seqs, lens, n_rows, rows, row_stride, dcal, max_edges, workspace_bytes, out);
+}
+
+void rafft_barriers_free(rafft_barriers_result *r)
+{
+    if (r && r->_owner) delete (BarriersOwner *)r->_owner;
+}
+
+int rafft_barriers_counters(long long out[6])
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < 6; k++) out[k] = g_barriers_counters[k];
     return 0;
 }
 

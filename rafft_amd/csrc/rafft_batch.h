@@ -1,7 +1,7 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
 // function and pair probabilities), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
-// energy band), findpath_batch (folding barriers between structure pairs) and descend_batch (gradient walks to local minima), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
+// energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima) and barriers_batch (exact barrier trees of energy bands), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
 // sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
 // the launches.  The sequence drivers share their opening (SeqCall) and their view of a chunk (ChunkView).
@@ -878,6 +878,205 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
     }
     g_err = err;
     return 0;
+}
+
+// ---- exact barrier trees of energy bands
+
+constexpr size_t BARRIERS_WORKSPACE = (size_t)512 << 20;
+constexpr size_t BARRIERS_WORKSPACE_MAX = (size_t)64 << 30;        // (a chunk's rows are numbered in 31 bits: at 56 bytes a row and more, this holds them)
+
+// what a rafft_barriers_result points into; rafft_barriers_free deletes it
+struct BarriersOwner {
+    rafft_barriers_result res;
+    std::vector<rafft_barriers_seq> seq;
+    std::vector<std::vector<rafft_barriers_min>> minima;
+    std::vector<std::vector<rafft_barriers_edge>> edges;
+    std::vector<std::vector<int32_t>> basin;
+};
+
+// of the last call: chunks, kernel launches, rows that ran, neighbour probes that hit, minima, edges
+long long g_barriers_counters[6];
+
+// rafft_barriers_batch (arguments validated by the entry point).  One pack of the sequences; every row of a sequence without an
+// error is checked (descend_parse_row; its pair table is formed again when its chunk is staged) and so is the order of its dcal;
+// the sequences that are left are laid out in chunks (barriers_layout).  Per chunk: one upload of the pair tables, the five
+// launches of rafft_barriers.hip, one download of basin (as ranks of minima), of the edge table and of the records, one
+// synchronise; then, per sequence on the host, the minima numbered by rank, the basin sizes, the edges compacted and sorted, and
+// the tree (barriers_tree).  No energy table is read: the call has no temperature.
+int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                   const int *const *dcal, int max_edges, long long workspace_bytes, rafft_barriers_result **out)
+{
+    *out = nullptr;
+    for (long long &c : g_barriers_counters) c = 0;
+    std::unique_ptr<BarriersOwner> own(new BarriersOwner);
+    own->seq.resize(n_seq); own->minima.resize(n_seq); own->edges.resize(n_seq); own->basin.resize(n_seq);
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_BARRIERS_MAX_LEN);
+    const size_t budget = std::min(workspace_bytes > 0 ? (size_t)workspace_bytes : BARRIERS_WORKSPACE, BARRIERS_WORKSPACE_MAX);
+    // the call's error text names the first erroneous sequence in input order
+    std::string err = pk.first_err;
+    int err_at = n_seq;
+    for (int s = 0; s < n_seq && err_at == n_seq; s++) if (pk.status[s]) err_at = s;
+    auto note = [&](int s, int status, const std::string &msg) {
+        own->seq[s].status = status;
+        if (s < err_at) { err_at = s; err = "sequence " + std::to_string(s) + ": " + msg; }
+    };
+    std::vector<int> run, rL, rn;
+    std::vector<unsigned long long> rcode;
+    std::vector<int16_t> pt;
+    for (int s = 0; s < n_seq; s++) {
+        const int L = pk.L[s];
+        own->seq[s] = rafft_barriers_seq{pk.status[s], pk.len[s], n_rows[s], 0, 0, 0, nullptr, nullptr, nullptr};
+        if (pk.status[s]) continue;
+        if (n_rows[s] == 0) { note(s, RAFFT_ERR_EMPTY, "no rows"); continue; }
+        if (n_rows[s] > RAFFT_BARRIERS_MAX_ROWS) { note(s, RAFFT_ERR_CAPACITY, "more than RAFFT_BARRIERS_MAX_ROWS rows"); continue; }
+        int bad = -1, dec = -1;
+        for (int r = 0; r < n_rows[s] && bad < 0 && dec < 0; r++) {
+            if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, rows[s] + (size_t)r * (size_t)row_stride[s], pt)) bad = r;
+            else if (r > 0 && dcal[s][r] < dcal[s][r - 1]) dec = r;
+        }
+        if (bad >= 0) { note(s, RAFFT_ERR_STRUCT, "row " + std::to_string(bad) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3"); continue; }
+        if (dec >= 0) { note(s, RAFFT_ERR_STRUCT, "row " + std::to_string(dec) + ": its dcal is below that of the row before it"); continue; }
+        const unsigned long long area = barriers_area_bytes(L, n_rows[s], barriers_edge_cap(n_rows[s], max_edges));
+        if (area > (unsigned long long)budget) {
+            note(s, RAFFT_ERR_CAPACITY, "its work area needs " + std::to_string(area) + " bytes, workspace_bytes is " + std::to_string(budget));
+            continue;
+        }
+        run.push_back(s); rL.push_back(L); rn.push_back(n_rows[s]); rcode.push_back(pk.code_off[s]);
+    }
+    auto finish = [&]() {
+        int n_failed = 0;
+        for (int s = 0; s < n_seq; s++) {
+            rafft_barriers_seq &o = own->seq[s];
+            n_failed += o.status != 0;
+            if (o.status) { own->minima[s].clear(); own->edges[s].clear(); own->basin[s].clear(); o.n_minima = o.n_edges = 0; }
+            // (never a null pointer, as rafft_subopt_seq: an empty list points at one spare element)
+            if (own->minima[s].empty()) own->minima[s].reserve(1);
+            if (own->edges[s].empty()) own->edges[s].reserve(1);
+            if (own->basin[s].empty()) own->basin[s].reserve(1);
+            o.minima = own->minima[s].data(); o.edges = own->edges[s].data(); o.basin = own->basin[s].data();
+        }
+        own->res = rafft_barriers_result{n_seq, n_failed, own->seq.data(), own.get()};
+        *out = &own->res;
+        own.release();
+        g_err = err;
+        return 0;
+    };
+    if (run.empty()) return finish();
+    SeamGuard sg;
+    DevScratch mem;
+    if (int rc = sg.enter()) return rc;
+    hipStream_t st = sg.stream;
+    const BarLayout y = barriers_layout(run.size(), rL.data(), rn.data(), rcode.data(), max_edges, budget);
+    uint8_t *d_codes; BarSeq *d_qs; BarRec *d_rec; unsigned char *d_pt; uint64_t *d_keys; unsigned long long *d_tab, *d_ekeys; unsigned *d_evals; int *d_down, *d_basin;
+    if (int rc = mem.alloc(d_codes, pk.codes.size())) return rc;
+    if (int rc = mem.alloc(d_qs, run.size() * sizeof(BarSeq))) return rc;
+    if (int rc = mem.alloc(d_rec, run.size() * sizeof(BarRec))) return rc;
+    if (int rc = mem.alloc(d_pt, y.max_pt + 16)) return rc;
+    if (int rc = mem.alloc(d_keys, y.max_rows * 16 + 16)) return rc;
+    if (int rc = mem.alloc(d_tab, y.max_tab * 8)) return rc;
+    if (int rc = mem.alloc(d_ekeys, y.max_edge * 8)) return rc;
+    if (int rc = mem.alloc(d_evals, y.max_edge * 4)) return rc;
+    if (int rc = mem.alloc(d_down, y.max_rows * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_basin, y.max_rows * 4 + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_codes, pk.codes.data(), pk.codes.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qs, y.qs.data(), run.size() * sizeof(BarSeq), hipMemcpyHostToDevice, st));
+    std::vector<BarRec> rec(run.size(), BarRec{BAR_EMPTY, 0, 0, 0});
+    HIPCHK(hipMemcpyAsync(d_rec, rec.data(), run.size() * sizeof(BarRec), hipMemcpyHostToDevice, st));
+    std::vector<unsigned char> hpt(y.max_pt + 16);
+    std::vector<int> hbasin(y.max_rows);
+    std::vector<unsigned long long> hek(y.max_edge);
+    std::vector<unsigned> hev(y.max_edge);
+    std::vector<int32_t> index, father, saddle;
+    g_barriers_counters[0] = (long long)y.plan.chunks.size();
+    for (size_t ci = 0; ci < y.plan.chunks.size(); ci++) {
+        const ChunkPlan::Range &c = y.plan.chunks[ci];
+        const int nq = (int)(c.b - c.a);
+        const unsigned nr = (unsigned)y.chunk_rows[ci];
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = run[k];
+            const BarSeq &q = y.qs[k];
+            for (int r = 0; r < q.n_rows; r++) {
+                if (descend_parse_row(pk.codes.data() + pk.code_off[s], q.L, rows[s] + (size_t)r * (size_t)row_stride[s], pt))
+                    return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+                memcpy(hpt.data() + q.pt_off + (size_t)r * (size_t)q.pt_stride, pt.data(), (size_t)q.L * 2);
+            }
+        }
+        HIPCHK(hipMemcpyAsync(d_pt, hpt.data(), y.chunk_pt[ci], hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_tab, 0xff, y.chunk_tab[ci] * 8, st));
+        HIPCHK(hipMemsetAsync(d_ekeys, 0xff, y.chunk_edge[ci] * 8, st));
+        HIPCHK(hipMemsetAsync(d_evals, 0xff, y.chunk_edge[ci] * 4, st));
+        const size_t lds = (size_t)barriers_lds_bytes(y.chunk_lmax[ci]);
+        const unsigned nb = (nr + 255u) / 256u;
+        const BarSeq *qs = d_qs + c.a;
+        BarRec *rc = d_rec + c.a;
+        hipLaunchKernelGGL(barriers_keys_kernel<0>, dim3(nr), dim3(64), 0, st, qs, nq, d_pt, d_keys);
+        hipLaunchKernelGGL(barriers_insert_kernel<0>, dim3(nb), dim3(256), 0, st, qs, nq, nr, d_keys, d_tab, rc);
+        hipLaunchKernelGGL(barriers_scan_kernel<BAR_DOWN>, dim3(nr), dim3(64), lds, st, qs, nq, d_codes, d_pt, d_keys, d_tab, d_down, d_basin, d_ekeys, d_evals, rc);
+        hipLaunchKernelGGL(barriers_basin_kernel<0>, dim3(nb), dim3(256), 0, st, qs, nq, nr, d_down, d_basin, rc);
+        hipLaunchKernelGGL(barriers_scan_kernel<BAR_EDGES>, dim3(nr), dim3(64), lds, st, qs, nq, d_codes, d_pt, d_keys, d_tab, d_down, d_basin, d_ekeys, d_evals, rc);
+        HIPCHK(hipGetLastError());
+        g_barriers_counters[1] += 5;
+        g_barriers_counters[2] += nr;
+        HIPCHK(hipMemcpyAsync(hbasin.data(), d_basin, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hek.data(), d_ekeys, y.chunk_edge[ci] * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hev.data(), d_evals, y.chunk_edge[ci] * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rec.data() + c.a, rc, (size_t)nq * sizeof(BarRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = run[k];
+            const BarSeq &q = y.qs[k];
+            const BarRec &d = rec[k];
+            const int n = q.n_rows;
+            g_barriers_counters[3] += (long long)d.hits;
+            if (d.flags & BAR_TABLE_BAD) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the row table is inconsistent");
+            if (d.dup != BAR_EMPTY) {
+                note(s, RAFFT_ERR_STRUCT, "rows " + std::to_string((unsigned)d.dup) + " and " + std::to_string((unsigned)(d.dup >> 32)) + " are the same structure");
+                continue;
+            }
+            if (d.flags & BAR_EDGES_FULL) {
+                note(s, RAFFT_ERR_CAPACITY, "more than " + std::to_string(q.edge_cap) + " edges between basins: raise max_edges");
+                continue;
+            }
+            // minima by ascending rank, basins as their indices, basin sizes
+            const int *bs = hbasin.data() + q.row0;
+            std::vector<rafft_barriers_min> &mn = own->minima[s];
+            std::vector<int32_t> &basin = own->basin[s];
+            index.assign((size_t)n, -1);
+            for (int x = 0; x < n; x++) {
+                if (bs[x] < 0 || bs[x] > x) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": a basin outside the rows");
+                if (bs[x] == x) { index[x] = (int32_t)mn.size(); mn.push_back(rafft_barriers_min{x, -1, -1, dcal[s][x], 0, 0}); }
+            }
+            basin.resize((size_t)n);
+            for (int x = 0; x < n; x++) {
+                const int32_t m = index[bs[x]];
+                if (m < 0) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": a basin that is no minimum");
+                basin[x] = m;
+                mn[m].basin_size++;
+            }
+            // the edge table, compacted and sorted
+            std::vector<rafft_barriers_edge> &ed = own->edges[s];
+            for (size_t e = q.edge_off; e <= q.edge_off + q.edge_mask; e++) {
+                if (hek[e] == BAR_EMPTY) continue;
+                const unsigned a = (unsigned)(hek[e] >> 32), b = (unsigned)hek[e];
+                if (a >= (unsigned)n || b >= (unsigned)n || hev[e] >= (unsigned)n || index[a] < 0 || index[b] < 0)
+                    return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": an edge outside the minima");
+                ed.push_back(rafft_barriers_edge{index[a], index[b], (int32_t)hev[e]});
+            }
+            std::sort(ed.begin(), ed.end(), [](const rafft_barriers_edge &u, const rafft_barriers_edge &v) {
+                return u.saddle_rank != v.saddle_rank ? u.saddle_rank < v.saddle_rank : u.a != v.a ? u.a < v.a : u.b < v.b;
+            });
+            barriers_tree((int)mn.size(), ed, father, saddle);
+            for (size_t m = 0; m < mn.size(); m++) {
+                mn[m].father = father[m]; mn[m].saddle_rank = saddle[m];
+                mn[m].saddle_dcal = saddle[m] >= 0 ? dcal[s][saddle[m]] : 0;
+            }
+            own->seq[s].n_minima = (int32_t)mn.size();
+            own->seq[s].n_edges = (int32_t)ed.size();
+            g_barriers_counters[4] += (long long)mn.size();
+            g_barriers_counters[5] += (long long)ed.size();
+        }
+    }
+    return finish();
 }
 
 } // namespace

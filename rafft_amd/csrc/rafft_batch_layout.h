@@ -1,6 +1,6 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip and rafft_descend.hip read and write, and the sizes both sides
-// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk).  The layouts that fill the records are in
+// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip and rafft_barriers.hip read and write, and the sizes both sides
+// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
 
@@ -154,3 +154,47 @@ struct DsRec {
 };
 #define DS_MORE 1                   // the walk took `bound` steps and could take another
 #define DS_BAD_PAIR 2               // a non-canonical pair met on the device (the host refuses them: cannot happen)
+
+// ---- exact barrier trees of energy bands (rafft_barriers.hip)
+
+// What a sequence of n rows over L positions has on the device, its work area.  Per row: its pair table (int16, -1 = unpaired;
+// barriers_pt_bytes(L) bytes apart), its 128-bit key (two uint64), down and basin (int32 each: ranks within the sequence).  Per
+// sequence: the row table, barriers_row_slots(n) slots of 8 bytes (tag << 32 | rank; BAR_EMPTY when free), and the edge table,
+// barriers_edge_slots(cap) slots of a 64-bit key (a << 32 | b, a < b ranks of two minima) and a 32-bit value (the saddle rank).
+// Rows are numbered through the chunk (row0 + rank); keys, down and basin are indexed by that number.
+#define BAR_EMPTY (~0ull)
+RAFFT_HD constexpr unsigned long long barriers_pt_bytes(int L) { return fp_align16(2ull * (unsigned long long)L); }
+RAFFT_HD constexpr unsigned long long barriers_pow2(unsigned long long x) { unsigned long long p = 1; while (p < x) p <<= 1; return p; }
+// a power of two >= 2 n: the table is never more than half full, so a probe sequence is short and always meets a free slot
+RAFFT_HD constexpr unsigned long long barriers_row_slots(long long n) { return barriers_pow2(2ull * (unsigned long long)(n > 0 ? n : 1)); }
+// the distinct edges a sequence may have: max_edges, or 4 n when it is 0; 1024 at least, 2^30 at most (slot numbers fit 31 bits)
+RAFFT_HD constexpr long long barriers_clamp(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
+RAFFT_HD constexpr long long barriers_edge_cap(long long n, int max_edges) { return barriers_clamp(max_edges > 0 ? (long long)max_edges : 4 * n, 1024, 1ll << 30); }
+RAFFT_HD constexpr unsigned long long barriers_edge_slots(long long cap) { return barriers_pow2(2ull * (unsigned long long)cap); }
+RAFFT_HD constexpr unsigned long long barriers_area_bytes(int L, long long n, long long cap)
+{
+    return (unsigned long long)n * (barriers_pt_bytes(L) + 16ull + 4ull + 4ull) + 8ull * barriers_row_slots(n) + 12ull * barriers_edge_slots(cap);
+}
+// dynamic LDS of the neighbour kernels for the longest sequence of a chunk: the pair table
+RAFFT_HD constexpr int barriers_lds_bytes(int L) { return (2 * L + 15) & ~15; }
+
+struct BarSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long pt_off;      // first byte of its pair tables in the chunk's buffer
+    unsigned long long tab_off;     // first slot of its row table in the chunk's
+    unsigned long long edge_off;    // first slot of its edge table in the chunk's
+    unsigned tab_mask, edge_mask;   // slots - 1
+    unsigned edge_cap;              // distinct edges it may have
+    int L, n_rows;
+    int row0;                       // the chunk's number of its rank 0
+    int pt_stride;                  // bytes from one pair table to the next
+    int _pad;
+};
+struct BarRec {
+    unsigned long long dup;         // (x << 32 | r) of the lowest-ranked row x with a twin r < x; BAR_EMPTY: none
+    unsigned long long hits;        // neighbour probes of the down pass that found a row
+    unsigned claims;                // slots of the edge table taken
+    unsigned flags;                 // BAR_*
+};
+#define BAR_EDGES_FULL 1            // more distinct edges than edge_cap, or no free slot
+#define BAR_TABLE_BAD 2             // a row table without a free slot, or a rank outside the sequence in it (cannot happen)

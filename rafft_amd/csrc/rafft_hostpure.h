@@ -1,8 +1,8 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
 // that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
 // (chunks within a budget, the sequence pack, the graph pack, the solve order, the layouts of the four sequence drivers: every
-// offset their kernels dereference, as records of rafft_batch_layout.h - the moves, conflict masks and layout of findpath, and the rows and layout of descend).
-// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp, descend_check.cpp).  Part of the single translation unit
+// offset their kernels dereference, as records of rafft_batch_layout.h - the moves, conflict masks and layout of findpath, the rows and layout of descend, the layout and the tree of barriers).
+// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp, descend_check.cpp, barriers_check.cpp).  Part of the single translation unit
 // of rafft_api.hip (included there, before the kernels).
 #pragma once
 
@@ -511,6 +511,73 @@ static DsLayout descend_layout(size_t n, const int *L, const int *bound, const u
         y.max_io = std::max(y.max_io, io); y.max_mv = std::max(y.max_mv, mv);
     }
     return y;
+}
+
+// ---- rafft_barriers_batch: the layout of a call, and the tree from the edges between basins
+
+// The sequences that run (those without an error, in input order; sequence k has n[k] rows over L[k] positions, bases at
+// code_off[k]): their work areas (barriers_area_bytes), chunks of whole sequences whose areas fit the budget together, one
+// sequence at least - the caller refuses a sequence whose own area is above the budget before it gets here - and per chunk every
+// offset the kernels dereference, each buffer from 0.
+struct BarLayout {
+    std::vector<BarSeq> qs;             // one per sequence that runs
+    std::vector<size_t> bytes;          // per sequence: its work area
+    ChunkPlan plan;
+    std::vector<size_t> chunk_rows, chunk_pt, chunk_tab, chunk_edge;    // rows / pair-table bytes / row-table slots / edge-table slots of a chunk
+    std::vector<int> chunk_lmax;
+    size_t max_rows = 0, max_pt = 0, max_tab = 0, max_edge = 0, max_seqs = 0;
+};
+static BarLayout barriers_layout(size_t n_seq, const int *L, const int *n, const unsigned long long *code_off, int max_edges, size_t budget)
+{
+    BarLayout y;
+    y.qs.resize(n_seq); y.bytes.resize(n_seq);
+    for (size_t k = 0; k < n_seq; k++) y.bytes[k] = (size_t)barriers_area_bytes(L[k], n[k], barriers_edge_cap(n[k], max_edges));
+    y.plan = plan_chunks(n_seq, y.bytes.data(), nullptr, budget, 65535);
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        size_t rows = 0, pt = 0, tab = 0, edge = 0;
+        int lmax = 0;
+        for (size_t k = c.a; k < c.b; k++) {
+            const long long cap = barriers_edge_cap(n[k], max_edges);
+            const size_t ts = (size_t)barriers_row_slots(n[k]), es = (size_t)barriers_edge_slots(cap);
+            y.qs[k] = BarSeq{code_off[k], pt, tab, edge, (unsigned)(ts - 1), (unsigned)(es - 1), (unsigned)cap, L[k], n[k], (int)rows, (int)barriers_pt_bytes(L[k]), 0};
+            rows += (size_t)n[k]; pt += (size_t)n[k] * (size_t)barriers_pt_bytes(L[k]); tab += ts; edge += es;
+            lmax = std::max(lmax, L[k]);
+        }
+        y.chunk_rows.push_back(rows); y.chunk_pt.push_back(pt); y.chunk_tab.push_back(tab); y.chunk_edge.push_back(edge); y.chunk_lmax.push_back(lmax);
+        y.max_rows = std::max(y.max_rows, rows); y.max_pt = std::max(y.max_pt, pt); y.max_tab = std::max(y.max_tab, tab);
+        y.max_edge = std::max(y.max_edge, edge); y.max_seqs = std::max(y.max_seqs, c.b - c.a);
+    }
+    return y;
+}
+
+// The barrier tree over n_minima minima (numbered by ascending rank) from the edges between their gradient basins, sorted by
+// (saddle_rank, a, b): Kruskal with a union-find whose root is the lowest minimum index.  The edges of one saddle_rank are one
+// group - the row of that rank may join several components at once: every component that loses its root in the group gets the
+// lowest root of what it merged into as father and that rank as saddle.  A minimum that is never merged into a lower one stays a
+// root (father = saddle_rank = -1).
+static void barriers_tree(int n_minima, const std::vector<rafft_barriers_edge> &edges, std::vector<int32_t> &father, std::vector<int32_t> &saddle_rank)
+{
+    father.assign((size_t)n_minima, -1); saddle_rank.assign((size_t)n_minima, -1);
+    std::vector<int32_t> up((size_t)n_minima), lost;
+    for (int m = 0; m < n_minima; m++) up[m] = m;
+    auto find = [&](int32_t m) {
+        int32_t r = m;
+        while (up[r] != r) r = up[r];
+        while (up[m] != r) { const int32_t nx = up[m]; up[m] = r; m = nx; }
+        return r;
+    };
+    for (size_t e = 0; e < edges.size();) {
+        const int32_t t = edges[e].saddle_rank;
+        lost.clear();
+        for (; e < edges.size() && edges[e].saddle_rank == t; e++) {
+            const int32_t ra = find(edges[e].a), rb = find(edges[e].b);
+            if (ra == rb) continue;
+            const int32_t lo = std::min(ra, rb), hi = std::max(ra, rb);
+            up[hi] = lo;
+            lost.push_back(hi);
+        }
+        for (int32_t m : lost) { father[m] = find(m); saddle_rank[m] = t; }
+    }
 }
 
 // the step a step of a folding graph is compared with: the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)

@@ -27,6 +27,8 @@
 //   findpath_*_kernel   (rafft_findpath.hip) folding barriers between structure pairs: not part of the fold, but built on
 //                       loop_energy, PlainView's kin and the radix select below
 //   descend_kernel      (rafft_descend.hip) gradient walks to local minima, on loop_energy and findpath's view
+//   barriers_*_kernel   (rafft_barriers.hip) exact barrier trees of energy bands: keys, a hash table of the rows, neighbours looked up
+//                       in it; no energy is evaluated
 //
 // This is bandwidth/latency-bound small-FFT + integer table work: no MFMA.
 #include "rafft_kernels.h"
@@ -178,3 +180,4 @@ struct PlainView {
 #include "rafft_io_kernels.hip"         // stage_in_kernel, init_roots_kernel, output_kernel, eval_kernel
 #include "rafft_findpath.hip"           // findpath_init_kernel, findpath_expand_kernel, findpath_select_kernel, findpath_trace_kernel
 #include "rafft_descend.hip"            // descend_kernel
+#include "rafft_barriers.hip"           // barriers_keys_kernel, barriers_insert_kernel, barriers_scan_kernel, barriers_basin_kernel
