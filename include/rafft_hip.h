@@ -619,6 +619,83 @@ void rafft_barriers_free(rafft_barriers_result *r);
  * down), minima, edges */
 int  rafft_barriers_counters(long long out[6]);
 
+/* Stochastic folding trajectories.  Replaces: ViennaRNA's Kinfold, what a user of the reference runs to
+ * simulate folding on the full move set: continuous-time Monte Carlo (Gillespie) over insertion and deletion of single pairs,
+ * from the open chain or any structure, with first-passage times to stop structures and the state at given times.
+ * One call, n_seq sequences with n_rows[s] start rows each in the shape of rafft_descend_batch (rows, row_stride), and n_rep >= 1
+ * trajectories per row: trajectory k = r * n_rep + rep of sequence s starts from row r.
+ * The process is defined exactly, so same input, same bits.
+ *  - Neighbours and dE: exactly rafft_descend_batch's (insertion and deletion, lonely pairs allowed; dE from the three loop terms).
+ *  - Rates: Metropolis, min(1, exp(-dE / (100 kT))), dE in dcal, kT in kcal/mol = kt, or 1.98717e-3 * (temp + 273.15) when kt is 0.
+ *  - Weights: rates are integer weights W[d] of a table of RAFFT_KINFOLD_NW = 4096 uint64 entries the host builds once per call
+ *    (rafft_kinfold_weights): W[0] = 2^32 for every dE <= 0 - the table is uint64 so that it holds it -, W[d] = floor(2^32 *
+ *    exp(-d / (100 kT)) + 0.5), weight 0 for dE >= 4096.  A move of weight 0 is never taken: relative rates below 2^-33 are dropped.
+ *  - Step number t (from 0) of trajectory k: the Philox4x32-10 block of counter (k, t, 0, 0) under seeds[s] gives u = the 53-bit
+ *    uniform of words 0-1 (rafft_sample_batch's draw t of sample k) and v = word 2 << 32 | word 3.  Wtot = the sum of the weights
+ *    of all neighbours (64 bits).  Wtot == 0: the state is absorbing, the trajectory ends with time = t_max and
+ *    RAFFT_KINFOLD_ABSORBED.  dt = -log(1 - u) * 2^32 / Wtot in double; time + dt > t_max: it ends in the current state with
+ *    time = t_max and RAFFT_KINFOLD_TIME.  Otherwise, max_steps steps taken already: it ends with RAFFT_KINFOLD_MORE, status
+ *    RAFFT_ERR_CAPACITY and time = the time of its last jump (0: max_steps is RAFFT_KINFOLD_DEFAULT_STEPS).  Otherwise r = the
+ *    upper 64 bits of v * Wtot, the move is the first in ascending (i, j) whose inclusive cumulative weight exceeds r (bias at most
+ *    Wtot / 2^64), it is applied and time += dt.
+ *  - Watched rows: watch[s] holds n_watch[s] <= 64 rows of sequence s, watch_stride[s] apart, parsed as start rows are; the first
+ *    n_stop[s] of them are absorbing: a trajectory that arrives at one ends with RAFFT_KINFOLD_STOP, stop_index = its index (the
+ *    lowest, should two be equal) and time = the arrival time; a start row that is a stop row ends at time 0 with 0 steps.
+ *    n_watch may be NULL (nothing is watched anywhere).
+ *  - Sample grid: sample_times[n_times] ascending within [0, t_max]; for every tau a trajectory records the state it is in at tau
+ *    (after every jump at a time <= tau): its energy and the lowest watched row it equals, or -1.  After STOP or ABSORBED the last
+ *    state holds; after MORE the times not below the jump that was not taken hold (INT32_MIN, -2).
+ * Outputs (host): seq_out[s]; traj_out[seq_out[s].traj0 + k]; db_out[s] = n_rows[s] * n_rep end rows, lens[s] + 1 bytes apart, NUL
+ * terminated; samples_out[s] (may be NULL when n_times is 0) = per trajectory n_times pairs of int32 (dcal, watch index);
+ * moves_out / times_out may be NULL and so may their entries (both or neither per sequence; then no device buffer for logs
+ * exists), else per trajectory a block of 2 * bound ints as rafft_descend_batch's moves and a block of bound doubles, the time of
+ * every jump; bound = max_steps or RAFFT_KINFOLD_DEFAULT_STEPS.
+ * Errors of that sequence only (its rows all dots, its samples (INT32_MIN, -2)): RAFFT_ERR_BAD_CHAR, RAFFT_ERR_EMPTY,
+ * RAFFT_ERR_TOO_LONG (above RAFFT_KINFOLD_MAX_LEN), RAFFT_ERR_STRUCT for a malformed watched row.  Errors of that start row only
+ * (all its trajectories): RAFFT_ERR_STRUCT as in rafft_descend_batch (the row comes back as it went in); of that trajectory:
+ * RAFFT_ERR_CAPACITY as above.  For these the call returns RAFFT_OK, the neighbours are untouched and rafft_last_error() names the
+ * first such item.  RAFFT_ERR_PARAM, before anything is launched: a null argument, a negative count, a stride below the length,
+ * n_rep < 1, n_watch > 64, n_stop > n_watch, t_max negative or not finite, a grid that descends, is negative or exceeds t_max,
+ * kt negative or not finite, a negative max_steps or workspace_bytes.  RAFFT_ERR_TEMP as for the fold.  A batch of nothing but
+ * erroneous items never touches the device.  A trajectory depends on the sequence, its start row, the energy tables, temp, kt, the
+ * seed, k, t_max, max_steps, the watched rows and the grid only - not on the batch, its order, the chunking or the workspace.
+ * Device memory: trajectories are taken in chunks of whole trajectories in input order whose rows, samples and logs fit
+ * workspace_bytes (0: 512 MiB), one at least; the watched rows and the weight table lie beside them for the whole call. */
+#define RAFFT_KINFOLD_MAX_LEN RAFFT_DESCEND_MAX_LEN
+#define RAFFT_KINFOLD_NW 4096
+#define RAFFT_KINFOLD_MAX_WATCH 64
+#define RAFFT_KINFOLD_DEFAULT_STEPS (1 << 20)
+#define RAFFT_KINFOLD_TIME 1
+#define RAFFT_KINFOLD_STOP 2
+#define RAFFT_KINFOLD_ABSORBED 4
+#define RAFFT_KINFOLD_MORE 8
+typedef struct {
+    int32_t status;
+    int32_t length;        /* lens[s] as reported (0 for a negative one) */
+    int32_t n_traj;        /* n_rows[s] * n_rep */
+    int32_t traj0;         /* index of the sequence's first record in traj_out */
+} rafft_kinfold_seq;       /* 16 bytes */
+typedef struct {
+    int32_t status;
+    int32_t flags;         /* RAFFT_KINFOLD_*: why it ended */
+    int32_t n_steps;       /* jumps taken */
+    int32_t start_dcal;    /* energy of the start row */
+    int32_t end_dcal;      /* energy of the row returned */
+    int32_t stop_index;    /* the stop row it arrived at, or -1 */
+    double time;           /* arrival (STOP), last jump (MORE), else t_max */
+} rafft_kinfold_traj;      /* 32 bytes */
+int rafft_kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows,
+                        const int *row_stride, int n_rep, const int *n_watch, const int *n_stop, const char *const *watch,
+                        const int *watch_stride, const unsigned long long *seeds /* [n_seq]; NULL: all 0 */, double temp, double kt,
+                        double t_max, int max_steps, int n_times, const double *sample_times, long long workspace_bytes /* 0: 512 MiB */,
+                        rafft_kinfold_seq *seq_out, rafft_kinfold_traj *traj_out, char *const *db_out, int32_t *const *samples_out,
+                        int *const *moves_out, double *const *times_out);
+/* the weight table of a call at (temp, kt): RAFFT_KINFOLD_NW entries; RAFFT_ERR_PARAM for a null pointer, a kt that is negative
+ * or not finite, or a kT that is not above 0.  Host only: needs no device. */
+int rafft_kinfold_weights(double temp, double kt, uint64_t *out /* RAFFT_KINFOLD_NW */);
+/* of the last rafft_kinfold_batch: chunks, kernel launches, trajectories that ran, steps over all trajectories */
+int rafft_kinfold_counters(long long out[4]);
+
 /* library / build information: "gfx950 ..." */
 const char *rafft_version(void);
 

@@ -15,6 +15,7 @@ from .wuchty import subopt, subopt_batch, subopt_batch_raw  # noqa: F401
 from .findpath import findpath_batch, findpath_batch_raw, path_rows  # noqa: F401
 from .descend import descend_batch, descend_batch_raw, minima_batch, basin_graph  # noqa: F401
 from .barriers import barriers_batch_raw, barrier_tree, barrier_trees, BarrierTree  # noqa: F401
+from .kinfold import kinfold_batch, kinfold_batch_raw, kinfold_weights, first_passage, occupancy  # noqa: F401
 # (the function `landscape.landscape` is exported as folding_landscape: `rafft_amd.landscape` stays the module)
 from .landscape import landscape as folding_landscape, distance_matrix_gpu, mds_gpu, surface_gpu, Landscape  # noqa: F401
 from .utils import Structure, parse_rafft_output, paired_positions, dot_bracket, read_fasta, format_trajectory  # noqa: F401

@@ -136,6 +136,24 @@ class BarriersResult(C.Structure):
 BARRIERS_MAX_LEN = MFE_MAX_LEN           # RAFFT_BARRIERS_MAX_LEN
 BARRIERS_MAX_ROWS = SUBOPT_MAX_STRUCTS   # RAFFT_BARRIERS_MAX_ROWS
 
+
+class KinfoldSeq(C.Structure):
+    """rafft_kinfold_seq: one record per sequence of rafft_kinfold_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("n_traj", C.c_int32), ("traj0", C.c_int32)]
+
+
+class KinfoldTraj(C.Structure):
+    """rafft_kinfold_traj: one record per trajectory of rafft_kinfold_batch"""
+    _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("n_steps", C.c_int32), ("start_dcal", C.c_int32), ("end_dcal", C.c_int32),
+                ("stop_index", C.c_int32), ("time", C.c_double)]
+
+
+KINFOLD_MAX_LEN = DESCEND_MAX_LEN        # RAFFT_KINFOLD_MAX_LEN
+KINFOLD_NW = 4096                        # RAFFT_KINFOLD_NW
+KINFOLD_MAX_WATCH = 64                   # RAFFT_KINFOLD_MAX_WATCH
+KINFOLD_DEFAULT_STEPS = 1 << 20          # RAFFT_KINFOLD_DEFAULT_STEPS
+KF_TIME, KF_STOP, KF_ABSORBED, KF_MORE = 1, 2, 4, 8     # RAFFT_KINFOLD_*
+
 EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wait", "rafft_free_result", "rafft_last_error", "rafft_eval_structure",
            "rafft_eval_structures", "rafft_eval_structures_at", "rafft_expand_node", "rafft_get_stats", "rafft_version",
            "rafft_load_params", "rafft_load_params_text", "rafft_reset_params", "rafft_save_params", "rafft_params_info",
@@ -144,7 +162,7 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
            "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
            "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters", "rafft_barriers_batch",
-           "rafft_barriers_free", "rafft_barriers_counters"]
+           "rafft_barriers_free", "rafft_barriers_counters", "rafft_kinfold_batch", "rafft_kinfold_weights", "rafft_kinfold_counters"]
 
 _lib = None
 
@@ -257,6 +275,13 @@ def lib():
     L.rafft_barriers_free.argtypes = [C.POINTER(BarriersResult)]
     L.rafft_barriers_free.restype = None
     L.rafft_barriers_counters.argtypes = [C.POINTER(C.c_longlong * 6)]
+    L.rafft_kinfold_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                      C.POINTER(C.c_double), C.c_longlong, C.POINTER(KinfoldSeq), C.c_void_p, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_kinfold_weights.argtypes = [C.c_double, C.c_double, C.c_void_p]
+    L.rafft_kinfold_counters.argtypes = [C.POINTER(C.c_longlong * 4)]
     _lib = L
     return L
 

@@ -89,13 +89,24 @@ _OPTIONS = [
                                                     "is the `>name` line if there was one, the sequence and one line `structure energy count` per distinct\n"
                                                     "minimum its structures walk down to, energy ascending.  Not with --scores, --mfe, --pf, --findpath, --kin, --traj")),
     (("--max-steps",), dict(type=int, default=0, metavar="N", help="with --descend: a walk that is not at a minimum after N steps is an error (default 0: twice the\n"
-                                                                    "sequence's length + 16, which no walk of the tests came near)")),
+                                                                    "sequence's length + 16, which no walk of the tests came near); with --kinfold: a trajectory that has\n"
+                                                                    "not ended after N steps is an error (default 0: 2^20)")),
+    (("--kinfold",), dict(type=int, default=None, metavar="N", help="with -sf FILE --batch and --tmax T: N stochastic folding trajectories per sequence from the open chain on\n"
+                                                                   "the GPU (rafft_amd.kinfold_batch; insertion and deletion of single pairs, Metropolis rates, as ViennaRNA's\n"
+                                                                   "Kinfold).  Per sequence the output is the `>name` line if there was one, the sequence, with --stop the line\n"
+                                                                   "`structure energy` of the stop structure, the line `arrived SHARE median T mean T` over the first-passage\n"
+                                                                   "times of the trajectories that reached it by T (`arrived 0.0000` alone when none did), and with --times K\n"
+                                                                   "K lines `time mean-energy arrived-share`.  --seed S and --max-steps M apply.  Not with any of the other modes")),
+    (("--tmax",), dict(type=float, default=None, metavar="T", help="with --kinfold: the time at which a trajectory ends, in units of 1 / (rate of a downhill move)")),
+    (("--stop",), dict(default=None, metavar="mfe|FILE", help="with --kinfold: the structure at which a trajectory ends - `mfe`: the minimum-free-energy structure of\n"
+                                                             "every sequence (rafft_amd.mfe_batch); FILE: one dot-bracket line per sequence")),
+    (("--times",), dict(type=int, default=0, metavar="K", help="with --kinfold: a table of the mean energy and the arrived share at K log-spaced times up to T")),
     (("--barriers",), dict(action="store_true", help="with --subopt DELTA: the exact barrier tree of every sequence's band on the GPU (rafft_amd.barrier_trees; as\n"
                                                      "`RNAsubopt -e DELTA -s | barriers`): per sequence the `>name` line if there was one, the sequence and one\n"
                                                      "line `index structure energy father barrier` per local minimum, energy ascending (father 0: a root).\n"
                                                      "Not with --descend or --scores")),
     (("--minh",), dict(type=float, default=0.0, metavar="H", help="with --barriers: minima whose barrier is below H kcal/mol are folded into their fathers (default 0)")),
-    (("--seed",), dict(type=int, default=0, help="with --sample: the seed (default 0); the same seed gives the same structures")),
+    (("--seed",), dict(type=int, default=0, help="with --sample or --kinfold: the seed (default 0); the same seed gives the same structures")),
     (("--max_time", "-mt"), dict(type=float, default=30, help="with --kin: max time (exp scale), as rafft_kin -mt")),
     (("--n_steps", "-ns"), dict(type=int, default=100, help="with --kin: number of sample times, as rafft_kin -ns")),
     (("--output", "-o"), dict(help="write the result there instead of stdout")),
@@ -478,6 +489,66 @@ def main_findpath(args, findpath_batch=None):
         sys.stdout.write(text)
 
 
+def kinfold_grid(t_max, k):
+    """k log-spaced times ending at t_max, three decades (one time: t_max itself)"""
+    return [t_max * 10.0 ** (-3.0 * (k - 1 - t) / max(k - 1, 1)) for t in range(k)]
+
+
+def main_kinfold(args, seqs, names, kinfold_batch=None, mfe_batch=None):
+    """--kinfold N: stochastic folding trajectories of every sequence from the open chain instead of the fold"""
+    if (args.mfe or args.pf or args.sample is not None or args.subopt is not None or args.kin or args.traj or args.scores or args.descend
+            or args.barriers):
+        raise SystemExit("--kinfold gives folding trajectories of every sequence: no --mfe, no --pf, no --sample, no --subopt, no --kin, no --traj, "
+                         "no --scores, no --descend")
+    if not args.batch or args.seq_file is None:
+        raise SystemExit("--kinfold needs -sf FILE --batch")
+    if args.kinfold < 1:
+        raise SystemExit("--kinfold needs a positive number of trajectories")
+    if args.tmax is None or not args.tmax >= 0.0 or args.tmax == float("inf"):
+        raise SystemExit("--kinfold needs --tmax T, a finite time of 0 or more")
+    if args.times < 0:
+        raise SystemExit("--times is 0 or more")
+    import numpy as np
+    from . import _native as N
+    stops = None
+    if args.stop == "mfe":
+        if mfe_batch is None:
+            from .zuker import mfe_batch
+        stops = [m.str_struct for m in mfe_batch(seqs, args.temp)]
+    elif args.stop is not None:
+        stops = [ln.strip() for ln in open(args.stop) if ln.strip()]
+        if len(stops) != len(seqs):
+            raise SystemExit(f"{args.stop}: {len(stops)} structures for {len(seqs)} sequences")
+    if kinfold_batch is None:
+        from .kinfold import kinfold_batch
+    grid = kinfold_grid(args.tmax, args.times)
+    got = kinfold_batch(seqs, [[None]] * len(seqs), args.tmax, n_rep=args.kinfold, watch=[[st] for st in stops] if stops else None,
+                        n_stop=1 if stops else None, seeds=args.seed, sample_times=grid, temp=args.temp, max_steps=args.max_steps)
+    stop_dcal = None
+    if stops:
+        from .rafft import eval_structures
+        stop_dcal, _ = eval_structures(seqs, stops, temp=args.temp)
+    lines = []
+    for k, (s, d) in enumerate(zip(seqs, got)):
+        if names is not None and names[k]:
+            lines.append(names[k])
+        lines.append(s)
+        if stops:
+            lines.append(f"{stops[k]} {stop_dcal[k] / 100.0:7.2f}")
+        hit = (d["flags"] & N.KF_STOP) != 0
+        t = d["time"][hit]
+        lines.append(f"arrived {hit.mean():.4f}" + (f" median {np.median(t):.6g} mean {t.mean():.6g}" if len(t) else ""))
+        for ti, tau in enumerate(grid):
+            at = d["samples"][:, ti, :]
+            lines.append(f"{tau:.6g} {at[:, 0].mean() / 100.0:.4f} {(hit & (d['time'] <= tau)).mean():.4f}")
+    text = "".join(ln + "\n" for ln in lines)
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def _table_note():
     """one line on stderr when the fold used rule / model values of the built-in tables (never with ViennaRNA's own tables loaded)"""
     try:
@@ -511,6 +582,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     if args.descend and args.sample is None and args.subopt is None:
         return main_descend(args)
     seqs, known, names = read_records(args)
+    if args.kinfold is not None:
+        return main_kinfold(args, seqs, names)
     if args.subopt is not None and (args.mfe or args.pf or args.sample is not None or args.kin or args.traj):
         raise SystemExit(SUBOPT_EXCLUSIVE)
     if args.sample is not None and (args.mfe or args.pf or args.kin or args.traj):

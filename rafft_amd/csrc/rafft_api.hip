@@ -31,7 +31,7 @@
 #include <pthread.h>
 
 // kernels (rafft_kernels.hip - the shared device helpers, which in turn includes one file per fold kernel: rafft_expand.hip,
-// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip - is compiled into the same translation
+// rafft_expand_small.hip, rafft_beam.hip, rafft_materialize.hip, rafft_io_kernels.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip, rafft_kinfold.hip - is compiled into the same translation
 // unit so the templates and the Dev struct are shared without a device-link step)
 #include "rafft_kernels.hip"
 #include "rafft_kin.hip"
@@ -50,7 +50,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, pf_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch, kinfold_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -477,6 +477,58 @@ int rafft_barriers_counters(long long out[6])
     std::lock_guard<std::mutex> lk(g.mu);
     if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
     for (int k = 0; k < 6; k++) out[k] = g_barriers_counters[k];
+    return 0;
+}
+
+int rafft_kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                        int n_rep, const int *n_watch, const int *n_stop, const char *const *watch, const int *watch_stride,
+                        const unsigned long long *seeds, double temp, double kt, double t_max, int max_steps, int n_times, const double *sample_times,
+                        long long workspace_bytes, rafft_kinfold_seq *seq_out, rafft_kinfold_traj *traj_out, char *const *db_out,
+                        int32_t *const *samples_out, int *const *moves_out, double *const *times_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (const char *what = kinfold_check_call(n_rep, kt, t_max, max_steps, n_times, sample_times, workspace_bytes)) return fail(RAFFT_ERR_PARAM, what);
+    if (n_seq > 0 && (!seqs || !lens || !n_rows || !rows || !row_stride || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
+    if (n_seq > 0 && n_watch && (!n_stop || !watch || !watch_stride)) return fail(RAFFT_ERR_PARAM, "null argument");
+    if (n_seq > 0 && n_times > 0 && !samples_out) return fail(RAFFT_ERR_PARAM, "null argument");
+    if (n_seq > 0 && (moves_out == nullptr) != (times_out == nullptr)) return fail(RAFFT_ERR_PARAM, "moves_out and times_out go together");
+    long long total = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const std::string who = "sequence " + std::to_string(s);
+        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative row count");
+        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+        if (n_watch) {
+            if (const char *what = kinfold_check_watch(n_watch[s], n_stop[s])) return fail(RAFFT_ERR_PARAM, who + ": " + what);
+            if (n_watch[s] > 0) {
+                if (!watch[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+                if (watch_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
+            }
+        }
+        if (n_rows[s] > 0) {
+            if (!rows[s] || !db_out[s] || (n_times > 0 && !samples_out[s])) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+            if (row_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
+            if (moves_out && (moves_out[s] == nullptr) != (times_out[s] == nullptr)) return fail(RAFFT_ERR_PARAM, who + ": moves_out and times_out go together");
+        }
+        total += (long long)n_rows[s] * n_rep;
+        if (total > 0x7fffffffll) return fail(RAFFT_ERR_PARAM, "more than 2^31 - 1 trajectories");
+    }
+    if (total > 0 && !traj_out) return fail(RAFFT_ERR_PARAM, "null argument");
+    return kinfold_batch(n_seq, seqs, lens, n_rows, rows, row_stride, n_rep, n_watch, n_stop, watch, watch_stride, seeds, temp, kt, t_max, max_steps,
+                         n_times, sample_times, workspace_bytes, seq_out, traj_out, db_out, samples_out, moves_out, times_out);
+}
+
+int rafft_kinfold_weights(double temp, double kt, uint64_t *out)
+{
+    if (!out || !(temp > -273.15 && temp < 1000.0) || !kinfold_weights(temp, kt, out)) return RAFFT_ERR_PARAM;
+    return 0;
+}
+
+int rafft_kinfold_counters(long long out[4])
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!out) return fail(RAFFT_ERR_PARAM, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = g_kinfold_counters[k];
     return 0;
 }
 

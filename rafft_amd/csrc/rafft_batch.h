@@ -1,7 +1,7 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
 // function and pair probabilities), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
-// energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima) and barriers_batch (exact barrier trees of energy bands), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
+// energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima), barriers_batch (exact barrier trees of energy bands) and kinfold_batch (stochastic folding trajectories), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
 // sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
 // the launches.  The sequence drivers share their opening (SeqCall) and their view of a chunk (ChunkView).
@@ -1077,6 +1077,161 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
         }
     }
     return finish();
+}
+
+// ---- stochastic folding trajectories
+
+constexpr size_t KINFOLD_WORKSPACE = (size_t)512 << 20;
+
+// of the last call: chunks, kernel launches, trajectories that ran, steps over all trajectories
+long long g_kinfold_counters[4];
+
+// rafft_kinfold_batch (arguments validated by the entry point).  One pack of the sequences; the watched rows of every sequence
+// without an error become pair tables (a bad one is the sequence's error); every start row of what is left is checked
+// (descend_parse_row; its pair table is formed again when its chunk is staged, once for its n_rep trajectories); the trajectories
+// are laid out in chunks (kinfold_layout).  Per call: one upload of the weight table, the sample times and the watched tables.  Per
+// chunk: one upload of the pair tables, one launch of kinfold_kernel (one wavefront per trajectory), one download of the end rows,
+// the records, the sample records and - when any trajectory of the chunk has a log - the logs, one synchronise.
+int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
+                  int n_rep, const int *n_watch, const int *n_stop, const char *const *watch, const int *watch_stride,
+                  const unsigned long long *seeds, double temp, double kt, double t_max, int max_steps, int n_times, const double *sample_times,
+                  long long workspace_bytes, rafft_kinfold_seq *seq_out, rafft_kinfold_traj *traj_out, char *const *db_out,
+                  int32_t *const *samples_out, int *const *moves_out, double *const *times_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    for (long long &c : g_kinfold_counters) c = 0;
+    if (n_seq == 0) return 0;
+    std::vector<uint64_t> wtab(RAFFT_KINFOLD_NW);
+    if (!kinfold_weights(temp, kt, wtab.data())) return fail(RAFFT_ERR_PARAM, "kT is not above 0");
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_KINFOLD_MAX_LEN);
+    // the call's error text names the first erroneous item in input order: (sequence, trajectory), -1 for the sequence itself
+    std::string err = pk.first_err;
+    long long err_at = -1;
+    for (int s = 0; s < n_seq && err_at < 0; s++) if (pk.status[s]) err_at = ((long long)s << 32);
+    auto note = [&](int s, long long k, const std::string &msg) {
+        const long long at = ((long long)s << 32) + k + 1;
+        if (err_at < 0 || at < err_at) { err_at = at; err = msg; }
+    };
+    const int bound = kinfold_bound(max_steps);
+    struct Where { int s, k; };
+    std::vector<Where> run;
+    std::vector<int> wL, wnw, wns;
+    std::vector<unsigned> wk;
+    std::vector<unsigned long long> wcode, wwt, wseed;
+    std::vector<unsigned char> wlog;
+    std::vector<int16_t> pt, watch_pt;  // (pt: one table, filled again per row; watch_pt: the watched tables of the call)
+    int traj0 = 0;
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.len[s], L = pk.L[s], nw = n_watch ? n_watch[s] : 0, ns = n_watch ? n_stop[s] : 0;
+        const int n_traj = n_rows[s] * n_rep;
+        int status = pk.status[s];
+        const unsigned long long wt_off = watch_pt.size();
+        for (int w = 0; w < nw && !status; w++) {
+            if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, watch[s] + (size_t)w * (size_t)watch_stride[s], pt)) {
+                status = RAFFT_ERR_STRUCT;
+                watch_pt.resize(wt_off);
+                note(s, -1, "sequence " + std::to_string(s) + " watched row " + std::to_string(w) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3");
+            } else watch_pt.insert(watch_pt.end(), pt.begin(), pt.end());
+        }
+        seq_out[s] = rafft_kinfold_seq{status, len, n_traj, traj0};
+        for (int r = 0; r < n_rows[s]; r++) {
+            int st = status;
+            const char *row = rows[s] + (size_t)r * (size_t)row_stride[s];
+            if (!st && descend_parse_row(pk.codes.data() + pk.code_off[s], L, row, pt)) {
+                st = RAFFT_ERR_STRUCT;
+                note(s, (long long)r * n_rep, "sequence " + std::to_string(s) + " row " + std::to_string(r) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3");
+            }
+            for (int rep = 0; rep < n_rep; rep++) {
+                const int k = r * n_rep + rep;
+                traj_out[traj0 + k] = rafft_kinfold_traj{st, 0, 0, 0, 0, -1, 0.0};
+                if (!st) {
+                    run.push_back(Where{s, k});
+                    wL.push_back(L); wk.push_back((unsigned)k); wcode.push_back(pk.code_off[s]); wwt.push_back(wt_off);
+                    wseed.push_back(seeds ? seeds[s] : 0ull); wnw.push_back(nw); wns.push_back(ns);
+                    wlog.push_back(moves_out && times_out && moves_out[s] && times_out[s] ? 1 : 0);
+                    continue;
+                }
+                char *db = db_out[s] + (size_t)k * ((size_t)len + 1);
+                if (status) dot_row(db, len);
+                else {
+                    const size_t n = strnlen(row, (size_t)L);       // (the row comes back as it went in)
+                    memcpy(db, row, n);
+                    db[n] = 0;
+                }
+                if (n_times && samples_out && samples_out[s])
+                    for (int t = 0; t < n_times; t++) { int32_t *o = samples_out[s] + ((size_t)k * n_times + t) * 2; o[0] = INT32_MIN; o[1] = -2; }
+            }
+        }
+        traj0 += n_traj;
+    }
+    g_err = err;
+    if (run.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    const KfLayout y = kinfold_layout(run.size(), wL.data(), wk.data(), wcode.data(), wwt.data(), wseed.data(), wnw.data(), wns.data(), wlog.data(),
+                                      bound, n_times, workspace_bytes > 0 ? (size_t)workspace_bytes : KINFOLD_WORKSPACE);
+    KfTraj *d_ws; KfRec *d_rec; KfSample *d_smp; unsigned char *d_io, *d_log = nullptr;
+    unsigned long long *d_wtab; double *d_times; int16_t *d_watch;
+    if (int rc = mem.alloc(d_ws, run.size() * sizeof(KfTraj))) return rc;
+    if (int rc = mem.alloc(d_rec, run.size() * sizeof(KfRec))) return rc;
+    if (int rc = mem.alloc(d_smp, y.max_traj * (size_t)n_times * sizeof(KfSample) + 16)) return rc;
+    if (int rc = mem.alloc(d_io, y.max_io + 16)) return rc;
+    if (y.max_log) if (int rc = mem.alloc(d_log, y.max_log + 16)) return rc;   // (no caller asked for a log: no buffer)
+    if (int rc = mem.alloc(d_wtab, wtab.size() * sizeof(uint64_t))) return rc;
+    if (int rc = mem.alloc(d_times, (size_t)n_times * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(d_watch, watch_pt.size() * sizeof(int16_t) + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_ws, y.ws.data(), run.size() * sizeof(KfTraj), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_wtab, wtab.data(), wtab.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_times) HIPCHK(hipMemcpyAsync(d_times, sample_times, (size_t)n_times * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!watch_pt.empty()) HIPCHK(hipMemcpyAsync(d_watch, watch_pt.data(), watch_pt.size() * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    std::vector<unsigned char> io(y.max_io + 16), lg(y.max_log + 16);
+    std::vector<KfRec> rec(run.size());
+    std::vector<KfSample> smp(y.max_traj * (size_t)n_times + 1);
+    g_kinfold_counters[0] = (long long)y.plan.chunks.size();
+    g_kinfold_counters[2] = (long long)run.size();
+    for (size_t ci = 0; ci < y.plan.chunks.size(); ci++) {
+        const ChunkPlan::Range &c = y.plan.chunks[ci];
+        const size_t nt = c.b - c.a;
+        for (size_t t = c.a; t < c.b; t++) {
+            const int s = run[t].s, r = run[t].k / n_rep;
+            if (t == c.a || run[t - 1].s != s || run[t - 1].k / n_rep != r)
+                if (descend_parse_row(pk.codes.data() + pk.code_off[s], wL[t], rows[s] + (size_t)r * (size_t)row_stride[s], pt))
+                    return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+            memcpy(io.data() + y.ws[t].io_off, pt.data(), (size_t)wL[t] * 2);
+        }
+        HIPCHK(hipMemcpyAsync(d_io, io.data(), y.chunk_io[ci], hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(kinfold_kernel<0>, dim3((unsigned)nt), dim3(64), (size_t)kinfold_lds_bytes(y.chunk_lmax[ci]), st, g.T, d_ws + c.a, sc.d_codes,
+                           d_io, d_log, d_watch, d_wtab, d_times, n_times, t_max, d_smp, d_rec + c.a);
+        HIPCHK(hipGetLastError());
+        g_kinfold_counters[1]++;
+        HIPCHK(hipMemcpyAsync(io.data(), d_io, y.chunk_io[ci], hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rec.data() + c.a, d_rec + c.a, nt * sizeof(KfRec), hipMemcpyDeviceToHost, st));
+        if (n_times) HIPCHK(hipMemcpyAsync(smp.data(), d_smp, nt * (size_t)n_times * sizeof(KfSample), hipMemcpyDeviceToHost, st));
+        if (y.chunk_log[ci]) HIPCHK(hipMemcpyAsync(lg.data(), d_log, y.chunk_log[ci], hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t t = c.a; t < c.b; t++) {
+            const int s = run[t].s, k = run[t].k, L = wL[t];
+            const KfRec &d = rec[t];
+            const std::string who = "sequence " + std::to_string(s) + " trajectory " + std::to_string(k);
+            if (d.flags & KF_BAD_PAIR) return fail(RAFFT_ERR_HIP, "internal: " + who + ": a non-canonical pair on the device");
+            if (d.flags & KF_STUCK) return fail(RAFFT_ERR_HIP, "internal: " + who + ": the drawn number met no move");
+            if (d.n_steps < 0 || d.n_steps > bound) return fail(RAFFT_ERR_HIP, "internal: " + who + ": more steps than the bound");
+            traj_out[seq_out[s].traj0 + k] = rafft_kinfold_traj{(d.flags & KF_MORE) ? RAFFT_ERR_CAPACITY : 0, d.flags, d.n_steps, d.start, d.end, d.stop, d.time};
+            if (d.flags & KF_MORE) note(s, k, who + ": not ended after " + std::to_string(d.n_steps) + " steps (max_steps)");
+            memcpy(db_out[s] + (size_t)k * ((size_t)L + 1), io.data() + y.ws[t].io_off, (size_t)L + 1);
+            if (n_times && samples_out && samples_out[s])
+                memcpy(samples_out[s] + (size_t)k * n_times * 2, smp.data() + (t - c.a) * (size_t)n_times, (size_t)n_times * sizeof(KfSample));
+            if (wlog[t] && d.n_steps) {
+                memcpy(moves_out[s] + (size_t)k * 2 * (size_t)bound, lg.data() + y.ws[t].log_off, (size_t)d.n_steps * 8);
+                memcpy(times_out[s] + (size_t)k * (size_t)bound, lg.data() + y.ws[t].log_off + 8ull * (size_t)bound, (size_t)d.n_steps * 8);
+            }
+            g_kinfold_counters[3] += d.n_steps;
+        }
+    }
+    g_err = err;
+    return 0;
 }
 
 } // namespace

@@ -1,6 +1,6 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip and rafft_barriers.hip read and write, and the sizes both sides
-// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree).  The layouts that fill the records are in
+// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
+// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree, the buffers of a folding trajectory).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
 
@@ -198,3 +198,52 @@ struct BarRec {
 };
 #define BAR_EDGES_FULL 1            // more distinct edges than edge_cap, or no free slot
 #define BAR_TABLE_BAD 2             // a row table without a free slot, or a rank outside the sequence in it (cannot happen)
+
+// ---- stochastic folding trajectories (rafft_kinfold.hip)
+
+// What a trajectory over L positions has on the device.  Its row, in the chunk's row buffer from io_off, as a walk of descend has it:
+// the pair table on the way in, the end row and a NUL on the way out.  Its log, when the caller asked for it, in the chunk's log
+// buffer from log_off: 2 x bound ints (the moves, as descend's) and behind them bound doubles (the time of every jump).  Its sample
+// records, n_times of them, in the chunk's sample buffer at (its number in the chunk) * n_times.  The watched rows of its sequence
+// are n_watch pair tables of L int16 each, back to back from element wt_off of the call's watch buffer.
+#define RAFFT_KINFOLD_NW 4096                   // entries of the weight table: dE of 0 .. NW - 1 dcal; weight 0 beyond it
+#define RAFFT_KINFOLD_MAX_WATCH 64              // one lane of the wavefront per watched row
+#define RAFFT_KINFOLD_DEFAULT_STEPS (1 << 20)   // the steps a trajectory may take when max_steps is 0
+#define KINFOLD_NO_LOG (~0ull)
+#define KINFOLD_W0 (1ull << 32)                 // the weight of a move with dE <= 0: rate 1
+RAFFT_HD constexpr unsigned long long kinfold_io_bytes(int L) { return fp_align16(2ull * (unsigned long long)L); }
+RAFFT_HD constexpr unsigned long long kinfold_log_bytes(int bound) { return 16ull * (unsigned long long)bound; }
+RAFFT_HD constexpr int kinfold_bound(int max_steps) { return max_steps > 0 ? max_steps : RAFFT_KINFOLD_DEFAULT_STEPS; }
+// dynamic LDS of the kernel for the longest trajectory of a chunk: the pair table and the weight subtotal of every position
+RAFFT_HD constexpr int kinfold_pt_bytes(int L) { return (2 * L + 15) & ~15; }
+RAFFT_HD constexpr int kinfold_lds_bytes(int L) { return kinfold_pt_bytes(L) + 8 * L; }
+
+struct KfTraj {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long io_off;      // first byte of its row in the chunk's row buffer
+    unsigned long long log_off;     // first byte of its log in the chunk's log buffer, or KINFOLD_NO_LOG
+    unsigned long long wt_off;      // first int16 of its sequence's watched pair tables
+    unsigned long long seed;        // its sequence's
+    unsigned k;                     // its number within the sequence: the first word of its Philox counters
+    int L, bound;
+    int n_watch, n_stop;
+    int _pad;
+};
+struct KfSample {
+    int dcal;                       // the energy of the state at that time; INT32_MIN: not reached (KF_MORE)
+    int watch;                      // the lowest watched row the state equals, -1: none, -2: not reached
+};
+struct KfRec {
+    int flags;                      // KF_*
+    int n_steps;
+    int start, end;                 // energies of the start row and of the row the trajectory ended in
+    int stop;                       // the stop row it arrived at, or -1
+    int _pad;
+    double time;
+};
+#define KF_TIME 1                   // the next jump lies beyond t_max
+#define KF_STOP 2                   // arrived at a stop row
+#define KF_ABSORBED 4               // no neighbour has a weight above 0
+#define KF_MORE 8                   // `bound` steps taken and another would be taken
+#define KF_BAD_PAIR 16              // a non-canonical pair met on the device (the host refuses them: cannot happen)
+#define KF_STUCK 32                 // the drawn number met no move (cannot happen: it is below the sum of the weights)

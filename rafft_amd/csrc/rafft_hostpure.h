@@ -1,8 +1,8 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
 // that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
 // (chunks within a budget, the sequence pack, the graph pack, the solve order, the layouts of the four sequence drivers: every
-// offset their kernels dereference, as records of rafft_batch_layout.h - the moves, conflict masks and layout of findpath, the rows and layout of descend, the layout and the tree of barriers).
-// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp, descend_check.cpp, barriers_check.cpp).  Part of the single translation unit
+// offset their kernels dereference, as records of rafft_batch_layout.h - the moves, conflict masks and layout of findpath, the rows and layout of descend, the layout and the tree of barriers, the weight table, argument checks and layout of kinfold).
+// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp, descend_check.cpp, barriers_check.cpp, kinfold_check.cpp).  Part of the single translation unit
 // of rafft_api.hip (included there, before the kernels).
 #pragma once
 
@@ -10,6 +10,7 @@
 #include "rafft_batch_layout.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -578,6 +579,85 @@ static void barriers_tree(int n_minima, const std::vector<rafft_barriers_edge> &
         }
         for (int32_t m : lost) { father[m] = find(m); saddle_rank[m] = t; }
     }
+}
+
+// ---- rafft_kinfold_batch: the weight table, the call's own arguments and the layout of a call
+
+#define KINFOLD_GAS 1.98717e-3      // kcal / (mol K), as PF_GAS of rafft_pf.hip
+
+// kT of a call in kcal/mol: kt, or the gas constant times the absolute temperature when kt is 0
+static double kinfold_kT(double temp, double kt) { return kt != 0.0 ? kt : KINFOLD_GAS * (temp + 273.15); }
+
+// The weights of a call: W[0] = 2^32 (every dE <= 0), W[d] = floor(2^32 exp(-d / (100 kT)) + 0.5) for d dcal uphill; beyond the
+// table the weight is 0.  false: kt negative or not finite, or a kT that is not above 0 and finite.
+static bool kinfold_weights(double temp, double kt, uint64_t *out)
+{
+    if (!(kt >= 0.0) || !std::isfinite(kt)) return false;
+    const double kT = kinfold_kT(temp, kt);
+    if (!(kT > 0.0) || !std::isfinite(kT)) return false;
+    out[0] = KINFOLD_W0;
+    for (int d = 1; d < RAFFT_KINFOLD_NW; d++) out[d] = (uint64_t)std::floor(4294967296.0 * std::exp(-(double)d / (100.0 * kT)) + 0.5);
+    return true;
+}
+
+// what is wrong with the arguments of a call that are not a sequence's own, or null
+static const char *kinfold_check_call(int n_rep, double kt, double t_max, int max_steps, int n_times, const double *sample_times, long long workspace_bytes)
+{
+    if (n_rep < 1) return "n_rep below 1";
+    if (!(kt >= 0.0) || !std::isfinite(kt)) return "kt negative or not finite";
+    if (!(t_max >= 0.0) || !std::isfinite(t_max)) return "t_max negative or not finite";
+    if (max_steps < 0 || workspace_bytes < 0 || n_times < 0) return "negative argument";
+    if (n_times > 0 && !sample_times) return "null argument";
+    for (int t = 0; t < n_times; t++) {
+        if (!(sample_times[t] >= 0.0) || !(sample_times[t] <= t_max)) return "a sample time outside [0, t_max]";
+        if (t > 0 && sample_times[t] < sample_times[t - 1]) return "sample times descend";
+    }
+    return nullptr;
+}
+static const char *kinfold_check_watch(int n_watch, int n_stop)
+{
+    if (n_watch < 0 || n_stop < 0) return "negative count";
+    if (n_watch > RAFFT_KINFOLD_MAX_WATCH) return "more than 64 watched rows";
+    if (n_stop > n_watch) return "more stop rows than watched rows";
+    return nullptr;
+}
+
+// The trajectories that run (those without an error, in input order; trajectory t is over L[t] positions, the k[t]-th of its
+// sequence, its bases at code_off[t], its sequence's watched tables at wt_off[t], want_log[t]: the caller asked for its moves and
+// times): chunks of whole trajectories whose rows, sample records and logs together fit the budget, one at least,
+// KINFOLD_CHUNK_TRAJ at most.  Per chunk the rows lie back to back from byte 0 of the row buffer, the logs from byte 0 of the log
+// buffer, the sample records n_times apiece in the order of the trajectories.
+constexpr size_t KINFOLD_CHUNK_TRAJ = (size_t)1 << 22;
+struct KfLayout {
+    std::vector<KfTraj> ws;             // one per trajectory that runs
+    std::vector<size_t> bytes;          // per trajectory: row, samples and log
+    ChunkPlan plan;
+    std::vector<size_t> chunk_io, chunk_log;        // bytes of a chunk's rows / logs
+    std::vector<int> chunk_lmax;
+    size_t max_io = 0, max_log = 0, max_traj = 0;
+};
+static KfLayout kinfold_layout(size_t n, const int *L, const unsigned *k, const unsigned long long *code_off, const unsigned long long *wt_off,
+                               const unsigned long long *seed, const int *n_watch, const int *n_stop, const unsigned char *want_log, int bound,
+                               int n_times, size_t budget)
+{
+    KfLayout y;
+    y.ws.resize(n); y.bytes.resize(n);
+    const size_t log_bytes = (size_t)kinfold_log_bytes(bound), smp_bytes = (size_t)n_times * sizeof(KfSample);
+    for (size_t t = 0; t < n; t++) y.bytes[t] = (size_t)kinfold_io_bytes(L[t]) + smp_bytes + (want_log[t] ? log_bytes : 0);
+    y.plan = plan_chunks(n, y.bytes.data(), nullptr, budget, KINFOLD_CHUNK_TRAJ);
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        size_t io = 0, lg = 0;
+        int lmax = 0;
+        for (size_t t = c.a; t < c.b; t++) {
+            y.ws[t] = KfTraj{code_off[t], io, want_log[t] ? lg : KINFOLD_NO_LOG, wt_off[t], seed[t], k[t], L[t], bound, n_watch[t], n_stop[t], 0};
+            io += (size_t)kinfold_io_bytes(L[t]);
+            if (want_log[t]) lg += log_bytes;
+            lmax = std::max(lmax, L[t]);
+        }
+        y.chunk_io.push_back(io); y.chunk_log.push_back(lg); y.chunk_lmax.push_back(lmax);
+        y.max_io = std::max(y.max_io, io); y.max_log = std::max(y.max_log, lg); y.max_traj = std::max(y.max_traj, c.b - c.a);
+    }
+    return y;
 }
 
 // the step a step of a folding graph is compared with: the reference compares step 0 with the LAST step (fast_paths[-1], rafft_kin.py:75)

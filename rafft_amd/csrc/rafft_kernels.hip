@@ -29,6 +29,7 @@
 //   descend_kernel      (rafft_descend.hip) gradient walks to local minima, on loop_energy and findpath's view
 //   barriers_*_kernel   (rafft_barriers.hip) exact barrier trees of energy bands: keys, a hash table of the rows, neighbours looked up
 //                       in it; no energy is evaluated
+//   kinfold_kernel      (rafft_kinfold.hip) stochastic folding trajectories: descend's neighbours, summed weights, Philox
 //
 // This is bandwidth/latency-bound small-FFT + integer table work: no MFMA.
 #include "rafft_kernels.h"
@@ -181,3 +182,4 @@ struct PlainView {
 #include "rafft_findpath.hip"           // findpath_init_kernel, findpath_expand_kernel, findpath_select_kernel, findpath_trace_kernel
 #include "rafft_descend.hip"            // descend_kernel
 #include "rafft_barriers.hip"           // barriers_keys_kernel, barriers_insert_kernel, barriers_scan_kernel, barriers_basin_kernel
+#include "rafft_kinfold.hip"            // kinfold_kernel
