@@ -386,6 +386,50 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
                    double *const *prob_out     /* may be NULL, and so may prob_out[s]: lens[s] x lens[s] doubles, row-major,
                                                   P(i pairs j) at [i][j] for i < j, 0 elsewhere */);
 
+/* Maximum-expected-accuracy (MEA) structures and the ensemble diversity of a batch.  Replaces: what
+ * `RNAfold -p --MEA` prints beside the centroid.  rafft_mea_batch is rafft_pf_batch plus the recursion below on the device's own
+ * P; rafft_mea_probs_batch runs the same recursion on matrices the caller brings - pair probabilities, or pair frequencies of
+ * sampled rows, of a beam, of an energy band (the row is then their consensus structure).
+ * Definition, exact - same input, same bits.  For P(i,j), i < j, positions from 0, and gamma > 0 (0 means 1.0):
+ *   q_i = max(0, 1 - s_i), s_i the sum of P over the partners of i in ascending partner index; formed once and stored.
+ *   W(i,j) = (gamma + gamma) * P(i,j), one rounded multiply, formed once and stored.  (k,j) is a candidate iff P(k,j) > 0.
+ *   E[i][j] = 0 for j < i; else the maximum of E[i][j-1] + q_j and, over the candidates (k,j) with i <= k < j, of
+ *   (E[i][k-1] + W(k,j)) + E[k+1][j-1] in this association.  mea = E[0][L-1].
+ *   The row: intervals from (0, L-1); of (i,j), j is unpaired when E[i][j] == E[i][j-1] + q_j (go on with (i, j-1)), else j pairs
+ *   with the first k ascending whose candidate has the bits of E[i][j] (go on with (i, k-1) and (k+1, j-1)).  A cell that nothing
+ *   reproduces is RAFFT_ERR_HIP with a message, never a silently wrong row.
+ *   diversity = sum over i < j of 2 P(i,j) (1 - P(i,j)): per position the terms of its partners above it in ascending order, then
+ *   the positions' sums lane-strided over 64 lanes and a butterfly - an order that depends on the length only.
+ * rafft_mea_batch: arguments, chunks, errors of a sequence (RAFFT_ERR_CAPACITY included: all-dot row, zeros, the call returns
+ * RAFFT_OK) and RAFFT_ERR_TEMP as rafft_pf_batch; energy, mfe_dcal and prob_out have the bits rafft_pf_batch returns.  P > 0 holds
+ * only for canonical pairs with j - i > 3, so the row holds only such pairs; as in ViennaRNA it may hold an interior loop of more
+ * than 30 unpaired positions, which the ensemble does not; dcal is what rafft_eval_structure gives for the row.  RAFFT_ERR_PARAM,
+ * before anything is launched: rafft_pf_batch's cases and a gamma that is negative or not finite.
+ * rafft_mea_probs_batch: prob_in[s] is lens[s] x lens[s] doubles, row-major; only [i][j] with i < j is read.  Four L x L fp64
+ * tables a matrix, in chunks of whole matrices that fit workspace_bytes (0: 512 MiB; one matrix at least).  RAFFT_ERR_PARAM, before
+ * anything is launched and naming (sequence, i, j) in rafft_last_error(): an entry with i < j that is not finite, below 0, above 1,
+ * or non-zero with j - i <= 3; also a null argument, a negative count or workspace_bytes, a gamma that is negative or not finite.
+ * Row sums are not checked (frequencies of crossing rows are a legitimate input; q is clamped).  lens[s] <= 0 is RAFFT_ERR_EMPTY
+ * and a length above RAFFT_PF_MAX_LEN RAFFT_ERR_TOO_LONG: errors of that matrix only.
+ * Both: a sequence's result depends on its own inputs only, not on the batch, its order, the chunks or the workspace.
+ * Outputs (host): seq_out[s]; db_out[s] = lens[s] + 1 bytes, the MEA row; unpaired_out may be NULL and so may unpaired_out[s],
+ * else lens[s] doubles, q. */
+typedef struct {
+    int32_t status, length, mfe_dcal, n_pairs;
+    int32_t dcal, _pad;          /* energy of the MEA row */
+    double  energy;              /* ensemble free energy: the bits rafft_pf_batch returns */
+    double  mea, diversity;
+} rafft_mea_seq;                 /* 48 bytes */
+int rafft_mea_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                    double scale_factor, long long workspace_bytes, double gamma /* 0: 1.0 */,
+                    rafft_mea_seq *seq_out, char *const *db_out /* the MEA row */,
+                    double *const *prob_out /* may be NULL / hold NULLs */,
+                    double *const *unpaired_out /* may be NULL / hold NULLs: lens[s] doubles, q */);
+typedef struct { int32_t status, length, n_pairs, _pad; double mea, diversity; } rafft_mea_probs_seq;   /* 32 bytes */
+int rafft_mea_probs_batch(int n, const int *lens, const double *const *prob_in /* L x L row-major, [i][j], i<j read */,
+                          double gamma, long long workspace_bytes,
+                          rafft_mea_probs_seq *seq_out, char *const *db_out, double *const *unpaired_out);
+
 /* Structures drawn from the Boltzmann ensemble of a batch (stochastic traceback).  Replaces:
  * RNA.fold_compound(seq, md).pbacktrack(n) / `RNAsubopt -p n`, what a user of the reference takes from ViennaRNA to compare
  * fast-folding paths with the thermodynamic ensemble.

@@ -68,6 +68,18 @@ class PfSeq(C.Structure):
 PF_MAX_LEN = MFE_MAX_LEN         # RAFFT_PF_MAX_LEN
 
 
+class MeaSeq(C.Structure):
+    """rafft_mea_seq: one record per sequence of rafft_mea_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("mfe_dcal", C.c_int32), ("n_pairs", C.c_int32), ("dcal", C.c_int32),
+                ("_pad", C.c_int32), ("energy", C.c_double), ("mea", C.c_double), ("diversity", C.c_double)]
+
+
+class MeaProbsSeq(C.Structure):
+    """rafft_mea_probs_seq: one record per matrix of rafft_mea_probs_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("n_pairs", C.c_int32), ("_pad", C.c_int32), ("mea", C.c_double),
+                ("diversity", C.c_double)]
+
+
 class SampleSeq(C.Structure):
     """rafft_sample_seq: one record per sequence of rafft_sample_batch"""
     _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("mfe_dcal", C.c_int32), ("n_samples", C.c_int32), ("energy", C.c_double)]
@@ -162,7 +174,8 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_score_rows", "rafft_score_result", "rafft_kin_batch", "rafft_mfe_batch", "rafft_mfe_lds_len", "rafft_pf_batch",
            "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
            "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters", "rafft_barriers_batch",
-           "rafft_barriers_free", "rafft_barriers_counters", "rafft_kinfold_batch", "rafft_kinfold_weights", "rafft_kinfold_counters"]
+           "rafft_barriers_free", "rafft_barriers_counters", "rafft_kinfold_batch", "rafft_kinfold_weights", "rafft_kinfold_counters",
+           "rafft_mea_batch", "rafft_mea_probs_batch"]
 
 _lib = None
 
@@ -255,6 +268,10 @@ def lib():
     L.rafft_mfe_lds_len.argtypes = []
     L.rafft_pf_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.POINTER(PfSeq),
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_mea_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.c_double,
+                                  C.POINTER(MeaSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_mea_probs_batch.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_double, C.c_longlong, C.POINTER(MeaProbsSeq),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_sample_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.c_int,
                                      C.POINTER(C.c_ulonglong), C.POINTER(SampleSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_subopt_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_int, C.c_longlong,

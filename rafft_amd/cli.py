@@ -58,6 +58,13 @@ _OPTIONS = [
                                                "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
                                                "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
                                                "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --kin or --traj")),
+    (("--mea",), dict(type=float, nargs="?", const=1.0, default=None, metavar="GAMMA",
+                      help="no RAFFT fold: the maximum-expected-accuracy structure of every sequence on the GPU (rafft_amd.mea_batch; the\n"
+                           "pair probabilities of --pf; GAMMA weighs a pair against an unpaired base, default 1.0), one line per sequence:\n"
+                           "seq len structure energy_of_structure mea diversity.  With --scores the MEA rows are scored.  With --sample N\n"
+                           "the consensus of the N sampled rows (rafft_amd.mea_from_probs on their pair frequencies: seq len structure mea\n"
+                           "diversity) in place of the graph text.  Works with -s SEQ and with -sf FILE --batch; not with --mfe, --pf,\n"
+                           "--subopt, --kin or --traj")),
     (("--sample",), dict(type=int, metavar="N", help="no RAFFT fold: N structures drawn from the Boltzmann ensemble of every sequence on the GPU\n"
                                                      "(rafft_amd.sample_batch; the ensemble of --pf).  Per sequence the fast-folding-graph text with a single\n"
                                                      "step 0 that holds the distinct sampled structures, energy ascending - `rafft_landscape OUT` draws the\n"
@@ -291,6 +298,50 @@ def main_pf(args, seqs, known, names, pf_batch=None, scorer=None):
         sys.stdout.write(text)
 
 
+MEA_EXCLUSIVE = "--mea gives the maximum-expected-accuracy structure of every sequence: no --mfe, no --pf, no --subopt, no --kin, no --traj"
+
+
+def check_gamma(gamma):
+    import math
+    if not (math.isfinite(gamma) and gamma > 0.0):
+        raise SystemExit("--mea GAMMA is a positive number")
+
+
+class MeaRow:
+    """a MEA row as the score table takes a structure: the row and ITS energy (a MeaResult's `energy` is the ensemble's)"""
+    def __init__(self, res):
+        self.str_struct, self.energy = res.structure, res.energy_of_structure
+
+
+def format_mea_line(sequence, res):
+    return f"{sequence} {len(sequence)} {res.structure} {res.energy_of_structure:.2f} {res.mea:.4f} {res.diversity:.4f}"
+
+
+def format_consensus_line(sequence, res):
+    return f"{sequence} {len(sequence)} {res.structure} {res.mea:.4f} {res.diversity:.4f}"
+
+
+def main_mea(args, seqs, known, names, mea_batch=None, scorer=None):
+    """--mea [GAMMA]: the MEA structures instead of the fold.  `scorer` as for main_mfe."""
+    check_gamma(args.mea)
+    if mea_batch is None:
+        from .mccaskill import mea_batch
+    results = mea_batch(seqs, args.mea, args.temp)
+    if args.scores:
+        if scorer is None:
+            from .scoring import score_rows_gpu as scorer
+        beams = [[MeaRow(r)] for r in results]
+        write_scores(args.scores, seqs, names, beams, scorer(beams, known), "energy")
+        if not args.output:
+            return
+    text = "".join(format_mea_line(s, r) + "\n" for s, r in zip(seqs, results))
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def sampled_step(structs):
     """the distinct structures of a list of samples, energy ascending, ties by row text"""
     seen = {}
@@ -305,6 +356,10 @@ def main_sample(args, seqs, known, names, sample_batch=None, scorer=None):
         raise SystemExit("--sample gives structures drawn from the ensemble of every sequence: no --mfe, no --pf, no --kin, no --traj")
     if args.sample < 1:
         raise SystemExit("--sample needs a positive number of structures")
+    if args.mea is not None:
+        check_gamma(args.mea)
+        if args.descend:
+            raise SystemExit("--sample N --mea gives the consensus of the sampled rows: no --descend")
     if sample_batch is None:
         from .mccaskill import sample_batch
     samples = sample_batch(seqs, args.sample, args.seed, args.temp)
@@ -316,7 +371,11 @@ def main_sample(args, seqs, known, names, sample_batch=None, scorer=None):
         write_scores(args.scores, seqs, names, samples, scorer(samples, known), args.select)
         if not args.output:
             return
-    if not args.descend:
+    if args.mea is not None:
+        from .mccaskill import mea_from_probs, pair_frequencies
+        consensus = mea_from_probs([pair_frequencies(sm) for sm in samples], args.mea)
+        text = "".join(format_consensus_line(s, r) + "\n" for s, r in zip(seqs, consensus))
+    elif not args.descend:
         from .utils import format_trajectory
         text = "".join(format_trajectory(s, [sampled_step(sm)]) for s, sm in zip(seqs, samples))
     if args.output:
@@ -563,13 +622,14 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None):
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None, mea_batch=None):
     """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch` / `subopt_batch`: injection points for tests (the fold, the
     callable (results, known) -> score table that stands in for scoring.score_batch_gpu - with --mfe, --pf and --sample for
     scoring.score_rows_gpu -, the callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable
     (sequences, temp) that stands in for zuker.mfe_batch, the callable (sequences, temp) that stands in for mccaskill.pf_batch,
     the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch, and the callable (sequences, delta,
-    max_structs, temp) that stands in for wuchty.subopt_batch)."""
+    max_structs, temp) that stands in for wuchty.subopt_batch; `mea_batch`: the callable (sequences, gamma, temp) that stands in for
+    mccaskill.mea_batch)."""
     args = parse_arguments(argv)
     if args.findpath:
         if args.descend:
@@ -584,6 +644,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     seqs, known, names = read_records(args)
     if args.kinfold is not None:
         return main_kinfold(args, seqs, names)
+    if args.mea is not None and (args.mfe or args.pf or args.subopt is not None or args.kin or args.traj):
+        raise SystemExit(MEA_EXCLUSIVE)
     if args.subopt is not None and (args.mfe or args.pf or args.sample is not None or args.kin or args.traj):
         raise SystemExit(SUBOPT_EXCLUSIVE)
     if args.sample is not None and (args.mfe or args.pf or args.kin or args.traj):
@@ -603,6 +665,8 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
         return main_subopt(args, seqs, known, names, subopt_batch, scorer)
     if args.sample is not None:
         return main_sample(args, seqs, known, names, sample_batch, scorer)
+    if args.mea is not None:
+        return main_mea(args, seqs, known, names, mea_batch, scorer)
     if args.pf:
         return main_pf(args, seqs, known, names, pf_batch, scorer)
     if args.mfe:

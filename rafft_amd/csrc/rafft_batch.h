@@ -1,6 +1,6 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
 // workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
-// function and pair probabilities), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
+// function and pair probabilities), mea_batch and mea_probs_batch (maximum-expected-accuracy structures), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
 // energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima), barriers_batch (exact barrier trees of energy bands) and kinfold_batch (stochastic folding trajectories), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
 // sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
@@ -365,6 +365,25 @@ int pf_front_inside(hipStream_t st, const PfFront &f, const ChunkView &v)
     return 0;
 }
 
+// What rafft_pf_batch and rafft_mea_batch do to chunk c (v: its view) of six tables a sequence after the inside pass: one launch
+// per anti-diagonal downwards, the probabilities (table 3 then holds P, the d_db rows the centroids), and the copies of P the
+// caller asked for.
+int pf_outside_probs(hipStream_t st, const PfFront &f, const ChunkView &v, const ChunkPlan::Range &c, const std::vector<int> &order, double *const *prob_out)
+{
+    for (int d = v.Lmax - 1; d >= 4; d--)
+        hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
+    HIPCHK(hipGetLastError());
+    if (prob_out)
+        for (size_t k = c.a; k < c.b; k++) {
+            const PfSeq &q = f.qs[order[k]];
+            if (prob_out[order[k]])
+                HIPCHK(hipMemcpyAsync(prob_out[order[k]], f.d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+    return 0;
+}
+
 // rafft_pf_batch (arguments validated by the entry point).  One pack, one guard, one upload of the bases.  The shared front, then
 // per chunk of six tables a sequence: the inside pass, one launch per anti-diagonal downwards, the probabilities.  One synchronise at
 // the end.
@@ -394,17 +413,7 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
     for (const ChunkPlan::Range &c : f.plan.chunks) {
         const ChunkView v = chunk_view(c, f.d_order, order, pk);
         if (int rc = pf_front_inside(st, f, v)) return rc;
-        for (int d = v.Lmax - 1; d >= 4; d--)
-            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
-        HIPCHK(hipGetLastError());
-        if (prob_out)
-            for (size_t k = c.a; k < c.b; k++) {
-                const PfSeq &q = qs[order[k]];
-                if (prob_out[order[k]])
-                    HIPCHK(hipMemcpyAsync(prob_out[order[k]], f.d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
-            }
+        if (int rc = pf_outside_probs(st, f, v, c, order, prob_out)) return rc;
     }
     std::vector<PfRec> rec(n_seq);
     std::vector<char> db(f.n_db + 16);
@@ -424,6 +433,186 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
         memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
     }
     g_err = err;
+    return 0;
+}
+
+// ---- maximum-expected-accuracy structures
+
+constexpr size_t MEA_WORKSPACE = (size_t)512 << 20;
+static_assert(MEA_NT == PF_NT, "pf_diag_blocks counts the workgroups of mea_diag_kernel too");
+
+// The recursion on the P tables of chunk v: q, WT and the diversity's shares, one launch per anti-diagonal upwards, the traceback.
+int mea_chunk(hipStream_t st, const MeaSeq *d_mq, const ChunkView &v, double *d_ws, double *d_aux, double gamma, uint32_t *d_stack, int16_t *d_pt, char *d_db,
+              MeaRec *d_rec)
+{
+    const int nt = (v.Lmax + MEA_TILE - 1) / MEA_TILE;
+    hipLaunchKernelGGL(mea_prepare_kernel, dim3((unsigned)std::min(nt * nt, 1024), v.ny), dim3(MEA_NT), 0, st, d_mq, v.ord, d_ws, d_aux, gamma);
+    HIPCHK(hipGetLastError());
+    for (int d = 0; d < v.Lmax; d++)
+        hipLaunchKernelGGL(mea_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(MEA_NT), 0, st, d_mq, v.ord, d_ws, d_aux, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mea_traceback_kernel, dim3(v.ny), dim3(64), 0, st, d_mq, v.ord, d_ws, d_aux, d_stack, d_pt, d_db, d_rec);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int mea_bad(int s, int bad)
+{
+    return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + (bad == MEA_BAD_STACK ? ": the stack of pending intervals is full" : ": the traceback found no candidate for a cell"));
+}
+
+// rafft_mea_batch (arguments validated by the entry point; gamma > 0).  rafft_pf_batch's call - the shared front, per chunk the
+// inside pass, the outside pass and the probabilities - and then, per chunk, mea_chunk on table 3 with WT, E and ET in the dead
+// tables 0, 1, 2 (mea_layout), and one eval_kernel launch on the pair tables the traceback left.  One synchronise at the end.
+int mea_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, double gamma,
+              rafft_mea_seq *seq_out, char *const *db_out, double *const *prob_out, double *const *unpaired_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.len[s];
+        seq_out[s] = rafft_mea_seq{pk.status[s], len, 0, 0, 0, 0, 0.0, 0.0, 0.0};
+        dot_row(db_out[s], len);
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)len * len * sizeof(double));
+        if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, (size_t)len * sizeof(double));
+    }
+    g_err = pk.first_err;
+    const std::vector<int> &order = pk.fold;
+    if (order.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    PfFront f;
+    if (int rc = pf_front(sc, mem, pk, temp, scale_factor, workspace_bytes, 6, nullptr, f)) return rc;
+    const std::vector<PfSeq> &qs = f.qs;
+    for (int s = 0; s < n_seq; s++) seq_out[s].mfe_dcal = f.mfe[s].dcal;
+    const MeaLayout y = mea_layout(qs);
+    const size_t n_run = order.size();
+    std::vector<long long> e_off(n_run);
+    std::vector<int> e_len(n_run);
+    for (size_t k = 0; k < n_run; k++) { e_off[k] = (long long)qs[order[k]].code_off; e_len[k] = qs[order[k]].L; }
+    MeaSeq *d_mq; MeaRec *d_mrec; uint32_t *d_stack; int16_t *d_pt; long long *d_eoff; int *d_elen, *d_eout, *d_est;
+    if (int rc = mem.alloc(d_mq, y.qs.size() * sizeof(MeaSeq))) return rc;
+    if (int rc = mem.alloc(d_mrec, y.qs.size() * sizeof(MeaRec))) return rc;
+    if (int rc = mem.alloc(d_stack, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_pt, pk.codes.size() * 2)) return rc;
+    if (int rc = mem.alloc(d_eoff, n_run * 8)) return rc;
+    if (int rc = mem.alloc(d_elen, n_run * 4)) return rc;
+    if (int rc = mem.alloc(d_eout, n_run * 4)) return rc;
+    if (int rc = mem.alloc(d_est, n_run * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(d_mq, y.qs.data(), y.qs.size() * sizeof(MeaSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_eoff, e_off.data(), n_run * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_elen, e_len.data(), n_run * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_mrec, 0, y.qs.size() * sizeof(MeaRec), st));
+    for (const ChunkPlan::Range &c : f.plan.chunks) {
+        const ChunkView v = chunk_view(c, f.d_order, order, pk);
+        if (int rc = pf_front_inside(st, f, v)) return rc;
+        if (int rc = pf_outside_probs(st, f, v, c, order, prob_out)) return rc;
+        if (int rc = mea_chunk(st, d_mq, v, f.d_ws, f.d_aux, gamma, d_stack, d_pt, f.d_db, d_mrec)) return rc;
+        hipLaunchKernelGGL(eval_kernel, dim3(v.ny), dim3(64), 0, st, g.T, (int)v.ny, f.d_codes, d_pt, d_eoff + c.a, d_elen + c.a, d_eout + c.a, d_est + c.a, (int *)nullptr);
+        HIPCHK(hipGetLastError());
+        if (unpaired_out)
+            for (size_t k = c.a; k < c.b; k++) {
+                const PfSeq &q = qs[order[k]];
+                if (unpaired_out[order[k]]) HIPCHK(hipMemcpyAsync(unpaired_out[order[k]], f.d_aux + q.aux_off, (size_t)q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+    }
+    std::vector<PfRec> rec(n_seq);
+    std::vector<MeaRec> mrec(n_seq);
+    std::vector<int> e_out(n_run), e_st(n_run), run_of(n_seq, -1);
+    std::vector<char> db(f.n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), f.d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(mrec.data(), d_mrec, qs.size() * sizeof(MeaRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e_out.data(), d_eout, n_run * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e_st.data(), d_est, n_run * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), f.d_db, f.n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t k = 0; k < n_run; k++) run_of[order[k]] = (int)k;
+    std::string err = pk.first_err;
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        const size_t L = (size_t)qs[s].L;
+        if (rec[s].status || rec[s].bad) {
+            pf_left_range(s, seq_out[s].status, err, prob_out ? prob_out[s] : nullptr, L * L * sizeof(double));
+            if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, L * sizeof(double));
+            continue;
+        }
+        if (mrec[s].bad) return mea_bad(s, mrec[s].bad);
+        if (e_st[run_of[s]]) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the row holds a pair the energy model refuses");
+        seq_out[s].n_pairs = mrec[s].n_pairs;
+        seq_out[s].dcal = e_out[run_of[s]];
+        seq_out[s].energy = rec[s].energy;
+        seq_out[s].mea = mrec[s].mea;
+        seq_out[s].diversity = mrec[s].diversity;
+        memcpy(db_out[s], db.data() + qs[s].db_off, L + 1);
+    }
+    g_err = err;
+    return 0;
+}
+
+// rafft_mea_probs_batch (arguments validated by the entry point; gamma > 0).  Every matrix is checked before the device is touched;
+// then chunks of four tables a matrix (mea_probs_layout): the upload of P, mea_chunk, the download of q.  One synchronise at the end.
+int mea_probs_batch(int n, const int *lens, const double *const *prob_in, double gamma, long long workspace_bytes, rafft_mea_probs_seq *seq_out,
+                    char *const *db_out, double *const *unpaired_out)
+{
+    if (n == 0) return 0;
+    const MeaProbsLayout y = mea_probs_layout(n, lens, workspace_bytes > 0 ? (size_t)workspace_bytes : MEA_WORKSPACE);
+    for (int s : y.order) {
+        int bi = 0, bj = 0;
+        const char *why = nullptr;
+        if (mea_probs_bad_entry(prob_in[s], y.L[s], bi, bj, why))
+            return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + ": P(" + std::to_string(bi) + "," + std::to_string(bj) + ") " + why);
+    }
+    for (int s = 0; s < n; s++) {
+        seq_out[s] = rafft_mea_probs_seq{y.status[s], y.len[s], 0, 0, 0.0, 0.0};
+        dot_row(db_out[s], y.len[s]);
+        if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, (size_t)y.len[s] * sizeof(double));
+    }
+    g_err = y.first_err;
+    const std::vector<int> &order = y.order;
+    if (order.empty()) return 0;
+    SeamGuard sg;
+    if (int rc = sg.enter()) return rc;
+    hipStream_t st = sg.stream;
+    DevScratch mem;
+    MeaSeq *d_mq; MeaRec *d_mrec; uint32_t *d_stack; int16_t *d_pt; int *d_order; double *d_ws, *d_aux; char *d_db;
+    if (int rc = mem.alloc(d_mq, y.qs.size() * sizeof(MeaSeq))) return rc;
+    if (int rc = mem.alloc(d_mrec, y.qs.size() * sizeof(MeaRec))) return rc;
+    if (int rc = mem.alloc(d_stack, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_pt, y.n_pt * 2 + 16)) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_aux, y.n_aux * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(d_db, y.n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_mq, y.qs.data(), y.qs.size() * sizeof(MeaSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_mrec, 0, y.qs.size() * sizeof(MeaRec), st));
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        const ChunkView v{d_order + c.a, (unsigned)(c.b - c.a), chunk_lmax(c, order, y.L)};
+        for (size_t k = c.a; k < c.b; k++) {
+            const MeaSeq &q = y.qs[order[k]];
+            HIPCHK(hipMemcpyAsync(d_ws + q.p_off, prob_in[order[k]], (size_t)q.L * q.L * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        if (int rc = mea_chunk(st, d_mq, v, d_ws, d_aux, gamma, d_stack, d_pt, d_db, d_mrec)) return rc;
+    }
+    std::vector<MeaRec> mrec(n);
+    std::vector<char> db(y.n_db + 16);
+    if (unpaired_out)
+        for (int s : order)
+            if (unpaired_out[s]) HIPCHK(hipMemcpyAsync(unpaired_out[s], d_aux + y.qs[s].aux_off, (size_t)y.L[s] * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(mrec.data(), d_mrec, y.qs.size() * sizeof(MeaRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s : order) {
+        if (mrec[s].bad) return mea_bad(s, mrec[s].bad);
+        seq_out[s].n_pairs = mrec[s].n_pairs;
+        seq_out[s].mea = mrec[s].mea;
+        seq_out[s].diversity = mrec[s].diversity;
+        memcpy(db_out[s], db.data() + y.qs[s].db_off, (size_t)y.L[s] + 1);
+    }
+    g_err = y.first_err;
     return 0;
 }
 

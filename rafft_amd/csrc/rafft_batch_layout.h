@@ -1,5 +1,5 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_pf.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
+// of rafft_mfe.hip, rafft_pf.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
 // compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree, the buffers of a folding trajectory).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
@@ -39,6 +39,28 @@ struct PfSeq {
 struct PfRec {
     int status, n_pairs, bad, pad;  // bad: a probability that is not finite
     double energy, mfe_frequency;
+};
+
+// ---- maximum-expected-accuracy structures (rafft_mea.hip)
+
+// What a sequence of L positions has on the device.  Four L x L fp64 tables in the workspace: P (read for i < j only), WT (the
+// weights, transposed), E and its transposed copy ET.  In the aux buffer from aux_off, mea_aux_doubles(L) doubles: q (L), the
+// positions' shares of the diversity (L), the diversity.  A traceback stack of mea_stack_words(L) words (an interval is i | j << 16),
+// a pair table of L int16 (-1 = unpaired), a row of L + 1 bytes.
+RAFFT_HD constexpr unsigned long long mea_aux_doubles(int L) { return 2ull * (unsigned long long)L + 2ull; }
+RAFFT_HD constexpr unsigned long long mea_stack_words(int L) { return (unsigned long long)L + 8ull; }
+
+struct MeaSeq {
+    unsigned long long p_off, wt_off, e_off, et_off;    // first double of each table in the workspace
+    unsigned long long aux_off;     // first double of q
+    unsigned long long stack_off;   // first word of its traceback stack
+    unsigned long long pt_off;      // first int16 of its pair table
+    unsigned long long db_off;      // its row in the output (L + 1 bytes)
+    int L, pad;
+};
+struct MeaRec {
+    int bad, n_pairs;               // bad: MEA_BAD_*
+    double mea, diversity;
 };
 
 // ---- structures drawn from the ensemble (rafft_sample.hip)

@@ -346,6 +346,78 @@ static SampleLayout sample_layout(const SeqPack &pk, const ChunkPlan &plan, int 
     return y;
 }
 
+// rafft_mea_batch: the records of mea's kernels over the tables of a pf_layout with six tables a sequence.  After pf_prob_kernel
+// table 3 holds P and the others are dead: WT, E and ET go to tables 0, 1 and 2, q and the diversity over ps and pb (4 (L + 1)
+// doubles of aux are there, mea_aux_doubles(L) are taken), the pair table lies where the sequence's bases lie in `codes` (what
+// eval_kernel expects), the row where the centroid row lay.  n_stack: words of traceback stacks.
+struct MeaLayout {
+    std::vector<MeaSeq> qs;
+    unsigned long long n_stack = 0;
+};
+static MeaLayout mea_layout(const std::vector<PfSeq> &pf)
+{
+    MeaLayout y;
+    y.qs.resize(pf.size());
+    for (size_t s = 0; s < pf.size(); s++) {
+        const PfSeq &q = pf[s];
+        const unsigned long long LL = (unsigned long long)q.L * (unsigned long long)q.L;
+        y.qs[s] = MeaSeq{q.tab_off + 3 * LL, q.tab_off, q.tab_off + LL, q.tab_off + 2 * LL, q.aux_off, y.n_stack, q.code_off, q.db_off, q.L, 0};
+        if (q.L) y.n_stack += mea_stack_words(q.L);
+    }
+    return y;
+}
+
+// rafft_mea_probs_batch: matrices of lens[s] x lens[s]; status (empty before too long), `order`: the matrices without an error in
+// input order, chunks (plan: over order) of four L x L fp64 tables a matrix within the budget (one matrix at least): P, WT, E, ET
+// in this order.  n_aux doubles of q and the diversity, n_stack words of stacks, n_pt int16 of pair tables, n_db bytes of rows.
+struct MeaProbsLayout {
+    std::vector<int> status, len, L, order;
+    std::vector<MeaSeq> qs;
+    ChunkPlan plan;
+    unsigned long long n_aux = 0, n_stack = 0, n_pt = 0, n_db = 0;
+    std::string first_err;
+};
+static MeaProbsLayout mea_probs_layout(int n, const int *lens, size_t budget)
+{
+    MeaProbsLayout y;
+    y.status.resize(n); y.len.resize(n); y.L.resize(n); y.qs.resize(n);
+    for (int s = 0; s < n; s++) {
+        const int st = lens[s] <= 0 ? RAFFT_ERR_EMPTY : lens[s] > RAFFT_PF_MAX_LEN ? RAFFT_ERR_TOO_LONG : 0;
+        y.status[s] = st;
+        y.len[s] = lens[s] > 0 ? lens[s] : 0;
+        const int L = y.L[s] = st ? 0 : lens[s];
+        y.qs[s] = MeaSeq{0, 0, 0, 0, y.n_aux, y.n_stack, y.n_pt, y.n_db, L, 0};
+        if (st) {
+            if (y.first_err.empty()) y.first_err = "sequence " + std::to_string(s) + (st == RAFFT_ERR_EMPTY ? ": empty" : ": longer than RAFFT_PF_MAX_LEN");
+            continue;
+        }
+        y.n_aux += mea_aux_doubles(L); y.n_stack += mea_stack_words(L); y.n_pt += (unsigned long long)L; y.n_db += (unsigned long long)L + 1;
+        y.order.push_back(s);
+    }
+    std::vector<size_t> tab_bytes(y.order.size());
+    for (size_t k = 0; k < y.order.size(); k++) tab_bytes[k] = 4 * (size_t)y.L[y.order[k]] * y.L[y.order[k]] * sizeof(double);
+    y.plan = plan_chunks(y.order.size(), tab_bytes.data(), nullptr, budget, 65535);
+    for (size_t k = 0; k < y.order.size(); k++) {
+        MeaSeq &q = y.qs[y.order[k]];
+        const unsigned long long LL = (unsigned long long)q.L * (unsigned long long)q.L;
+        q.p_off = y.plan.off[k] / sizeof(double); q.wt_off = q.p_off + LL; q.e_off = q.wt_off + LL; q.et_off = q.e_off + LL;
+    }
+    return y;
+}
+
+// The first entry of a matrix that rafft_mea_probs_batch refuses, for i < j: one that is not finite, below 0 or above 1, or
+// non-zero with j - i <= 3.  (i, j) and the reason, or false
+static bool mea_probs_bad_entry(const double *P, int L, int &bi, int &bj, const char *&why)
+{
+    for (int i = 0; i < L; i++)
+        for (int j = i + 1; j < L; j++) {
+            const double x = P[(size_t)i * L + j];
+            const char *w = !(x - x == 0.0) ? "is not finite" : (x < 0.0 || x > 1.0) ? "is outside [0, 1]" : (j - i <= 3 && x != 0.0) ? "is not 0 although j - i <= 3" : nullptr;
+            if (w) { bi = i; bj = j; why = w; return true; }
+        }
+    return false;
+}
+
 // rafft_subopt_batch: chunks (plan: over pk.fold) of three L x L int32 tables a sequence as the primary cost, its two frontier
 // buffers of max_structs states and its max_structs counts (rounded up to 256 bytes) as the second.  Per chunk the frontiers back to
 // back from byte 0 of the frontier buffer; n_f ints of exterior energies over the whole call.  mq: what mfe_diag_kernel reads of a

@@ -1,7 +1,9 @@
 """Partition function, base-pair probabilities and centroid structures on the GPU (rafft_pf_batch): what a
 user of the reference gets from ViennaRNA's RNA.fold_compound(seq, md).pf() / bpp(), the calls beside the RNA.fold of
 benchmark_results/src/vrna_mfe.py:25.  The ensemble is the one mfe_batch minimises over.  Structures drawn from that ensemble
-(rafft_sample_batch): what ViennaRNA's pbacktrack / `RNAsubopt -p` give."""
+(rafft_sample_batch): what ViennaRNA's pbacktrack / `RNAsubopt -p` give.  Maximum-expected-accuracy structures
+and the ensemble diversity from the pair probabilities, or from pair frequencies of any rows (rafft_mea_batch /
+rafft_mea_probs_batch): what `RNAfold -p --MEA` gives."""
 import ctypes as C
 
 import numpy as np
@@ -123,3 +125,132 @@ def sample_batch(sequences, n_samples, seeds=None, temp=37.0, raise_errors=True)
 
 def sample(sequence, n_samples, seed=None, temp=37.0):
     return sample_batch([sequence], n_samples, seed, temp)[0]
+
+
+# ---- maximum-expected-accuracy structures (rafft_mea_batch / rafft_mea_probs_batch)
+
+class MeaResult:
+    """structure: the MEA row; mea: its expected accuracy, the sum of 2 gamma P over its pairs and of the unpaired probabilities
+    over its unpaired positions; energy_of_structure: the row's energy in kcal/mol (None for a row made from a matrix alone);
+    energy: the ensemble free energy in kcal/mol (None likewise); diversity: the mean base-pair distance of the ensemble, sum of
+    2 P (1 - P); unpaired: numpy array of q; probs: L x L numpy array or None.  str_struct: the row, so that the scorers take it."""
+    __slots__ = ("structure", "mea", "energy_of_structure", "energy", "diversity", "unpaired", "probs")
+
+    def __init__(self, structure, mea, energy_of_structure, energy, diversity, unpaired, probs=None):
+        self.structure, self.mea, self.energy_of_structure, self.energy = structure, mea, energy_of_structure, energy
+        self.diversity, self.unpaired, self.probs = diversity, unpaired, probs
+
+    @property
+    def str_struct(self):
+        return self.structure
+
+    def __repr__(self):
+        return f"MeaResult({self.structure!r}, mea={self.mea:.2f}, diversity={self.diversity:.2f})"
+
+
+def mea_batch_raw(sequences, gamma=1.0, temp=37.0, scale_factor=0.0, workspace_bytes=0, probs=True):
+    """(rows, records, probs, unpaired) of rafft_mea_batch: the MEA rows, one dict per sequence with the fields of rafft_mea_seq,
+    with probs=True one L x L numpy array per sequence (None beyond RAFFT_PF_MAX_LEN), and one array of L unpaired probabilities
+    per sequence; nothing is raised for a sequence's own error (its row is all dots, its numbers are 0)."""
+    L = N.lib()
+    _params_mod.ensure_default_params()
+    n = len(sequences)
+    enc, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
+    rec = (N.MeaSeq * n)()
+    pr, ptrs = None, None
+    if probs:
+        pr = [np.zeros((len(e), len(e)), dtype=np.float64) if len(e) <= N.PF_MAX_LEN else None for e in enc]
+        ptrs = (C.c_void_p * n)(*[p.ctypes.data if p is not None and p.size else None for p in pr])
+    un = [np.zeros(len(e), dtype=np.float64) for e in enc]
+    uptrs = (C.c_void_p * n)(*[u.ctypes.data if u.size else None for u in un])
+    N.check(L.rafft_mea_batch(n, arr, lens, float(temp), float(scale_factor), int(workspace_bytes), float(gamma), rec, out, ptrs, uptrs))
+    recs = [{k: getattr(r, k) for k, _ in N.MeaSeq._fields_} for r in rec]
+    return [b.value.decode("ascii") for b in bufs], recs, pr, un
+
+
+def mea_batch(sequences, gamma=1.0, temp=37.0, probs=False, raise_errors=True):
+    """The MEA structure of every sequence, as a list of MeaResult.  A sequence with an error raises what fold_batch raises for it
+    (raise_errors=False: its entry is None)."""
+    rows, recs, pr, un = mea_batch_raw(sequences, gamma, temp, probs=probs)
+    out = []
+    for k, s in enumerate(sequences):
+        st = recs[k]["status"]
+        if st != N.OK:
+            if raise_errors:
+                raise_for_status(st, s, k, "mea_batch", "RAFFT_PF_MAX_LEN", "the scaled partition function left the fp64 range")
+            out.append(None)
+        else:
+            out.append(MeaResult(rows[k], recs[k]["mea"], recs[k]["dcal"] / 100.0, recs[k]["energy"], recs[k]["diversity"], un[k],
+                                 pr[k] if pr is not None else None))
+    return out
+
+
+def mea(sequence, gamma=1.0, temp=37.0):
+    return mea_batch([sequence], gamma, temp)[0]
+
+
+def mea_from_probs_raw(matrices, gamma=1.0, workspace_bytes=0):
+    """(rows, records, unpaired) of rafft_mea_probs_batch for a list of square fp64 matrices (only [i][j], i < j, is read)"""
+    L = N.lib()
+    mats = [np.ascontiguousarray(m, dtype=np.float64) for m in matrices]
+    for k, m in enumerate(mats):
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError(f"matrix {k}: shape {m.shape} is not square")
+    n = len(mats)
+    lens = (C.c_int * n)(*[m.shape[0] for m in mats])
+    ptrs = (C.c_void_p * n)(*[m.ctypes.data if m.size else None for m in mats])
+    bufs = [C.create_string_buffer(m.shape[0] + 1) for m in mats]
+    out = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+    un = [np.zeros(m.shape[0], dtype=np.float64) for m in mats]
+    uptrs = (C.c_void_p * n)(*[u.ctypes.data if u.size else None for u in un])
+    rec = (N.MeaProbsSeq * n)()
+    N.check(L.rafft_mea_probs_batch(n, lens, ptrs, float(gamma), int(workspace_bytes), rec, out, uptrs))
+    recs = [{k: getattr(r, k) for k, _ in N.MeaProbsSeq._fields_} for r in rec]
+    return [b.value.decode("ascii") for b in bufs], recs, un
+
+
+def mea_from_probs(matrices, gamma=1.0):
+    """The MEA row of every matrix of pair probabilities or pair frequencies (pair_frequencies), as a list of MeaResult without
+    energies.  An empty matrix or one beyond RAFFT_PF_MAX_LEN raises ValueError."""
+    rows, recs, un = mea_from_probs_raw(matrices, gamma)
+    out = []
+    for k, r in enumerate(recs):
+        if r["status"] != N.OK:
+            raise ValueError(f"matrix {k}: " + ("empty" if r["status"] == N.ERR_EMPTY else "longer than RAFFT_PF_MAX_LEN"))
+        out.append(MeaResult(rows[k], r["mea"], None, None, r["diversity"], un[k], None))
+    return out
+
+
+def pair_frequencies(rows, weights=None):
+    """The L x L matrix mea_from_probs takes, from dot-bracket rows of one length (text, bytes, or objects with str_struct): at
+    [i][j], i < j, the weighted share of the rows that hold the pair (i,j).  weights: one non-negative number per row (None: all
+    equal); they are normalised to sum 1."""
+    texts = [r if isinstance(r, str) else r.decode("ascii") if isinstance(r, (bytes, bytearray)) else r.str_struct for r in rows]
+    if not texts:
+        raise ValueError("no rows")
+    L = len(texts[0])
+    w = np.ones(len(texts)) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != (len(texts),) or (w < 0).any() or not w.sum() > 0:
+        raise ValueError("weights: one non-negative number per row, not all zero")
+    counts = {}
+    for t, x in zip(texts, w):
+        if len(t) != L:
+            raise ValueError("rows of different lengths")
+        stack = []
+        for j, ch in enumerate(t):
+            if ch == "(":
+                stack.append(j)
+            elif ch == ")":
+                if not stack:
+                    raise ValueError(f"unbalanced row {t!r}")
+                key = (stack.pop(), j)
+                counts[key] = counts.get(key, 0.0) + x
+            elif ch != ".":
+                raise ValueError(f"row {t!r} holds {ch!r}")
+        if stack:
+            raise ValueError(f"unbalanced row {t!r}")
+    F = np.zeros((L, L), dtype=np.float64)
+    total = float(w.sum())
+    for (i, j), x in counts.items():
+        F[i, j] = min(1.0, x / total)
+    return F
