@@ -349,6 +349,25 @@ int rafft_mfe_batch(int n_seq, const char *const *seqs, const int *lens, double 
 /* the longest sequence whose tables fit the LDS class */
 int rafft_mfe_lds_len(void);
 
+/* Minimum-free-energy structures under a maximum base-pair span, for sequences of up to RAFFT_MFE_SPAN_MAX_LEN nt (DESIGN.md
+ * section 18; what `RNAfold --maxBPspan` is used for).  A pair (i, j), i < j, is allowed iff j - i + 1 <= max_span; everything
+ * else is rafft_mfe_batch's ensemble and energy, and the exterior loop is not restricted.  dcal is the minimum of
+ * rafft_eval_structure over that ensemble and rafft_eval_structure of the returned row gives dcal again.  The candidate order of
+ * the traceback is rafft_mfe_batch's, the exterior stems that end at j being visited with i ascending from
+ * max(0, j - max_span + 1): a sequence with lens[s] <= max_span gets the row, dcal and n_pairs of rafft_mfe_batch byte for byte.
+ * max_span of 1 to 4 gives the open chain.  The result is a function of the sequence, the energy tables, temp and max_span alone.
+ * The work is O(L W^2), W = min(max_span, L), in W launches of up to L cells; a sequence has 4 x L x W int32 tables in device
+ * memory (75 MiB at 32768 nt and span 150) and sequences are processed in chunks that fit workspace_bytes (0: 512 MiB; one
+ * sequence at least).
+ * Outputs and the errors of a sequence (RAFFT_ERR_TOO_LONG: above RAFFT_MFE_SPAN_MAX_LEN) as rafft_mfe_batch.  RAFFT_ERR_PARAM,
+ * before anything is launched: a null argument, a negative count or workspace, max_span outside 1 .. RAFFT_MFE_MAX_LEN.
+ * RAFFT_ERR_TEMP as for the fold. */
+#define RAFFT_MFE_SPAN_MAX_LEN RAFFT_MAX_LEN
+int rafft_mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                         int max_span,               /* 1 .. RAFFT_MFE_MAX_LEN */
+                         long long workspace_bytes,  /* 0: 512 MiB; one sequence at least */
+                         rafft_mfe_seq *seq_out, char *const *db_out /* db_out[s]: lens[s] + 1 bytes, NUL terminated */);
+
 /* Partition function, base-pair probabilities and centroid structures of a batch (McCaskill).  Replaces:
  * RNA.fold_compound(seq, md).pf() / bpp(), the calls beside the RNA.fold of benchmark_results/src/vrna_mfe.py:25.
  * The ensemble is the one rafft_mfe_batch minimises over: canonical pairs, hairpins of at least 3, interior loops of at most 30

@@ -8,7 +8,7 @@ fallback - importing works anywhere, calling needs the built library and a GPU."
 from .rafft import fold, fold_batch, submit_batch, eval_structures, eval_structures_info, last_stats  # noqa: F401
 from .params import load_params, load_params_from_viennarna, reset_params, save_params, params_info, unpinned_entries  # noqa: F401
 from .rafft_kin import kinetics, kinetics_batch  # noqa: F401
-from .zuker import mfe, mfe_batch  # noqa: F401
+from .zuker import mfe, mfe_batch, mfe_span, mfe_span_batch, mfe_span_batch_raw  # noqa: F401
 from .mccaskill import pf, pf_batch, sample, sample_batch  # noqa: F401
 from .mccaskill import MeaResult, mea, mea_batch, mea_from_probs, pair_frequencies  # noqa: F401
 from .wuchty import subopt, subopt_batch, subopt_batch_raw  # noqa: F401

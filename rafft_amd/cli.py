@@ -54,6 +54,8 @@ _OPTIONS = [
                                                 "dangles=2, lonely pairs allowed, interior loops up to 30 - RNA.fold's defaults), one line per sequence as\n"
                                                 "benchmark_results/src/vrna_mfe.py prints it: seq len structure energy #pairs.  With --scores the table of\n"
                                                 "mfe_scores.csv.  Works with -s SEQ and with -sf FILE --batch")),
+    (("--span",), dict(type=int, default=None, metavar="W", help="with --mfe: only pairs (i, j) with j - i + 1 <= W, 1 <= W <= 4096 (rafft_amd.mfe_span_batch; as\n"
+                                                                 "`RNAfold --maxBPspan W`), for sequences of up to 32768 nt.  Output and --scores as --mfe")),
     (("--pf",), dict(action="store_true", help="no RAFFT fold: the partition function of every sequence on the GPU (rafft_amd.pf_batch; the ensemble of --mfe),\n"
                                                "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
                                                "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
@@ -253,6 +255,9 @@ def main_mfe(args, seqs, known, names, mfe_batch=None, scorer=None):
     in for scoring.score_rows_gpu."""
     if args.kin or args.traj:
         raise SystemExit("--mfe gives one structure per sequence: no --kin, no --traj")
+    if mfe_batch is None and args.span is not None:
+        from .zuker import mfe_span_batch
+        mfe_batch = lambda sequences, temp: mfe_span_batch(sequences, args.span, temp)
     if mfe_batch is None:
         from .zuker import mfe_batch
     structs = mfe_batch(seqs, args.temp)
@@ -631,6 +636,10 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     max_structs, temp) that stands in for wuchty.subopt_batch; `mea_batch`: the callable (sequences, gamma, temp) that stands in for
     mccaskill.mea_batch)."""
     args = parse_arguments(argv)
+    if args.span is not None and not args.mfe:
+        raise SystemExit("--span W restricts the pairs of --mfe: it needs --mfe")
+    if args.span is not None and not 1 <= args.span <= 4096:
+        raise SystemExit("--span is 1 to 4096")
     if args.findpath:
         if args.descend:
             raise SystemExit("--findpath and --descend are two modes")

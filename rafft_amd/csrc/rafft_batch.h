@@ -1,5 +1,5 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
-// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), pf_batch (partition
+// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), mfe_span_batch (the same under a base-pair span, to 32768 nt), pf_batch (partition
 // function and pair probabilities), mea_batch and mea_probs_batch (maximum-expected-accuracy structures), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
 // energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima), barriers_batch (exact barrier trees of energy bands) and kinfold_batch (stochastic folding trajectories), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
@@ -295,6 +295,71 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
     DevScratch mem;
     if (int rc = sc.open(mem, pk, temp)) return rc;
     if (int rc = mfe_held(sc.st, pk, sc.d_codes, lds_len, workspace_bytes, seq_out, db_out)) return rc;
+    g_err = pk.first_err;
+    return 0;
+}
+
+// ---- minimum-free-energy folds under a base-pair span
+
+// rafft_mfe_span_batch (arguments validated by the entry point).  Chunks of whole sequences in input order whose banded tables fit
+// the workspace budget (one sequence at least; mfe_span_layout): per chunk one launch per anti-diagonal of its widest band, then
+// the exterior loop and the traceback, a wavefront a sequence each.  One synchronise at the end.
+int mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int max_span, long long workspace_bytes, rafft_mfe_seq *seq_out,
+                   char *const *db_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_SPAN_MAX_LEN, "RAFFT_MFE_SPAN_MAX_LEN");
+    for (int s = 0; s < n_seq; s++) {
+        seq_out[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+        dot_row(db_out[s], pk.len[s]);
+    }
+    g_err = pk.first_err;
+    if (pk.fold.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    const MfeSpanLayout y = mfe_span_layout(pk, max_span, workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE);
+    const std::vector<MfeSpanSeq> &qs = y.qs;
+    MfeSpanSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_f, *d_ws;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSpanSeq))) return rc;
+    if (int rc = mem.alloc(d_f, y.n_f * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_stack, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_db, y.n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
+    if (int rc = mem.alloc(d_order, pk.fold.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSpanSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, pk.fold.data(), pk.fold.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
+    HIPCHK(hipFuncSetAttribute((const void *)mfe_span_exterior_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mfe_span_lds_bytes(RAFFT_MFE_SPAN_MAX_LEN)));
+    HIPCHK(hipFuncSetAttribute((const void *)mfe_span_traceback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mfe_span_lds_bytes(RAFFT_MFE_SPAN_MAX_LEN)));
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        const ChunkView v = chunk_view(c, d_order, pk.fold, pk);
+        const int Wmax = mfe_span_chunk_wmax(c, pk.fold, qs);
+        for (int d = 0; d < Wmax; d++) {
+            const unsigned nx = (unsigned)std::min((v.Lmax - d + MFE_SPAN_NT / 64 - 1) / (MFE_SPAN_NT / 64), 2048);
+            hipLaunchKernelGGL(mfe_span_diag_kernel, dim3(nx, v.ny), dim3(MFE_SPAN_NT), 0, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d);
+        }
+        HIPCHK(hipGetLastError());
+        const size_t lds = (size_t)mfe_span_lds_bytes(v.Lmax);
+        hipLaunchKernelGGL(mfe_span_exterior_kernel, dim3(v.ny), dim3(64), lds, st, d_qs, v.ord, d_ws, d_f);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mfe_span_traceback_kernel, dim3(v.ny), dim3(64), lds, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d_f, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<int4> rec(n_seq);
+    std::vector<char> db(y.n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
+        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
+        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
     g_err = pk.first_err;
     return 0;
 }

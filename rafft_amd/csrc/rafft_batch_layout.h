@@ -1,5 +1,5 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_pf.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
+// of rafft_mfe.hip, rafft_mfe_span.hip, rafft_pf.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
 // compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree, the buffers of a folding trajectory).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
@@ -24,6 +24,26 @@ struct MfeSeq {
     unsigned long long stack_off;   // first word of its traceback stack (L + 8 words)
     unsigned long long db_off;      // its row in the output (L + 1 bytes)
     int L, pad;
+};
+
+// ---- minimum-free-energy folds under a base-pair span (rafft_mfe_span.hip)
+
+// What a sequence of L positions folded with pairs of at most max_span positions has on the device.  W = min(max_span, L) cells
+// d = j - i a row.  Four tables of L x W int32 back to back from tab_off: C and M as [i][d], M1 and X (C + exterior stem) by
+// their 3' end as [j][d].  F: L + 1 ints.  A traceback stack of L + 8 words (i | d << 15 | table << 30), a row of L + 1 bytes.
+#define MFE_SPAN_TABLES 4
+RAFFT_HD constexpr int mfe_span_width(int L, int max_span) { return max_span < L ? max_span : L; }
+RAFFT_HD constexpr unsigned long long mfe_span_table_ints(int L, int W) { return (unsigned long long)L * (unsigned long long)W; }
+// dynamic LDS of the exterior and the traceback kernel for the longest sequence of a chunk: F, then the pair table over it
+RAFFT_HD constexpr int mfe_span_lds_bytes(int L) { return (L + 1) * 4; }
+
+struct MfeSpanSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long tab_off;     // first int of its four L x W tables in the workspace
+    unsigned long long f_off;       // first int of its exterior energies (L + 1)
+    unsigned long long stack_off;   // first word of its traceback stack (L + 8 words)
+    unsigned long long db_off;      // its row in the output (L + 1 bytes)
+    int L, W;
 };
 
 // ---- partition function and pair probabilities (rafft_pf.hip)

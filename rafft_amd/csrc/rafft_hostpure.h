@@ -211,14 +211,14 @@ static ChunkPlan plan_chunks(size_t n, const size_t *cost, const size_t *cost2, 
 
 // The sequences of rafft_mfe_batch / rafft_pf_batch.  Per sequence: status (empty before too long before bad character), the
 // length as reported (max(len, 0)), the folded length (0 for an error) and where its bases lie in `codes` (kBaseCode & 7, back to
-// back, 16 zero bytes behind the last); `fold`: the sequences without an error, in input order; first_err: the first error's text.
+// back, 16 zero bytes behind the last); `fold`: the sequences without an error, in input order; first_err: the first error's text (`limit`: the name it gives max_len).
 struct SeqPack {
     std::vector<int> status, len, L, fold;
     std::vector<unsigned long long> code_off;
     std::vector<uint8_t> codes;
     std::string first_err;
 };
-static SeqPack pack_sequences(int n_seq, const char *const *seqs, const int *lens, int max_len)
+static SeqPack pack_sequences(int n_seq, const char *const *seqs, const int *lens, int max_len, const char *limit = "RAFFT_MFE_MAX_LEN")
 {
     SeqPack p;
     p.status.resize(n_seq); p.len.resize(n_seq); p.L.resize(n_seq); p.code_off.resize(n_seq);
@@ -234,7 +234,7 @@ static SeqPack pack_sequences(int n_seq, const char *const *seqs, const int *len
         p.code_off[s] = n_codes;
         if (st) {
             if (p.first_err.empty())
-                p.first_err = "sequence " + std::to_string(s) + (st == RAFFT_ERR_EMPTY ? ": empty" : st == RAFFT_ERR_TOO_LONG ? ": longer than RAFFT_MFE_MAX_LEN" : ": character outside ACGUN");
+                p.first_err = "sequence " + std::to_string(s) + (st == RAFFT_ERR_EMPTY ? ": empty" : st == RAFFT_ERR_TOO_LONG ? std::string(": longer than ") + limit : ": character outside ACGUN");
             continue;
         }
         n_codes += (unsigned long long)p.L[s];
@@ -286,6 +286,40 @@ static MfeLayout mfe_layout(const SeqPack &pk, int lds_len, size_t budget)
     y.order = y.lds_order;
     y.order.insert(y.order.end(), y.hbm_order.begin(), y.hbm_order.end());
     return y;
+}
+
+// rafft_mfe_span_batch: every sequence has W = min(max_span, L) cells a row and MFE_SPAN_TABLES tables of L x W int32; chunks
+// (plan: over pk.fold) of whole sequences in input order.  n_f ints of exterior energies, n_stack words of traceback stacks, n_db
+// bytes of rows over the whole call.
+struct MfeSpanLayout {
+    std::vector<MfeSpanSeq> qs;
+    ChunkPlan plan;
+    unsigned long long n_f = 0, n_stack = 0, n_db = 0;
+};
+static MfeSpanLayout mfe_span_layout(const SeqPack &pk, int max_span, size_t budget)
+{
+    MfeSpanLayout y;
+    const int n_seq = (int)pk.L.size();
+    y.qs.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) {
+        const int L = pk.L[s];
+        y.qs[s] = MfeSpanSeq{pk.code_off[s], 0, y.n_f, y.n_stack, y.n_db, L, mfe_span_width(L, max_span)};
+        if (!L) continue;
+        y.n_f += (unsigned long long)L + 1; y.n_stack += (unsigned long long)L + 8; y.n_db += (unsigned long long)L + 1;
+    }
+    const std::vector<int> &order = pk.fold;
+    std::vector<size_t> tab_bytes(order.size());
+    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)(MFE_SPAN_TABLES * mfe_span_table_ints(y.qs[order[k]].L, y.qs[order[k]].W) * 4);
+    y.plan = plan_chunks(order.size(), tab_bytes.data(), nullptr, budget, 65535);
+    for (size_t k = 0; k < order.size(); k++) y.qs[order[k]].tab_off = y.plan.off[k] / 4;
+    return y;
+}
+// the widest band of the sequences order[a .. b) of a chunk: the anti-diagonals its fill launches
+static int mfe_span_chunk_wmax(const ChunkPlan::Range &c, const std::vector<int> &order, const std::vector<MfeSpanSeq> &qs)
+{
+    int Wmax = 0;
+    for (size_t k = c.a; k < c.b; k++) Wmax = std::max(Wmax, qs[order[k]].W);
+    return Wmax;
 }
 
 // rafft_pf_batch / rafft_sample_batch: chunks (plan: over pk.fold) of n_tabs L x L fp64 tables a sequence and, with cost2, a second

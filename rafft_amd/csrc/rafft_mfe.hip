@@ -139,44 +139,64 @@ __device__ inline void mfe_cell(const Tab &tb, const SmallT *T, const BigT *B, c
     if (lane == 0) { tb.c(i, j) = c; tb.m1(i, j) = m1; tb.m(i, j) = m; }
 }
 
-// One wavefront: the exterior loop, then the traceback with an explicit stack of (i, j, table) words.  F: L + 1 ints of LDS (F[j + 1]
-// = exterior energy of 0..j; the pair table once the exterior loop is traced).  `stack`: `cap` words only lane 0 touches.
-// rec = (dcal, pairs, 1 when no candidate reproduced a cell - an internal error, 0)
+// What the exterior loop and the traceback need to know of a layout besides its table view: how a stack word packs (i, j, table),
+// where the exterior stems that end at j begin (i ascending from there), and the exterior candidate C[i][j] + stem (MFE_INF: none).
 enum { MFE_K_C = 0, MFE_K_M = 1, MFE_K_M1 = 2 };
-template <class Tab>
-__device__ inline void mfe_traceback(const Tab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, int *F, uint32_t *stack, int cap,
-                                     char *db, int4 *rec, int lane)
+struct MfeWalkFull {
+    __device__ __forceinline__ uint32_t pack(int i, int j, int kind) const { return (uint32_t)i | (uint32_t)j << 12 | (uint32_t)kind << 24; }
+    __device__ __forceinline__ void unpack(uint32_t w, int &i, int &j, int &kind) const { i = (int)(w & 4095u); j = (int)((w >> 12) & 4095u); kind = (int)(w >> 24); }
+    __device__ __forceinline__ int lo(int) const { return 0; }
+    template <class Tab>
+    __device__ __forceinline__ int ext(const Tab &tb, const SmallT *T, const uint8_t *S, int L, int i, int j) const
+    {
+        const int c = tb.c(i, j);
+        return c < MFE_INFH ? c + mfe_stem_ext(T, S, L, i, j) : MFE_INF;
+    }
+};
+
+// One wavefront: the exterior loop.  F: L + 1 ints of LDS, F[j + 1] = exterior energy of 0..j
+template <class Tab, class Walk>
+__device__ inline void mfe_exterior(const Tab &tb, const Walk &wk, const SmallT *T, const uint8_t *S, int L, int *F, int lane)
 {
     if (lane == 0) F[0] = 0;
     wave_sync();
     for (int j = 0; j < L; j++) {
         int best = MFE_INF;
-        for (int i = lane; i <= j - 4; i += 64) {
-            const int c = tb.c(i, j);
-            if (c < MFE_INFH) best = min(best, F[i] + c + mfe_stem_ext(T, S, L, i, j));
+        for (int i = wk.lo(j) + lane; i <= j - 4; i += 64) {
+            const int e = wk.ext(tb, T, S, L, i, j);
+            if (e < MFE_INFH) best = min(best, F[i] + e);
         }
         best = mfe_wave_min(best);
         const int prev = F[j];
         if (lane == 0) F[j + 1] = min(prev, best);
         wave_sync();
     }
+}
+
+// One wavefront: the traceback from the F of mfe_exterior, with an explicit stack of (i, j, table) words; F holds the pair table
+// once the exterior loop is traced.  `stack`: `cap` words only lane 0 touches.
+// rec = (dcal, pairs, 1 when no candidate reproduced a cell - an internal error, 0)
+template <class Tab, class Walk>
+__device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT *T, const BigT *B, const uint8_t *S, int L, int *F, uint32_t *stack, int cap,
+                                     char *db, int4 *rec, int lane)
+{
     const int mfe = F[L];
     int sp = 0, npairs = 0, bad = 0;
     auto push = [&](int i, int j, int kind) {
         if (sp >= cap) { bad = 1; return; }
-        if (lane == 0) stack[sp] = (uint32_t)i | (uint32_t)j << 12 | (uint32_t)kind << 24;
+        if (lane == 0) stack[sp] = wk.pack(i, j, kind);
         sp++;
     };
     for (int j = L - 1; j >= 4 && !bad;) {
         const int v = F[j + 1];
         if (v == F[j]) { j--; continue; }
         int found = -1;
-        for (int i0 = 0; i0 <= j - 4 && found < 0; i0 += 64) {
+        for (int i0 = wk.lo(j); i0 <= j - 4 && found < 0; i0 += 64) {
             const int i = i0 + lane;
             bool hit = false;
             if (i <= j - 4) {
-                const int c = tb.c(i, j);
-                hit = c < MFE_INFH && F[i] + c + mfe_stem_ext(T, S, L, i, j) == v;
+                const int e = wk.ext(tb, T, S, L, i, j);
+                hit = e < MFE_INFH && F[i] + e == v;
             }
             const unsigned long long bal = __ballot(hit);
             if (bal) found = i0 + __ffsll((long long)bal) - 1;
@@ -195,7 +215,8 @@ __device__ inline void mfe_traceback(const Tab &tb, const SmallT *T, const BigT 
         uint32_t w = 0;
         if (lane == 0) w = stack[sp];
         w = (uint32_t)__shfl((int)w, 0, 64);
-        int i = (int)(w & 4095u), j = (int)((w >> 12) & 4095u), kind = (int)(w >> 24);
+        int i, j, kind;
+        wk.unpack(w, i, j, kind);
         if (kind == MFE_K_M) {
             for (;;) {
                 const int v = tb.m(i, j);
@@ -291,7 +312,10 @@ __global__ __launch_bounds__(MFE_LDS_NT) void mfe_lds_kernel(const EnergyTables 
         for (int i = wave; i + d < L; i += MFE_LDS_NT / 64) mfe_cell(tb, T, B, S, L, i, i + d, lane);
         __syncthreads();
     }
-    if (wave == 0) mfe_traceback(tb, T, B, S, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, lane);
+    if (wave == 0) {
+        mfe_exterior(tb, MfeWalkFull(), T, S, L, F, lane);
+        mfe_traceback(tb, MfeWalkFull(), T, B, S, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, lane);
+    }
 }
 
 // HBM class: anti-diagonal d of the sequences order[0 .. gridDim.y), four cells per workgroup and round
@@ -317,5 +341,6 @@ __global__ __launch_bounds__(64) void mfe_traceback_kernel(const EnergyTables *E
     int *t0 = tabs + q.tab_off;
     const size_t LL = (size_t)L * L;
     const MfeTabHbm tb{t0, t0 + LL, t0 + 2 * LL, L};
-    mfe_traceback(tb, &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, (int)threadIdx.x);
+    mfe_exterior(tb, MfeWalkFull(), &ET->s, codes + q.code_off, L, F, (int)threadIdx.x);
+    mfe_traceback(tb, MfeWalkFull(), &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, (int)threadIdx.x);
 }

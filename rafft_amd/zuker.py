@@ -38,3 +38,34 @@ def mfe_batch(sequences, temp=37.0, raise_errors=True):
 
 def mfe(sequence, temp=37.0):
     return mfe_batch([sequence], temp)[0]
+
+
+def mfe_span_batch_raw(sequences, max_span, temp=37.0, workspace_bytes=0):
+    """(rows, dcal, n_pairs, status) of rafft_mfe_span_batch: the MFE structures whose pairs (i, j) all
+    have j - i + 1 <= max_span, of sequences of up to N.MFE_SPAN_MAX_LEN nt.  As mfe_batch_raw otherwise."""
+    L = N.lib()
+    _params_mod.ensure_default_params()
+    n = len(sequences)
+    _, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
+    rec = (N.MfeSeq * n)()
+    N.check(L.rafft_mfe_span_batch(n, arr, lens, float(temp), int(max_span), int(workspace_bytes), rec, out))
+    return ([b.value.decode("ascii") for b in bufs], [r.dcal for r in rec], [r.n_pairs for r in rec], [r.status for r in rec])
+
+
+def mfe_span_batch(sequences, max_span, temp=37.0, raise_errors=True):
+    """The MFE structure under a maximum base-pair span of every sequence, as a list of utils.Structure; errors as mfe_batch."""
+    rows, dcal, _, status = mfe_span_batch_raw(sequences, max_span, temp)
+    en = energies_from_dcal(np.asarray(dcal, dtype=np.int32)).tolist() if rows else []
+    out = []
+    for k, s in enumerate(sequences):
+        if status[k] != N.OK:
+            if raise_errors:
+                raise_for_status(status[k], s, k, "mfe_span_batch", "RAFFT_MFE_SPAN_MAX_LEN")
+            out.append(None)
+        else:
+            out.append(Structure(rows[k], dcal[k], en[k]))
+    return out
+
+
+def mfe_span(sequence, max_span, temp=37.0):
+    return mfe_span_batch([sequence], max_span, temp)[0]
