@@ -450,6 +450,28 @@ int rafft_findpath_counters(long long out[4])
     return 0;
 }
 
+// What the three row calls ask of sequence s before anything runs, as text behind "sequence s", nullptr when nothing is wrong:
+// check_seq_args - its row count and its bases; check_row_block - one block of n rows `stride` bytes apart (`own`: the call's other
+// per-sequence pointers that go with the block are there).
+static const char *check_seq_args(const char *const *seqs, const int *lens, const int *n_rows, int s)
+{
+    if (n_rows[s] < 0) return ": negative row count";
+    if (lens[s] > 0 && !seqs[s]) return ": null pointer";
+    return nullptr;
+}
+static const char *check_row_block(int len, int n, const char *block, int stride, bool own)
+{
+    if (n <= 0) return nullptr;
+    if (!block || !own) return ": null pointer";
+    if (stride < (len > 0 ? len : 0)) return ": stride below the length";
+    return nullptr;
+}
+static const char *check_row_args(const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride, int s, bool own)
+{
+    const char *what = check_seq_args(seqs, lens, n_rows, s);
+    return what ? what : check_row_block(lens[s], n_rows[s], rows[s], row_stride[s], own);
+}
+
 int rafft_descend_batch(int n_seq, const char *const *seqs, const int *lens, const int *n_rows, const char *const *rows, const int *row_stride,
                         double temp, int max_steps, long long workspace_bytes, rafft_descend_seq *seq_out, rafft_descend_row *row_out,
                         char *const *db_out, int *const *moves_out)
@@ -459,13 +481,7 @@ int rafft_descend_batch(int n_seq, const char *const *seqs, const int *lens, con
     if (n_seq > 0 && (!seqs || !lens || !n_rows || !rows || !row_stride || !seq_out || !db_out)) return fail(RAFFT_ERR_PARAM, "null argument");
     long long total = 0;
     for (int s = 0; s < n_seq; s++) {
-        const std::string who = "sequence " + std::to_string(s);
-        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative row count");
-        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
-        if (n_rows[s] > 0) {
-            if (!rows[s] || !db_out[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
-            if (row_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
-        }
+        if (const char *what = check_row_args(seqs, lens, n_rows, rows, row_stride, s, db_out[s] != nullptr)) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + what);
         total += n_rows[s];
     }
     if (total > 0x7fffffffll) return fail(RAFFT_ERR_PARAM, "more than 2^31 - 1 rows");
@@ -489,15 +505,8 @@ int rafft_barriers_batch(int n_seq, const char *const *seqs, const int *lens, co
     *out = nullptr;
     if (n_seq < 0 || max_edges < 0 || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
     if (n_seq > 0 && (!seqs || !lens || !n_rows || !rows || !row_stride || !dcal)) return fail(RAFFT_ERR_PARAM, "null argument");
-    for (int s = 0; s < n_seq; s++) {
-        const std::string who = "sequence " + std::to_string(s);
-        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative row count");
-        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
-        if (n_rows[s] > 0) {
-            if (!rows[s] || !dcal[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
-            if (row_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
-        }
-    }
+    for (int s = 0; s < n_seq; s++)
+        if (const char *what = check_row_args(seqs, lens, n_rows, rows, row_stride, s, dcal[s] != nullptr)) return fail(RAFFT_ERR_PARAM, "sequence " + std::to_string(s) + what);
     return barriers_batch(n_seq, seqs, lens, n_rows, rows, row_stride, dcal, max_edges, workspace_bytes, out);
 }
 
@@ -529,21 +538,15 @@ int rafft_kinfold_batch(int n_seq, const char *const *seqs, const int *lens, con
     if (n_seq > 0 && (moves_out == nullptr) != (times_out == nullptr)) return fail(RAFFT_ERR_PARAM, "moves_out and times_out go together");
     long long total = 0;
     for (int s = 0; s < n_seq; s++) {
+        // (the watched rows are asked about between the sequence and its start rows: the order of the texts is kept)
         const std::string who = "sequence " + std::to_string(s);
-        if (n_rows[s] < 0) return fail(RAFFT_ERR_PARAM, who + ": negative row count");
-        if (lens[s] > 0 && !seqs[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
+        if (const char *what = check_seq_args(seqs, lens, n_rows, s)) return fail(RAFFT_ERR_PARAM, who + what);
         if (n_watch) {
             if (const char *what = kinfold_check_watch(n_watch[s], n_stop[s])) return fail(RAFFT_ERR_PARAM, who + ": " + what);
-            if (n_watch[s] > 0) {
-                if (!watch[s]) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
-                if (watch_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
-            }
+            if (const char *what = check_row_block(lens[s], n_watch[s], watch[s], watch_stride[s], true)) return fail(RAFFT_ERR_PARAM, who + what);
         }
-        if (n_rows[s] > 0) {
-            if (!rows[s] || !db_out[s] || (n_times > 0 && !samples_out[s])) return fail(RAFFT_ERR_PARAM, who + ": null pointer");
-            if (row_stride[s] < (lens[s] > 0 ? lens[s] : 0)) return fail(RAFFT_ERR_PARAM, who + ": stride below the length");
-            if (moves_out && (moves_out[s] == nullptr) != (times_out[s] == nullptr)) return fail(RAFFT_ERR_PARAM, who + ": moves_out and times_out go together");
-        }
+        if (const char *what = check_row_block(lens[s], n_rows[s], rows[s], row_stride[s], db_out[s] && !(n_times > 0 && !samples_out[s]))) return fail(RAFFT_ERR_PARAM, who + what);
+        if (n_rows[s] > 0 && moves_out && (moves_out[s] == nullptr) != (times_out[s] == nullptr)) return fail(RAFFT_ERR_PARAM, who + ": moves_out and times_out go together");
         total += (long long)n_rows[s] * n_rep;
         if (total > 0x7fffffffll) return fail(RAFFT_ERR_PARAM, "more than 2^31 - 1 trajectories");
     }

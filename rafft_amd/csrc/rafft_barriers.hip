@@ -12,10 +12,7 @@
 //   barriers_basin_kernel   one thread per row: the end of the chain of down
 //   barriers_scan_kernel<BAR_EDGES>  the same enumeration: a neighbour of lower rank in another basin is an edge; the smallest
 //                           rank per pair of basins is kept by an unsigned minimum, which is order-free - same bits every run
-// The enumeration of a row's neighbours is descend_kernel's, less what an energy needs: lane l takes positions l, l + 64, ...; the
-// 5' end of a pair is that pair's removal; an unpaired position walks right over unpaired positions and whole helices up to the 3'
-// end of the pair that encloses it, which visits exactly the positions of its own loop.  It is written once (barriers_neighbours).
-// Every probe loop is bounded by its table's slot count: a full or corrupt table ends as a flag in BarRec, never as a spin.
+// The neighbours of a row are rafft_moves.h's, less what an energy needs (barriers_neighbours, on next_partner).  Every probe loop is bounded by its table's slot count: a full or corrupt table ends as a flag in BarRec, never as a spin.
 #pragma once
 
 #include "rafft_batch_layout.h"     // BarSeq, BarRec, the barriers_* sizes
@@ -80,22 +77,14 @@ __device__ __forceinline__ unsigned barriers_neighbours(const BarSeq &q, const u
             if (r != BAR_NO_RANK) { hits++; visit(r); }
             continue;
         }
-        // x is unpaired: the positions of its loop to the right, up to the 3' end of the enclosing pair
-        int p = x + 1;
+        // x is unpaired: its partners to the right (end = L: the walk ends at the 3' end of the enclosing pair by itself)
 #pragma unroll 1
-        while (p < L) {
-            const int z = pt[p];
-            if (z >= 0) {
-                if (z < p) break;
-                p = z + 1;
-                continue;
-            }
-            if (p - x > 3 && pair_type(S[x], S[p])) {
-                pair_hash(x, p, &h1, &h2);
-                const unsigned r = barriers_find(q, tab, keys, k1 + h1, k2 + h2, false, flags);
-                if (r != BAR_NO_RANK) { hits++; visit(r); }
-            }
-            p++;
+        for (int p = x;;) {
+            p = next_partner(pt, S, x, p, L);
+            if (p >= L) break;
+            pair_hash(x, p, &h1, &h2);
+            const unsigned r = barriers_find(q, tab, keys, k1 + h1, k2 + h2, false, flags);
+            if (r != BAR_NO_RANK) { hits++; visit(r); }
         }
     }
     return hits;

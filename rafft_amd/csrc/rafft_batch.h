@@ -1022,6 +1022,15 @@ int findpath_batch(int n_paths, const char *const *seqs, const int *lens, const 
     return 0;
 }
 
+// ---- the row drivers: descend, barriers, kinfold.  Their row intake (row_ptr, ROW_PARSE_ERR, copy_row_back, FirstError) is host-pure.
+
+// The pair table of row r of sequence s again, when its chunk is staged: the first pass over the rows keeps none.
+static int restage_row(const SeqPack &pk, const char *const *rows, const int *row_stride, int s, int r, int L, std::vector<int16_t> &pt)
+{
+    if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, row_ptr(rows, row_stride, s, r), pt)) return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+    return 0;
+}
+
 // ---- gradient walks to local minima
 
 constexpr size_t DESCEND_WORKSPACE = (size_t)512 << 20;
@@ -1041,14 +1050,7 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
     for (long long &c : g_descend_counters) c = 0;
     if (n_seq == 0) return 0;
     const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_DESCEND_MAX_LEN);
-    // the call's error text names the first erroneous item in input order: (sequence, row), row -1 for the sequence itself
-    std::string err = pk.first_err;
-    long long err_at = -1;
-    for (int s = 0; s < n_seq && err_at < 0; s++) if (pk.status[s]) err_at = ((long long)s << 32);
-    auto note = [&](int s, int r, const std::string &msg) {
-        const long long at = ((long long)s << 32) + r + 1;
-        if (err_at < 0 || at < err_at) { err_at = at; err = msg; }
-    };
+    FirstError err(pk);                 // (items: rows)
     struct Where { int s, r; };
     std::vector<Where> run;
     std::vector<int> wL, wbound;
@@ -1064,13 +1066,11 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
             char *db = db_out[s] + (size_t)r * ((size_t)len + 1);
             o = rafft_descend_row{pk.status[s], 0, 0, 0};
             if (pk.status[s]) { dot_row(db, len); continue; }
-            const char *row = rows[s] + (size_t)r * (size_t)row_stride[s];
+            const char *row = row_ptr(rows, row_stride, s, r);
             if (int st = descend_parse_row(pk.codes.data() + pk.code_off[s], L, row, pt)) {
                 o.status = st;
-                const size_t n = strnlen(row, (size_t)L);        // (the row comes back as it went in)
-                memcpy(db, row, n);
-                db[n] = 0;
-                note(s, r, "sequence " + std::to_string(s) + " row " + std::to_string(r) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3");
+                copy_row_back(db, row, L);
+                err.note(s, r, "sequence " + std::to_string(s) + " row " + std::to_string(r) + ROW_PARSE_ERR);
                 continue;
             }
             run.push_back(Where{s, r});
@@ -1079,7 +1079,7 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
         }
         row0 += n_rows[s];
     }
-    g_err = err;
+    g_err = err.text();
     if (run.empty()) return 0;
     SeqCall sc;
     DevScratch mem;
@@ -1101,9 +1101,7 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
         const ChunkPlan::Range &c = y.plan.chunks[ci];
         const size_t nw = c.b - c.a;
         for (size_t k = c.a; k < c.b; k++) {
-            const int s = run[k].s;
-            if (descend_parse_row(pk.codes.data() + pk.code_off[s], wL[k], rows[s] + (size_t)run[k].r * (size_t)row_stride[s], pt))
-                return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+            if (int rc = restage_row(pk, rows, row_stride, run[k].s, run[k].r, wL[k], pt)) return rc;
             memcpy(io.data() + y.ws[k].io_off, pt.data(), (size_t)wL[k] * 2);
         }
         HIPCHK(hipMemcpyAsync(d_io, io.data(), y.chunk_io[ci], hipMemcpyHostToDevice, st));
@@ -1123,14 +1121,14 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
             if (d.n_steps < 0 || d.n_steps > wbound[k]) return fail(RAFFT_ERR_HIP, "internal: " + who + ": more steps than the bound");
             rafft_descend_row &o = row_out[seq_out[s].row0 + r];
             o = rafft_descend_row{(d.flags & DS_MORE) ? RAFFT_ERR_CAPACITY : 0, d.n_steps, d.start, d.end};
-            if (d.flags & DS_MORE) note(s, r, who + ": not at a minimum after " + std::to_string(d.n_steps) + " steps (max_steps)");
+            if (d.flags & DS_MORE) err.note(s, r, who + ": not at a minimum after " + std::to_string(d.n_steps) + " steps (max_steps)");
             memcpy(db_out[s] + (size_t)r * ((size_t)L + 1), io.data() + y.ws[k].io_off, (size_t)L + 1);
             if (wmoves[k] && d.n_steps)
                 memcpy(moves_out[s] + (size_t)r * 2 * (size_t)wbound[k], mv.data() + y.ws[k].mv_off, (size_t)d.n_steps * 8);
             g_descend_counters[3] += d.n_steps;
         }
     }
-    g_err = err;
+    g_err = err.text();
     return 0;
 }
 
@@ -1166,13 +1164,10 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
     own->seq.resize(n_seq); own->minima.resize(n_seq); own->edges.resize(n_seq); own->basin.resize(n_seq);
     const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_BARRIERS_MAX_LEN);
     const size_t budget = std::min(workspace_bytes > 0 ? (size_t)workspace_bytes : BARRIERS_WORKSPACE, BARRIERS_WORKSPACE_MAX);
-    // the call's error text names the first erroneous sequence in input order
-    std::string err = pk.first_err;
-    int err_at = n_seq;
-    for (int s = 0; s < n_seq && err_at == n_seq; s++) if (pk.status[s]) err_at = s;
+    FirstError err(pk);                 // (no items: every error is its sequence's)
     auto note = [&](int s, int status, const std::string &msg) {
         own->seq[s].status = status;
-        if (s < err_at) { err_at = s; err = "sequence " + std::to_string(s) + ": " + msg; }
+        err.note(s, -1, "sequence " + std::to_string(s) + ": " + msg);
     };
     std::vector<int> run, rL, rn;
     std::vector<unsigned long long> rcode;
@@ -1185,10 +1180,10 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
         if (n_rows[s] > RAFFT_BARRIERS_MAX_ROWS) { note(s, RAFFT_ERR_CAPACITY, "more than RAFFT_BARRIERS_MAX_ROWS rows"); continue; }
         int bad = -1, dec = -1;
         for (int r = 0; r < n_rows[s] && bad < 0 && dec < 0; r++) {
-            if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, rows[s] + (size_t)r * (size_t)row_stride[s], pt)) bad = r;
+            if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, row_ptr(rows, row_stride, s, r), pt)) bad = r;
             else if (r > 0 && dcal[s][r] < dcal[s][r - 1]) dec = r;
         }
-        if (bad >= 0) { note(s, RAFFT_ERR_STRUCT, "row " + std::to_string(bad) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3"); continue; }
+        if (bad >= 0) { note(s, RAFFT_ERR_STRUCT, "row " + std::to_string(bad) + ROW_PARSE_ERR); continue; }
         if (dec >= 0) { note(s, RAFFT_ERR_STRUCT, "row " + std::to_string(dec) + ": its dcal is below that of the row before it"); continue; }
         const unsigned long long area = barriers_area_bytes(L, n_rows[s], barriers_edge_cap(n_rows[s], max_edges));
         if (area > (unsigned long long)budget) {
@@ -1212,7 +1207,7 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
         own->res = rafft_barriers_result{n_seq, n_failed, own->seq.data(), own.get()};
         *out = &own->res;
         own.release();
-        g_err = err;
+        g_err = err.text();
         return 0;
     };
     if (run.empty()) return finish();
@@ -1250,8 +1245,7 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
             const int s = run[k];
             const BarSeq &q = y.qs[k];
             for (int r = 0; r < q.n_rows; r++) {
-                if (descend_parse_row(pk.codes.data() + pk.code_off[s], q.L, rows[s] + (size_t)r * (size_t)row_stride[s], pt))
-                    return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+                if (int rc = restage_row(pk, rows, row_stride, s, r, q.L, pt)) return rc;
                 memcpy(hpt.data() + q.pt_off + (size_t)r * (size_t)q.pt_stride, pt.data(), (size_t)q.L * 2);
             }
         }
@@ -1358,14 +1352,7 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
     std::vector<uint64_t> wtab(RAFFT_KINFOLD_NW);
     if (!kinfold_weights(temp, kt, wtab.data())) return fail(RAFFT_ERR_PARAM, "kT is not above 0");
     const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_KINFOLD_MAX_LEN);
-    // the call's error text names the first erroneous item in input order: (sequence, trajectory), -1 for the sequence itself
-    std::string err = pk.first_err;
-    long long err_at = -1;
-    for (int s = 0; s < n_seq && err_at < 0; s++) if (pk.status[s]) err_at = ((long long)s << 32);
-    auto note = [&](int s, long long k, const std::string &msg) {
-        const long long at = ((long long)s << 32) + k + 1;
-        if (err_at < 0 || at < err_at) { err_at = at; err = msg; }
-    };
+    FirstError err(pk);                 // (items: trajectories)
     const int bound = kinfold_bound(max_steps);
     struct Where { int s, k; };
     std::vector<Where> run;
@@ -1381,19 +1368,19 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
         int status = pk.status[s];
         const unsigned long long wt_off = watch_pt.size();
         for (int w = 0; w < nw && !status; w++) {
-            if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, watch[s] + (size_t)w * (size_t)watch_stride[s], pt)) {
+            if (descend_parse_row(pk.codes.data() + pk.code_off[s], L, row_ptr(watch, watch_stride, s, w), pt)) {
                 status = RAFFT_ERR_STRUCT;
                 watch_pt.resize(wt_off);
-                note(s, -1, "sequence " + std::to_string(s) + " watched row " + std::to_string(w) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3");
+                err.note(s, -1, "sequence " + std::to_string(s) + " watched row " + std::to_string(w) + ROW_PARSE_ERR);
             } else watch_pt.insert(watch_pt.end(), pt.begin(), pt.end());
         }
         seq_out[s] = rafft_kinfold_seq{status, len, n_traj, traj0};
         for (int r = 0; r < n_rows[s]; r++) {
             int st = status;
-            const char *row = rows[s] + (size_t)r * (size_t)row_stride[s];
+            const char *row = row_ptr(rows, row_stride, s, r);
             if (!st && descend_parse_row(pk.codes.data() + pk.code_off[s], L, row, pt)) {
                 st = RAFFT_ERR_STRUCT;
-                note(s, (long long)r * n_rep, "sequence " + std::to_string(s) + " row " + std::to_string(r) + ": malformed, a non-canonical pair, or a hairpin of fewer than 3");
+                err.note(s, (long long)r * n_rep, "sequence " + std::to_string(s) + " row " + std::to_string(r) + ROW_PARSE_ERR);
             }
             for (int rep = 0; rep < n_rep; rep++) {
                 const int k = r * n_rep + rep;
@@ -1407,18 +1394,14 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
                 }
                 char *db = db_out[s] + (size_t)k * ((size_t)len + 1);
                 if (status) dot_row(db, len);
-                else {
-                    const size_t n = strnlen(row, (size_t)L);       // (the row comes back as it went in)
-                    memcpy(db, row, n);
-                    db[n] = 0;
-                }
+                else copy_row_back(db, row, L);
                 if (n_times && samples_out && samples_out[s])
                     for (int t = 0; t < n_times; t++) { int32_t *o = samples_out[s] + ((size_t)k * n_times + t) * 2; o[0] = INT32_MIN; o[1] = -2; }
             }
         }
         traj0 += n_traj;
     }
-    g_err = err;
+    g_err = err.text();
     if (run.empty()) return 0;
     SeqCall sc;
     DevScratch mem;
@@ -1451,8 +1434,7 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
         for (size_t t = c.a; t < c.b; t++) {
             const int s = run[t].s, r = run[t].k / n_rep;
             if (t == c.a || run[t - 1].s != s || run[t - 1].k / n_rep != r)
-                if (descend_parse_row(pk.codes.data() + pk.code_off[s], wL[t], rows[s] + (size_t)r * (size_t)row_stride[s], pt))
-                    return fail(RAFFT_ERR_PARAM, "a row changed during the call");
+                if (int rc = restage_row(pk, rows, row_stride, s, r, wL[t], pt)) return rc;
             memcpy(io.data() + y.ws[t].io_off, pt.data(), (size_t)wL[t] * 2);
         }
         HIPCHK(hipMemcpyAsync(d_io, io.data(), y.chunk_io[ci], hipMemcpyHostToDevice, st));
@@ -1473,7 +1455,7 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
             if (d.flags & KF_STUCK) return fail(RAFFT_ERR_HIP, "internal: " + who + ": the drawn number met no move");
             if (d.n_steps < 0 || d.n_steps > bound) return fail(RAFFT_ERR_HIP, "internal: " + who + ": more steps than the bound");
             traj_out[seq_out[s].traj0 + k] = rafft_kinfold_traj{(d.flags & KF_MORE) ? RAFFT_ERR_CAPACITY : 0, d.flags, d.n_steps, d.start, d.end, d.stop, d.time};
-            if (d.flags & KF_MORE) note(s, k, who + ": not ended after " + std::to_string(d.n_steps) + " steps (max_steps)");
+            if (d.flags & KF_MORE) err.note(s, k, who + ": not ended after " + std::to_string(d.n_steps) + " steps (max_steps)");
             memcpy(db_out[s] + (size_t)k * ((size_t)L + 1), io.data() + y.ws[t].io_off, (size_t)L + 1);
             if (n_times && samples_out && samples_out[s])
                 memcpy(samples_out[s] + (size_t)k * n_times * 2, smp.data() + (t - c.a) * (size_t)n_times, (size_t)n_times * sizeof(KfSample));
@@ -1484,7 +1466,7 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
             g_kinfold_counters[3] += d.n_steps;
         }
     }
-    g_err = err;
+    g_err = err.text();
     return 0;
 }
 

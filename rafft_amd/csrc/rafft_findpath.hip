@@ -1,7 +1,10 @@
 // rafft_findpath.hip - folding barriers between pairs of structures (gfx950): the direct-path search of ViennaRNA's findpath (Flamm
 // et al. 2001) for a batch of independent problems, defined exactly in DESIGN.md section 13 and include/rafft_hip.h.  Every loop
-// term comes from loop_energy (rafft_device.h) through a view of the pair table with one move applied: the energy model is not
-// stated again.  Included by rafft_kernels.hip, after rafft_io_kernels.hip (PlainView, select_smallest_inplace).
+// term comes from loop_energy (rafft_device.h) through FpView, and the energy of a whole row is rafft_moves.h's structure_energy:
+// the energy model is not stated again.  findpath_expand_kernel keeps ITS OWN COPY of the enclosing-pair walk: on enclosing_pair
+// the compiler shaped that loop differently (same registers) and the calls took 0.8-1.1 % longer on the MI355X
+// (profiles/move_set_refactor_ab.txt); a change to the walk in rafft_moves.h must be made there as well.  Included by
+// rafft_kernels.hip, after rafft_io_kernels.hip (PlainView, select_smallest_inplace) and rafft_moves.h.
 //
 // A STATE of a problem is the set of applied moves (a mask of fp_mask_words(d) 64-bit words) with its energy and its saddle so far;
 // the BEAM of a level holds up to W states in key order.  A LEVEL of a chunk is two launches in stream order (no other
@@ -31,13 +34,6 @@
 #define FP_SEL_NT 512
 #define FP_NO_KEY (~0ull)
 
-// the pair table `pt` with the partners of i and j replaced (i < 0: as it is)
-struct FpView {
-    const int16_t *pt;
-    int i, j, vi, vj;
-    __device__ __forceinline__ int operator()(int x) const { return x == i ? vi : x == j ? vj : (int)pt[x]; }
-};
-
 __device__ __forceinline__ bool fp_in_range(int e) { return e > -FINDPATH_BIAS && e < FINDPATH_BIAS; }
 
 template <int FP_EMIT_LAST>
@@ -49,17 +45,11 @@ __global__ __launch_bounds__(64) void findpath_init_kernel(const EnergyTables *E
     const int L = q.L;
     const uint8_t *S = codes + q.code_off;
     const int16_t *ptA = (const int16_t *)(d_in + q.in_off), *ptB = (const int16_t *)(d_in + q.in_off + fp_in_pt_bytes(L));
-    // one call site of loop_energy for both structures and all their loops (index L: the exterior loop), as eval_kernel sums them
+    // one call site of loop_energy for both structures
     int ea = 0, eb = 0, bad = 0;
 #pragma unroll 1
     for (int which = 0; which < 2; which++) {
-        const FpView v{which ? ptB : ptA, -1, -1, -1, -1};
-        int e = 0;
-#pragma unroll 1
-        for (int i = lane; i <= L; i += 64) {
-            const int j = i < L ? (int)v.pt[i] : L;
-            if (j > i || i == L) e += loop_energy(&ET->s, &ET->b, S, L, v, i < L ? i : -1, j, &bad);
-        }
+        const int e = structure_energy(ET, S, L, which ? ptB : ptA, lane, &bad);
         if (which) eb = e; else ea = e;
     }
     for (int o = 32; o > 0; o >>= 1) { ea += __shfl_xor(ea, o, 64); eb += __shfl_xor(eb, o, 64); bad |= __shfl_xor(bad, o, 64); }

@@ -585,6 +585,39 @@ static int descend_parse_row(const uint8_t *codes, int L, const char *row, std::
     return 0;
 }
 
+// ---- the row intake of the three row drivers (rafft_descend_batch, rafft_barriers_batch, rafft_kinfold_batch)
+
+// row r of sequence s in the caller's blocks of rows
+static const char *row_ptr(const char *const *rows, const int *row_stride, int s, size_t r) { return rows[s] + r * (size_t)row_stride[s]; }
+
+// what descend_parse_row's RAFFT_ERR_STRUCT says, behind the name of the row
+static const char *const ROW_PARSE_ERR = ": malformed, a non-canonical pair, or a hairpin of fewer than 3";
+
+// a bad row comes back as it went in: its bytes up to L or an earlier NUL, and a NUL
+static void copy_row_back(char *db, const char *row, int L)
+{
+    const size_t n = strnlen(row, (size_t)L);
+    memcpy(db, row, n);
+    db[n] = 0;
+}
+
+// The call's error text: that of the first erroneous item in input order, (sequence, item), item -1 for the sequence itself.
+// Seeded with the pack's first error; a later note at the same place does not replace an earlier one.
+struct FirstError {
+    long long at = -1;
+    std::string msg;
+    explicit FirstError(const SeqPack &pk) : msg(pk.first_err)
+    {
+        for (size_t s = 0; s < pk.status.size() && at < 0; s++) if (pk.status[s]) at = (long long)s << 32;
+    }
+    void note(int s, long long item, const std::string &m)
+    {
+        const long long k = ((long long)s << 32) + item + 1;
+        if (at < 0 || k < at) { at = k; msg = m; }
+    }
+    const std::string &text() const { return msg; }
+};
+
 // The walks that run (those without an error, in input order; walk k is over L[k] positions, may take bound[k] steps, its bases
 // lie at code_off[k], want_moves[k]: the caller asked for its moves): chunks of whole walks whose rows and move buffers together fit
 // the budget, one walk at least, DESCEND_CHUNK_WALKS at most.  Per chunk the rows lie back to back from byte 0 of the row buffer,

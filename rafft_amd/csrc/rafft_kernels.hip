@@ -26,10 +26,10 @@
 //   eval_kernel         (rafft_io_kernels.hip) whole-structure energy (rafft/utils.py:135-138), C-ABI hook
 //   findpath_*_kernel   (rafft_findpath.hip) folding barriers between structure pairs: not part of the fold, but built on
 //                       loop_energy, PlainView's kin and the radix select below
-//   descend_kernel      (rafft_descend.hip) gradient walks to local minima, on loop_energy and findpath's view
+//   descend_kernel      (rafft_descend.hip) gradient walks to local minima over the move set of rafft_moves.h
 //   barriers_*_kernel   (rafft_barriers.hip) exact barrier trees of energy bands: keys, a hash table of the rows, neighbours looked up
 //                       in it; no energy is evaluated
-//   kinfold_kernel      (rafft_kinfold.hip) stochastic folding trajectories: descend's neighbours, summed weights, Philox
+//   kinfold_kernel      (rafft_kinfold.hip) stochastic folding trajectories: the same move set (its own copy), summed weights, Philox
 //
 // This is bandwidth/latency-bound small-FFT + integer table work: no MFMA.
 #include "rafft_kernels.h"
@@ -179,6 +179,7 @@ struct PlainView {
 #include "rafft_beam.hip"               // beam_step_kernel, the seen table
 #include "rafft_materialize.hip"        // materialize_kernel, materialize_team_kernel, dedupe_kernel
 #include "rafft_io_kernels.hip"         // stage_in_kernel, init_roots_kernel, output_kernel, eval_kernel
+#include "rafft_moves.h"                // the single-pair move set of the four below: FpView, enclosing_pair, next_partner, moves_at, structure_energy
 #include "rafft_findpath.hip"           // findpath_init_kernel, findpath_expand_kernel, findpath_select_kernel, findpath_trace_kernel
 #include "rafft_descend.hip"            // descend_kernel
 #include "rafft_barriers.hip"           // barriers_keys_kernel, barriers_insert_kernel, barriers_scan_kernel, barriers_basin_kernel

@@ -1,7 +1,11 @@
 // rafft_kinfold.hip - stochastic folding trajectories (gfx950): continuous-time Monte Carlo (Gillespie) over insertion and deletion
 // of single pairs with Metropolis rates, what ViennaRNA's Kinfold simulates, defined exactly in DESIGN.md section 16 and
-// include/rafft_hip.h.  The neighbours and their dE are rafft_descend.hip's: every loop term comes from loop_energy
-// (rafft_device.h) through FpView (rafft_findpath.hip).  Included by rafft_kernels.hip, after rafft_descend.hip.
+// include/rafft_hip.h.  The neighbours and their dE are those of rafft_moves.h, but this kernel keeps ITS OWN COPY of moves_at's
+// body (enclosing pair, next partner, phase machine) and of the start energy: built on moves_at it kept its 108-110 VGPRs but went
+// from 29 to 43 spilled SGPRs - in three shapes of the visitor alike - and its calls took 3.4 % longer on the MI355X
+// (profiles/move_set_refactor_ab.txt).  A change to the move set in rafft_moves.h must be made here as well; the bit-for-bit
+// comparisons of tests/test_gpu_kinfold.py with the mirror would show a disagreement.  Included by rafft_kernels.hip, after
+// rafft_descend.hip.
 //
 // One WAVEFRONT per trajectory, one launch per chunk, the whole trajectory inside it, for the reasons rafft_descend.hip gives: a
 // call brings thousands of trajectories over tens to hundreds of positions, each a long chain of short steps.  A trajectory holds

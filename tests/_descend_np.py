@@ -66,6 +66,54 @@ def neighbours(seq, row):
     return out
 
 
+# ---- neighbours, stated another way: two unpaired positions may pair when the same pair encloses both (they are members of one loop)
+
+def move_row(row, i, j, rem):
+    return row[:i] + ("." if rem else "(") + row[i + 1:j] + ("." if rem else ")") + row[j + 1:]
+
+
+def all_neighbours(seq, row):
+    """[(i, j, is_removal)], sorted"""
+    out, members, stack = [], {}, [-1]
+    for x, c in enumerate(row):
+        if c == "(":
+            stack.append(x)
+        elif c == ")":
+            out.append((stack.pop(), x, True))
+        else:
+            members.setdefault(stack[-1], []).append(x)
+    for g in members.values():
+        for a, i in enumerate(g):
+            for j in g[a + 1:]:
+                if j - i > 3 and seq[i] + seq[j] in CANONICAL:
+                    out.append((i, j, False))
+    return sorted(out)
+
+
+def random_row(rng, seq, n_add):
+    """the open chain of `seq` with up to n_add random legal pairs added, one after the other"""
+    row = "." * len(seq)
+    for _ in range(n_add):
+        adds = [n for n in all_neighbours(seq, row) if not n[2]]
+        if not adds:
+            break
+        i, j, _ = adds[int(rng.integers(len(adds)))]
+        row = move_row(row, i, j, False)
+    return row
+
+
+# the lengths at which the lanes' stride over the positions, x = lane, lane + 64, ..., turns over
+STRIDE_LENGTHS = (63, 64, 65, 129)
+
+
+def stride_rows(L):
+    """(seq, rows): a random sequence of L nt and four rows of it - the open chain, a few pairs, some helices' worth, and as many
+    pairs as random additions find room for"""
+    rng = np.random.default_rng(L)
+    seq = "".join(rng.choice(list("ACGU"), L))
+    return seq, [random_row(rng, seq, n) for n in (0, 3, L // 6, L)]
+
+
 def walk(seq, row, max_steps=0, energy=oracle.eval_structure):
     """dict(status, end, n_steps, start_dcal, end_dcal, moves, dcal, ties, tie_kinds): moves as the library reports them - (i, j) for
     an added pair, (-i-1, -j-1) for a removed one; dcal: the energy of every row of the path; ties: the steps at which more than one

@@ -1,6 +1,7 @@
 // Host-side check of the descend part of rafft_amd/csrc/rafft_hostpure.h: the pair table and status of a start row
 // (descend_parse_row) against what the test passes in, and the layout of a call (descend_layout, the descend_* sizes of
-// rafft_batch_layout.h) at the edges of the workspace budget against values derived by hand.  Plain C++, no HIP, no GPU.
+// rafft_batch_layout.h) at the edges of the workspace budget against values derived by hand, and the row intake the three row
+// drivers share (row_ptr, copy_row_back, FirstError).  Plain C++, no HIP, no GPU.
 // usage: descend_check [SEQ ROW STATUS PAIRS]...   PAIRS = "i-j,i-j,..." (ascending 5' end), ignored when STATUS != 0; ROW may be
 // shorter than SEQ (the library then meets its NUL).  Test infrastructure.
 #include <cstdio>
@@ -82,10 +83,62 @@ static void check_layout()
     }
 }
 
+static void check_intake()
+{
+    // row_ptr: blocks of rows with a stride of their own each
+    const char a[] = "....\0((..))\0", b[] = "x.yy.zz.";
+    const char *const rows[2] = {a, b};
+    const int stride[2] = {7, 3};
+    CHECK(row_ptr(rows, stride, 0, 0) == a && row_ptr(rows, stride, 0, 1) == a + 7 && row_ptr(rows, stride, 1, 2) == b + 6);
+    // copy_row_back: the row's bytes up to L or an earlier NUL, then a NUL; nothing behind it is written or read
+    {
+        std::vector<char> row = {'(', '(', '.', 0}, db(8, '#');          // (an early NUL: the row ends there, and so does the buffer)
+        copy_row_back(db.data(), row.data(), 6);
+        CHECK(std::string(db.data(), 8) == std::string("((.\0####", 8));
+        std::vector<char> full = {'(', '.', '.', '.', ')'}, db2(8, '#'); // (no NUL within L: exactly L bytes are read)
+        copy_row_back(db2.data(), full.data(), 5);
+        CHECK(std::string(db2.data(), 8) == std::string("(...)\0##", 8));
+        std::vector<char> empty = {0}, db3(2, '#');
+        copy_row_back(db3.data(), empty.data(), 1);
+        CHECK(db3[0] == 0 && db3[1] == '#');
+    }
+    // FirstError: the lowest (sequence, item) wins, item -1 is the sequence itself, the first note of a place stays
+    {
+        SeqPack pk;
+        pk.status = {0, RAFFT_ERR_EMPTY, 0, RAFFT_ERR_BAD_CHAR};
+        pk.first_err = "sequence 1: empty";
+        FirstError e(pk);
+        CHECK(e.text() == "sequence 1: empty");
+        e.note(2, 0, "s2 r0");          CHECK(e.text() == "sequence 1: empty");        // behind the pack's error
+        e.note(1, 3, "s1 r3");          CHECK(e.text() == "sequence 1: empty");        // at the sequence that has it: the sequence comes first
+        e.note(1, -1, "s1");            CHECK(e.text() == "sequence 1: empty");        // ... and stays (strictly lower only)
+        e.note(0, 5, "s0 r5");          CHECK(e.text() == "s0 r5");
+        e.note(0, 2, "s0 r2");          CHECK(e.text() == "s0 r2");                    // a note out of order
+        e.note(0, 4, "s0 r4");          CHECK(e.text() == "s0 r2");
+        e.note(0, 2, "s0 r2 again");    CHECK(e.text() == "s0 r2");
+        e.note(0, 0, "s0 r0");          CHECK(e.text() == "s0 r0");
+        e.note(0, -1, "s0");            CHECK(e.text() == "s0");                       // item -1 against item 0
+        e.note(0, 0, "s0 r0 again");    CHECK(e.text() == "s0");
+        e.note(0, -1, "s0 again");      CHECK(e.text() == "s0");
+    }
+    {
+        SeqPack pk;
+        pk.status = {0, 0, 0};
+        FirstError e(pk);
+        CHECK(e.text().empty() && e.at < 0);
+        e.note(2, -1, "s2");            CHECK(e.text() == "s2");
+        e.note(1, 0x7ffffffell, "s1 last");     CHECK(e.text() == "s1 last");          // the largest item stays below the next sequence
+        e.note(1, 0, "s1 r0");          CHECK(e.text() == "s1 r0");
+        e.note(2, -1, "s2 again");      CHECK(e.text() == "s1 r0");
+    }
+    CHECK(std::string("sequence 0 row 0") + ROW_PARSE_ERR == "sequence 0 row 0: malformed, a non-canonical pair, or a hairpin of fewer than 3");
+}
+
 int main(int argc, char **argv)
 {
     check_sizes();
     check_layout();
+    check_intake();
     if ((argc - 1) % 4) { fprintf(stderr, "usage: descend_check [SEQ ROW STATUS PAIRS]...\n"); return 2; }
     for (int k = 1; k + 3 < argc; k += 4) check_case(argv[k], argv[k + 1], atoi(argv[k + 2]), argv[k + 3]);
     printf("%d cases, %d failures\n", (argc - 1) / 4, fails);

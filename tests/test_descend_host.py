@@ -125,6 +125,47 @@ def test_host_pure_part_against_the_tests_values_under_sanitizers(tmp_path):
     assert r.returncode == 1 and "1 failures" in r.stdout
 
 
+def move_set_cases():
+    """(sequence, row): the valid rows of PARSE_CASES, a slice of the starts, rows constructed for the edges of the walks, random rows
+    at the lengths where the lanes' stride of 64 turns over"""
+    cases = [(seq, row[:len(seq)]) for seq, row, st in PARSE_CASES if st == 0] + DS.starts()[::40]
+    hp, two = "GGGGAAAACCCC", "A" + "GGGAAACCC" + "U" + "GGGAAACCC" + "U"
+    cases += [("G", "."), ("GAAC", "...."), ("GAAAC", "....."), ("GAAAC", "(...)"),            # L = 1, 4 and 5, the shortest row with a possible pair
+              (hp, "." * 12), ("AAAAAAAAAAAAUUUU" * 4, "." * 64),                               # open chains
+              (two, "." + "(((...)))" + "." + "(((...)))" + "."),                                # an exterior loop of two helices, a partner directly behind each
+              (two, "." + "(((...)))" + "." + "........." + "."), (two, "(" + "(((...)))" + ")" + "(((...)))" + "."),
+              ("GAGAAACGAAACGAAACC", "(.(...)(...).....)"), ("GAGAAACGAAACGAAACC", "..(...)(...)......"),      # a multiloop, and before it closes
+              ("GAAAAAAAAAAAAAAAAC", "(................)"), (hp, "(..........)"), (hp, "(.(......).)"),           # lonely pairs
+              ("GGGNAAAANCCC", "(((......)))"), ("GGGNAAAANCCC", "." * 12), ("NNNNNNNNNNNN", "." * 12), ("NGGGAAAACCCN", ".(((....)))."), ("UNNNNAUNNNNA", "." * 12)]
+    for L in DS.STRIDE_LENGTHS:
+        seq, rows = DS.stride_rows(L)
+        cases += [(seq, row) for row in rows]
+    return cases
+
+
+def test_move_set_positions_against_brute_force_on_the_host(tmp_path):
+    """rafft_moves.h's enclosing_pair and next_partner, host-only: the moves they yield equal the program's own brute force, the
+    restatement's brute-force scan (DS.neighbours) and the loops' members (DS.all_neighbours) - three statements against the one
+    under test -, with next_partner bounded by the enclosing pair and by L"""
+    argv = []
+    for seq, row in move_set_cases():
+        assert DS.parse_status(seq, row) == 0, (seq, row)
+        want = sorted((i, j, rem) for i, j, rem, _ in DS.neighbours(seq, row))
+        assert want == DS.all_neighbours(seq, row), (seq, row)
+        argv += [seq, row, ",".join(f"{i}-{j}-{'r' if rem else 'a'}" for i, j, rem in want)]
+    assert len(argv) // 3 >= 90 and any(len(a) > 5000 for a in argv[2::3]) and "" in argv[2::3]
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "moves_check")
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "-O1", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-missing-braces",
+                           os.path.join(ROOT, "tests", "hostcheck", "moves_check.cpp"), "-o", exe])
+    r = subprocess.run([exe] + argv, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and f"{len(argv) // 3} cases, 0 failures" in r.stdout and not r.stderr, r.stdout + r.stderr[-2000:]
+    # the program does tell a wrong list from a right one: a move too few, a move too many, a removal called an addition
+    for wrong in ("0-11-r,1-10-r,2-9-r", "0-11-r,1-10-r,2-9-r,3-8-r,4-8-a", "0-11-r,1-10-r,2-9-r,3-8-a"):
+        r = subprocess.run([exe, "GGGGAAAACCCC", "((((....))))", wrong], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 1 and "1 cases, 2 failures" in r.stdout, (wrong, r.stdout + r.stderr)
+
+
 def test_descend_records_and_limits_match_the_header():
     hdr = open(os.path.join(ROOT, "include", "rafft_hip.h")).read()
     for name, cls, fields in (("rafft_descend_seq", _native.DescendSeq, ["status", "length", "n_rows", "row0"]),

@@ -18,6 +18,7 @@ from rafft_amd import _native as N, barriers as BR, descend as DSm, findpath as 
 from conftest import ROOT
 import _barriers_np as BM
 import _descend_np as DS
+from _descend_np import all_neighbours, move_row
 import _loops as LP
 import _par_reader as PR
 
@@ -149,29 +150,7 @@ def test_ties_and_plateaus_follow_the_order_of_the_list():
     assert any(len(a["rank"]) != len(b["rank"]) or a["basin_size"].tolist() != b["basin_size"].tolist() for a, b in zip(got, got2))
 
 
-# ---- neighbours, stated a third way: two unpaired positions may pair when the same pair encloses both (they are members of one loop)
-
-def move_row(row, i, j, rem):
-    return row[:i] + ("." if rem else "(") + row[i + 1:j] + ("." if rem else ")") + row[j + 1:]
-
-
-def all_neighbours(seq, row):
-    """[(i, j, is_removal)]"""
-    out, members, stack = [], {}, [-1]
-    for x, c in enumerate(row):
-        if c == "(":
-            stack.append(x)
-        elif c == ")":
-            out.append((stack.pop(), x, True))
-        else:
-            members.setdefault(stack[-1], []).append(x)
-    for g in members.values():
-        for a, i in enumerate(g):
-            for j in g[a + 1:]:
-                if j - i > 3 and seq[i] + seq[j] in DS.CANONICAL:
-                    out.append((i, j, False))
-    return out
-
+# ---- neighbours, stated a third way (_descend_np.all_neighbours: from the loops' members)
 
 class Lookup:
     """the ranks of a row's neighbours in a band: neighbours from the loops' members, found through a sum of random 64-bit numbers

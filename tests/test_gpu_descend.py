@@ -18,6 +18,7 @@ import rafft_amd
 from rafft_amd import _native as N, descend as DSm, findpath as FPm, mccaskill, params, rafft as R
 from conftest import ROOT
 import _descend_np as DS
+from _descend_np import all_neighbours, move_row
 import _loops as LP
 import _par_reader as PR
 
@@ -75,29 +76,7 @@ def same_as_mirror(got, want, what):
     assert got["start_dcal"] == want["start_dcal"] and got["end_dcal"] == want["end_dcal"] and got["moves"] == want["moves"], (what, got, want)
 
 
-# ---- neighbours, stated a third way: two unpaired positions may pair when the same pair encloses both (they are members of one loop)
-
-def move_row(row, i, j, rem):
-    return row[:i] + ("." if rem else "(") + row[i + 1:j] + ("." if rem else ")") + row[j + 1:]
-
-
-def all_neighbours(seq, row):
-    """[(i, j, is_removal)]"""
-    out, members, stack = [], {}, [-1]
-    for x, c in enumerate(row):
-        if c == "(":
-            stack.append(x)
-        elif c == ")":
-            out.append((stack.pop(), x, True))
-        else:
-            members.setdefault(stack[-1], []).append(x)
-    for g in members.values():
-        for a, i in enumerate(g):
-            for j in g[a + 1:]:
-                if j - i > 3 and seq[i] + seq[j] in DS.CANONICAL:
-                    out.append((i, j, False))
-    return out
-
+# ---- neighbours, stated a third way (_descend_np.all_neighbours: from the loops' members)
 
 def disturbed(rng, seq, row, n_remove, n_add):
     """`row` with some pairs removed and random legal pairs added, one after the other"""
@@ -213,6 +192,19 @@ def test_longer_sequences_from_sampled_and_disturbed_rows():
             n_mirror += 1
     assert n_mirror >= 24
     print(f"{walk_checks(seqs, rows, got)} rows evaluated back")
+
+
+@pytest.mark.parametrize("L", DS.STRIDE_LENGTHS)
+def test_lengths_where_the_lanes_stride(L):
+    """63, 64, 65 and 129 positions, where a lane's share x = lane, lane + 64, ... gains a position: random rows from the open chain
+    to one with no room left, exactly the restatement's walks"""
+    seq, rows = DS.stride_rows(L)
+    en = DS.cached_energy()
+    want = [DS.walk(seq, row, 0, en) for row in rows]
+    assert {m[0] < 0 for w in want for m in w["moves"]} == {True, False} and max(w["n_steps"] for w in want) >= 9
+    got = flat([seq] * len(rows), rows)
+    for row, g, w in zip(rows, got, want):
+        same_as_mirror(g, w, (L, row))
 
 
 # ---- edges

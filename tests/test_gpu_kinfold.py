@@ -19,6 +19,7 @@ import oracle
 from rafft_amd import _native as N, kinfold as KFm, findpath as FPm, mccaskill, params, rafft as R, zuker
 from conftest import ROOT
 import _descend_np as DS
+from _descend_np import all_neighbours, move_row
 import _kinfold_np as KF
 import _loops as LP
 import _par_reader as PR
@@ -127,28 +128,6 @@ def test_trajectories_are_the_restatements_bit_for_bit(sets, which):
 
 # ---- 2. larger sizes: the same equality where the restatement is affordable, and what can be checked beyond it
 
-def move_row(row, i, j, rem):
-    return row[:i] + ("." if rem else "(") + row[i + 1:j] + ("." if rem else ")") + row[j + 1:]
-
-
-def all_neighbours(seq, row):
-    """[(i, j, is_removal)], a third way: two unpaired positions may pair when the same pair encloses both (members of one loop)"""
-    out, members, stack = [], {}, [-1]
-    for x, c in enumerate(row):
-        if c == "(":
-            stack.append(x)
-        elif c == ")":
-            out.append((stack.pop(), x, True))
-        else:
-            members.setdefault(stack[-1], []).append(x)
-    for g in members.values():
-        for a, i in enumerate(g):
-            for j in g[a + 1:]:
-                if j - i > 3 and seq[i] + seq[j] in DS.CANONICAL:
-                    out.append((i, j, False))
-    return sorted(out)
-
-
 def path_checks(items, W, seed_of, sampled_steps=3, temp=37.0, seed=5):
     """items: (seq, start row, k, trajectory).  Every row of every logged path evaluates back with the running energy; on up to
     `sampled_steps` steps per trajectory the sum of the weights (through the jump time) and the move are what the neighbours of
@@ -218,6 +197,23 @@ def test_longer_sequences_equal_the_restatement_and_evaluate_back():
     print(f"\n{len(items)} trajectories, {sum(steps)} steps, {max(steps)} at most")
     assert all(g["status"] == 0 for _, _, _, g in items) and sum(steps) >= 10 * len(items)
     assert path_checks(items, W, 77) >= 2 * len(items)
+
+
+@pytest.mark.parametrize("L", DS.STRIDE_LENGTHS)
+def test_lengths_where_the_lanes_stride(L):
+    """63, 64, 65 and 129 positions, where a lane's share x = lane, lane + 64, ... gains a position and the lane that owns the drawn
+    position, xs & 63, is no longer xs: four trajectories of 32 steps from random rows, exactly the restatement's"""
+    seq, rows = DS.stride_rows(L)
+    watch, grid = [rows[2], "." * L], [1e-3, 1.0, 1e9]
+    M = KF.Mirror(KFm.kinfold_weights())
+    want = [M.trajectory(seq, r, k, 900 + L, 1e9, 32, watch, 0, grid) for k, r in enumerate(rows)]
+    assert all(w["n_steps"] == 32 and w["flags"] == KF.KF_MORE for w in want)
+    top = max(max(-a - 1 if a < 0 else a, -b - 1 if b < 0 else b) for w in want for a, b in w["moves"])
+    assert top >= (64 if L == 129 else L - 4), top            # (moves reach the last positions, those of the second share at 129)
+    got = run([seq], [rows], 1e9, watch=[watch], n_stop=0, seeds=[900 + L], sample_times=grid, max_steps=32)[0]
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        same_as_mirror(g, w, (L, k))
 
 
 def test_300_and_1000_nt():
