@@ -405,6 +405,37 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
                    double *const *prob_out     /* may be NULL, and so may prob_out[s]: lens[s] x lens[s] doubles, row-major,
                                                   P(i pairs j) at [i][j] for i < j, 0 elsewhere */);
 
+/* Partition function, base-pair probabilities, centroid and unpaired probabilities under a maximum base-pair span, for sequences
+ * of up to RAFFT_MFE_SPAN_MAX_LEN nt (what `RNAfold -p --maxBPspan` and `RNAplfold -L` are used for on long
+ * RNAs).  The ensemble is rafft_pf_batch's restricted to the structures whose pairs (i, j), i < j, all have j - i + 1 <= max_span;
+ * the exterior loop is not restricted.  Weights, kT and dangles=2 are rafft_pf_batch's.  Z is the sum of the weights over that
+ * ensemble, P(i,j) the weight share of its structures that hold (i,j), energy = -kT ln Z, the centroid row holds the pairs with
+ * P > 0.5, mfe_dcal is what rafft_mfe_span_batch returns for the same max_span (the call runs it first; the scale comes from it)
+ * and mfe_frequency = exp((energy - mfe_dcal/100) / kT).  unpaired[i] = 1 - sum_j P(i,j) - sum_h P(h,i), clamped to [0, 1], each
+ * position summed in an order that lens[s] and max_span fix.  max_span of 1 to 4 gives the open chain: energy 0, every P 0.
+ * Every sequence has six L x W fp64 tables in device memory, W = min(max_span, L): 48 L W + 8 (3 L + 2 W + 6) + 8 (L + 1) + L + 1
+ * bytes with its other arrays (226 MiB at 32768 nt and span 150); chunks of whole sequences, in input order, that fit
+ * workspace_bytes (0: 512 MiB; one sequence at least).  The band cells are scaled fp64 as rafft_pf_batch's; the exterior sums,
+ * which cover the whole sequence, are held as a mantissa and a binary exponent per position, so their range does not limit L.
+ * Outputs (host): seq_out[s] and db_out[s] as rafft_pf_batch.  prob_out may be NULL and so may prob_out[s], else it is BANDED:
+ * lens[s] x W_s doubles, W_s = min(max_span, lens[s]), P(i, i + d) at [i * W_s + d]; entries with d < 4 or i + d >= lens[s] are
+ * 0 (a dense matrix at 32768 nt would be 8 GiB).  unpaired_out may be NULL and so may unpaired_out[s], else lens[s] doubles.
+ * Errors of a sequence as rafft_pf_batch (RAFFT_ERR_TOO_LONG: above RAFFT_MFE_SPAN_MAX_LEN; the buffers of such a sequence are
+ * not written): its row is all dots, its numbers are 0, its neighbours are untouched, rafft_last_error() names the first such
+ * sequence.  RAFFT_ERR_CAPACITY: a band cell left the fp64 range - the mantissa of Z is not finite and positive, Z is below the
+ * weight of the MFE structure, or a probability is not finite; heterogeneous sequences at very wide spans can meet it.
+ * RAFFT_ERR_PARAM, before anything is launched: a null argument, a negative count or workspace, a scale_factor that is negative
+ * or not finite, max_span outside 1 .. RAFFT_MFE_MAX_LEN.  RAFFT_ERR_TEMP as for the fold.  A sequence's bits depend on the
+ * sequence, the energy tables, temp, scale_factor and max_span only - not on the batch, its order, the chunks or the workspace. */
+int rafft_pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                        double scale_factor,        /* 0: 1.07 */
+                        int max_span,               /* 1 .. RAFFT_MFE_MAX_LEN */
+                        long long workspace_bytes,  /* 0: 512 MiB; one sequence at least */
+                        rafft_pf_seq *seq_out,
+                        char *const *db_out,        /* db_out[s]: lens[s]+1 bytes, the centroid row, NUL terminated */
+                        double *const *prob_out,    /* may be NULL, and so may prob_out[s]: lens[s] x W_s doubles, banded */
+                        double *const *unpaired_out /* may be NULL, and so may unpaired_out[s]: lens[s] doubles */);
+
 /* Maximum-expected-accuracy (MEA) structures and the ensemble diversity of a batch.  Replaces: what
  * `RNAfold -p --MEA` prints beside the centroid.  rafft_mea_batch is rafft_pf_batch plus the recursion below on the device's own
  * P; rafft_mea_probs_batch runs the same recursion on matrices the caller brings - pair probabilities, or pair frequencies of

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libraffthip.so")
-SOURCES = ["rafft_api.hip", "rafft_kernels.hip", "rafft_expand.hip", "rafft_expand_small.hip", "rafft_beam.hip", "rafft_materialize.hip", "rafft_io_kernels.hip", "rafft_kin.hip", "rafft_kin_batch.hip", "rafft_landscape.hip", "rafft_score.hip", "rafft_mfe.hip", "rafft_mfe_span.hip", "rafft_pf.hip", "rafft_mea.hip", "rafft_sample.hip", "rafft_subopt.hip", "rafft_findpath.hip", "rafft_descend.hip", "rafft_barriers.hip", "rafft_kinfold.hip", "rafft_moves.h", "rafft_batch_layout.h", "rafft_rng.h", "rafft_host_ctx.h", "rafft_plan.h", "rafft_wave.h", "rafft_sched.h", "rafft_submit.h", "rafft_seam.h", "rafft_batch.h", "rafft_hostpure.h", "rafft_kernels.h", "rafft_expand_common.h", "rafft_device.h", "rafft_params.h", "rafft_config.h", "../../params/turner2004_tables.h"]
+SOURCES = ["rafft_api.hip", "rafft_kernels.hip", "rafft_expand.hip", "rafft_expand_small.hip", "rafft_beam.hip", "rafft_materialize.hip", "rafft_io_kernels.hip", "rafft_kin.hip", "rafft_kin_batch.hip", "rafft_landscape.hip", "rafft_score.hip", "rafft_mfe.hip", "rafft_mfe_span.hip", "rafft_pf.hip", "rafft_pf_span.hip", "rafft_mea.hip", "rafft_sample.hip", "rafft_subopt.hip", "rafft_findpath.hip", "rafft_descend.hip", "rafft_barriers.hip", "rafft_kinfold.hip", "rafft_moves.h", "rafft_batch_layout.h", "rafft_rng.h", "rafft_host_ctx.h", "rafft_plan.h", "rafft_wave.h", "rafft_sched.h", "rafft_submit.h", "rafft_seam.h", "rafft_batch.h", "rafft_hostpure.h", "rafft_kernels.h", "rafft_expand_common.h", "rafft_device.h", "rafft_params.h", "rafft_config.h", "../../params/turner2004_tables.h"]
 
 
 def needs_build():

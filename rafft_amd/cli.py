@@ -60,6 +60,12 @@ _OPTIONS = [
                                                "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
                                                "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
                                                "Works with -s SEQ and with -sf FILE --batch; not with --mfe, --kin or --traj")),
+    (("--pf-span",), dict(type=int, default=None, metavar="W", dest="pf_span",
+                          help="with --pf: the ensemble restricted to pairs (i, j) with j - i + 1 <= W, 1 <= W <= 4096 (rafft_amd.pf_span_batch; as\n"
+                               "`RNAfold -p --maxBPspan W`), for sequences of up to 32768 nt.  Output and --scores as --pf")),
+    (("--bpp",), dict(type=str, default=None, metavar="FILE", help="with --pf: the pair probabilities of every sequence into FILE, one line `name i j p` per pair\n"
+                                                                  "with p >= --bpp-cutoff, positions 1-based, i ascending then j.  With or without --pf-span")),
+    (("--bpp-cutoff",), dict(type=float, default=1e-5, metavar="C", dest="bpp_cutoff", help="the smallest probability --bpp writes (default 1e-5)")),
     (("--mea",), dict(type=float, nargs="?", const=1.0, default=None, metavar="GAMMA",
                       help="no RAFFT fold: the maximum-expected-accuracy structure of every sequence on the GPU (rafft_amd.mea_batch; the\n"
                            "pair probabilities of --pf; GAMMA weighs a pair against an unpaired base, default 1.0), one line per sequence:\n"
@@ -280,14 +286,30 @@ def format_pf_line(sequence, res):
     return f"{sequence} {len(sequence)} {res.centroid} {res.energy:.2f} {res.centroid.count('(')} {res.mfe_frequency:.4g}"
 
 
+def write_bpp(path, names, results, cutoff):
+    """--bpp: `name i j p` per pair with p >= cutoff, 1-based; a result's probs are banded (L, W) under --pf-span, else L x L"""
+    from .mccaskill import band_pairs, dense_pairs
+    with open(path, "w") as out:
+        for k, r in enumerate(results):
+            name = names[k] if names is not None and names[k] else str(k + 1)
+            banded = r.unpaired is not None                 # (what pf_span_batch alone fills)
+            for i, j, p in (band_pairs if banded else dense_pairs)(r.probs, cutoff):
+                out.write(f"{name} {i + 1} {j + 1} {p:.6g}\n")
+
+
 def main_pf(args, seqs, known, names, pf_batch=None, scorer=None):
     """--pf: centroid, ensemble free energy and MFE share instead of the fold.  `scorer` as for main_mfe."""
     if args.mfe or args.kin or args.traj:
         raise SystemExit("--pf gives the ensemble of every sequence: no --mfe, no --kin, no --traj")
+    if pf_batch is None and args.pf_span is not None:
+        from .mccaskill import pf_span_batch
+        pf_batch = lambda sequences, temp: pf_span_batch(sequences, args.pf_span, temp, probs=bool(args.bpp))
     if pf_batch is None:
         from .mccaskill import pf_batch as _pf
-        pf_batch = lambda sequences, temp: _pf(sequences, temp, probs=False)
+        pf_batch = lambda sequences, temp: _pf(sequences, temp, probs=bool(args.bpp))
     results = pf_batch(seqs, args.temp)
+    if args.bpp:
+        write_bpp(args.bpp, names, results, args.bpp_cutoff)
     if args.scores:
         if scorer is None:
             from .scoring import score_rows_gpu as scorer
@@ -640,6 +662,10 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
         raise SystemExit("--span W restricts the pairs of --mfe: it needs --mfe")
     if args.span is not None and not 1 <= args.span <= 4096:
         raise SystemExit("--span is 1 to 4096")
+    if (args.pf_span is not None or args.bpp) and not args.pf:
+        raise SystemExit("--pf-span W and --bpp FILE belong to --pf: they need --pf")
+    if args.pf_span is not None and not 1 <= args.pf_span <= 4096:
+        raise SystemExit("--pf-span is 1 to 4096")
     if args.findpath:
         if args.descend:
             raise SystemExit("--findpath and --descend are two modes")

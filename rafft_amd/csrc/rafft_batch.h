@@ -1,5 +1,5 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
-// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), mfe_span_batch (the same under a base-pair span, to 32768 nt), pf_batch (partition
+// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), mfe_span_batch (the same under a base-pair span, to 32768 nt), pf_span_batch (partition function and pair probabilities under a span, to 32768 nt), pf_batch (partition
 // function and pair probabilities), mea_batch and mea_probs_batch (maximum-expected-accuracy structures), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
 // energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima), barriers_batch (exact barrier trees of energy bands) and kinfold_batch (stochastic folding trajectories), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
 // pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
@@ -490,6 +490,111 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
         if (seq_out[s].status) continue;
         if (rec[s].status || rec[s].bad) {
             pf_left_range(s, seq_out[s].status, err, prob_out ? prob_out[s] : nullptr, (size_t)qs[s].L * qs[s].L * sizeof(double));
+            continue;
+        }
+        seq_out[s].n_pairs = rec[s].n_pairs;
+        seq_out[s].energy = rec[s].energy;
+        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
+        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    g_err = err;
+    return 0;
+}
+
+// ---- partition function and pair probabilities under a base-pair span
+
+// rafft_pf_span_batch (arguments validated by the entry point).  mfe_span_batch first, as any caller runs it: its energies give the
+// scales and the mfe_dcal of the records.  Then one guard and one upload of the bases; chunks of whole sequences in input order
+// whose banded tables fit the workspace budget (one sequence at least; pf_span_layout); per chunk one launch per anti-diagonal of
+// its widest band upwards, the exterior sums, one launch per anti-diagonal downwards, the probabilities, and the copies of P and
+// of unpaired the caller asked for.  One synchronise at the end.
+int pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, int max_span, long long workspace_bytes,
+                  rafft_pf_seq *seq_out, char *const *db_out, double *const *prob_out, double *const *unpaired_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_SPAN_MAX_LEN, "RAFFT_MFE_SPAN_MAX_LEN");
+    for (int s = 0; s < n_seq; s++) {
+        const int len = pk.len[s];
+        seq_out[s] = rafft_pf_seq{pk.status[s], len, 0, 0, 0.0, 0.0};
+        dot_row(db_out[s], len);
+        if (pk.status[s] == RAFFT_ERR_TOO_LONG) continue;               // (no buffer is asked for beyond the limit)
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)len * mfe_span_width(len, max_span) * sizeof(double));
+        if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, (size_t)len * sizeof(double));
+    }
+    g_err = pk.first_err;
+    const std::vector<int> &order = pk.fold;
+    if (order.empty()) return 0;
+    std::vector<rafft_mfe_seq> mfe(n_seq);
+    {
+        std::vector<char> rows;
+        std::vector<char *> row_ptr(n_seq);
+        size_t at = 0;
+        for (int s = 0; s < n_seq; s++) at += (size_t)pk.len[s] + 1;
+        rows.resize(at);
+        at = 0;
+        for (int s = 0; s < n_seq; s++) { row_ptr[s] = rows.data() + at; at += (size_t)pk.len[s] + 1; }
+        if (int rc = mfe_span_batch(n_seq, seqs, lens, temp, max_span, workspace_bytes, mfe.data(), row_ptr.data())) return rc;
+    }
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
+    PfSpanLayout y = pf_span_layout(pk, max_span, workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE);
+    for (int s = 0; s < n_seq; s++) {
+        PfSpanSeq &q = y.qs[s];
+        const double ln_scale = q.L ? -sf * ((double)mfe[s].dcal / 100.0) / (kt * (double)q.L) : 0.0;
+        q.mfe_dcal = mfe[s].dcal; q.scale = std::exp(ln_scale); q.ln_scale = std::log(q.scale);
+        seq_out[s].mfe_dcal = mfe[s].dcal;
+    }
+    const std::vector<PfSpanSeq> &qs = y.qs;
+    PfSpanSeq *d_qs; double *d_aux, *d_ws; int *d_exp, *d_order; char *d_db; PfRec *d_rec;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(PfSpanSeq))) return rc;
+    if (int rc = mem.alloc(d_aux, y.n_aux * sizeof(double) + 16)) return rc;
+    if (int rc = mem.alloc(d_exp, y.n_exp * sizeof(int) + 16)) return rc;
+    if (int rc = mem.alloc(d_db, y.n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(PfRec))) return rc;
+    if (int rc = mem.alloc(d_order, order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(PfSpanSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(PfRec), st));
+    hipLaunchKernelGGL(pf_span_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, d_qs, n_seq, d_aux, beta);
+    HIPCHK(hipGetLastError());
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        const ChunkView v = chunk_view(c, d_order, order, pk);
+        const int Wmax = pf_span_chunk_wmax(c, order, qs);
+        for (int d = 0; d < Wmax; d++)
+            hipLaunchKernelGGL(pf_span_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d_aux, beta, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pf_span_exterior_kernel, dim3(v.ny), dim3(64), 0, st, d_qs, v.ord, d_ws, d_aux, d_exp, kt, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+        for (int d = Wmax - 1; d >= 4; d--)
+            hipLaunchKernelGGL(pf_span_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d_aux, d_exp, beta, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pf_span_prob_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, d_qs, v.ord, d_ws, d_aux, d_exp, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+        for (size_t k = c.a; k < c.b; k++) {
+            const int s = order[k];
+            const PfSpanSeq &q = qs[s];
+            const size_t n = (size_t)pf_span_table_doubles(q.L, q.W);
+            if (prob_out && prob_out[s]) HIPCHK(hipMemcpyAsync(prob_out[s], d_ws + q.tab_off + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (unpaired_out && unpaired_out[s])
+                HIPCHK(hipMemcpyAsync(unpaired_out[s], d_aux + q.aux_off + 2 * ((size_t)q.W + 2) + 2 * ((size_t)q.L + 1), (size_t)q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+    }
+    std::vector<PfRec> rec(n_seq);
+    std::vector<char> db(y.n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::string err = pk.first_err;
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].status || rec[s].bad) {
+            pf_left_range(s, seq_out[s].status, err, prob_out ? prob_out[s] : nullptr, (size_t)pf_span_table_doubles(qs[s].L, qs[s].W) * sizeof(double));
+            if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, (size_t)qs[s].L * sizeof(double));
             continue;
         }
         seq_out[s].n_pairs = rec[s].n_pairs;

@@ -1,5 +1,5 @@
 // rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_mfe_span.hip, rafft_pf.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
+// of rafft_mfe.hip, rafft_mfe_span.hip, rafft_pf.hip, rafft_pf_span.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
 // compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree, the buffers of a folding trajectory).  The layouts that fill the records are in
 // rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
 #pragma once
@@ -59,6 +59,35 @@ struct PfSeq {
 struct PfRec {
     int status, n_pairs, bad, pad;  // bad: a probability that is not finite
     double energy, mfe_frequency;
+};
+
+// ---- partition function and pair probabilities under a base-pair span (rafft_pf_span.hip)
+
+// What a sequence of L positions with pairs of at most max_span positions has on the device.  W = mfe_span_width(L, max_span)
+// cells d = j - i a row.  Six tables of L x W fp64 back to back from tab_off: C, M, Co, Mo as [i][d], M1 and M1o by their 3' end
+// as [j][d]; between the inside and the outside pass Co holds C w(exterior stem) by the 5' end and M1o the same by the 3' end
+// (what the exterior sums read), after the probability kernel Mo holds P as [i][d].  From aux_off, pf_span_aux_doubles(L, W)
+// doubles: ps and pb (W + 2 each), the mantissas of F and of Fr (L + 1 each), unpaired (L).  From exp_off, pf_span_exp_ints(L)
+// ints: the binary exponents of F and of Fr (L + 1 each).  A row of L + 1 bytes.
+//   bytes of a sequence = 48 L W + 8 (3 L + 2 W + 6) + 8 (L + 1) + L + 1
+#define PF_SPAN_TABLES 6
+#define PF_SPAN_RING 4096           // slots of the exterior kernel's LDS ring (a mantissa and an exponent each: 48 KiB), a power of two
+RAFFT_HD constexpr unsigned long long pf_span_table_doubles(int L, int W) { return (unsigned long long)L * (unsigned long long)W; }
+RAFFT_HD constexpr unsigned long long pf_span_aux_doubles(int L, int W) { return 2ull * ((unsigned long long)W + 2ull) + 2ull * ((unsigned long long)L + 1ull) + (unsigned long long)L; }
+RAFFT_HD constexpr unsigned long long pf_span_exp_ints(int L) { return 2ull * ((unsigned long long)L + 1ull); }
+RAFFT_HD constexpr unsigned long long pf_span_seq_bytes(int L, int W)
+{
+    return 8ull * (PF_SPAN_TABLES * pf_span_table_doubles(L, W) + pf_span_aux_doubles(L, W)) + 4ull * pf_span_exp_ints(L) + (unsigned long long)L + 1ull;
+}
+
+struct PfSpanSeq {
+    unsigned long long code_off;    // bases in `codes`
+    unsigned long long tab_off;     // first double of its six L x W tables in the workspace
+    unsigned long long aux_off;     // first double of ps, pb, the mantissas of F and Fr, unpaired
+    unsigned long long exp_off;     // first int of the exponents of F and Fr
+    unsigned long long db_off;      // its row in the output (L + 1 bytes)
+    int L, W, mfe_dcal, pad;
+    double scale, ln_scale;
 };
 
 // ---- maximum-expected-accuracy structures (rafft_mea.hip)

@@ -349,6 +349,40 @@ static PfLayout pf_layout(const SeqPack &pk, int n_tabs, const size_t *cost2, si
     return y;
 }
 
+// rafft_pf_span_batch: every sequence has W = min(max_span, L) cells a row and PF_SPAN_TABLES tables of L x W fp64; chunks (plan:
+// over pk.fold) of whole sequences in input order.  n_aux doubles and n_exp ints of the aux arrays, n_db bytes of rows over the
+// whole call.  mfe_dcal, scale and ln_scale of qs are left 0: they need the span MFE, which the driver gets from the device.
+struct PfSpanLayout {
+    std::vector<PfSpanSeq> qs;
+    ChunkPlan plan;
+    unsigned long long n_aux = 0, n_exp = 0, n_db = 0;
+};
+static PfSpanLayout pf_span_layout(const SeqPack &pk, int max_span, size_t budget)
+{
+    PfSpanLayout y;
+    const int n_seq = (int)pk.L.size();
+    y.qs.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) {
+        const int L = pk.L[s], W = mfe_span_width(L, max_span);
+        y.qs[s] = PfSpanSeq{pk.code_off[s], 0, y.n_aux, y.n_exp, y.n_db, L, W, 0, 0, 0.0, 0.0};
+        if (!L) continue;
+        y.n_aux += pf_span_aux_doubles(L, W); y.n_exp += pf_span_exp_ints(L); y.n_db += (unsigned long long)L + 1;
+    }
+    const std::vector<int> &order = pk.fold;
+    std::vector<size_t> tab_bytes(order.size());
+    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)(PF_SPAN_TABLES * pf_span_table_doubles(y.qs[order[k]].L, y.qs[order[k]].W) * sizeof(double));
+    y.plan = plan_chunks(order.size(), tab_bytes.data(), nullptr, budget, 65535);
+    for (size_t k = 0; k < order.size(); k++) y.qs[order[k]].tab_off = y.plan.off[k] / sizeof(double);
+    return y;
+}
+// the widest band of the sequences order[a .. b) of a chunk: the anti-diagonals its passes launch
+static int pf_span_chunk_wmax(const ChunkPlan::Range &c, const std::vector<int> &order, const std::vector<PfSpanSeq> &qs)
+{
+    int Wmax = 0;
+    for (size_t k = c.a; k < c.b; k++) Wmax = std::max(Wmax, qs[order[k]].W);
+    return Wmax;
+}
+
 // rafft_sample_batch.  The rows of pk.fold[k], n_samples of L + 1 bytes: the second cost of its plan
 static std::vector<size_t> sample_row_costs(const SeqPack &pk, int n_samples)
 {

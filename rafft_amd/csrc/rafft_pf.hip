@@ -25,6 +25,8 @@
 // scale^-n and pb[n] = (b / scale)^n.  In P the scales cancel.
 // One size class: full L x L fp64 tables in device memory, one launch per anti-diagonal (stream order is the synchronisation),
 // one wavefront per cell, candidates over the 64 lanes, summed by a butterfly of fixed order.
+// pf_cell and pf_out_cell are templates over a table view, so that rafft_pf_span.hip runs them over L x W tables (DESIGN.md
+// section 19); the kernels of this file use the full view PfTab.
 #pragma once
 
 #include "rafft_batch_layout.h"     // PfSeq, PfRec
@@ -33,10 +35,17 @@
 #define PF_GAS 1.98717e-3           // kcal / (mol K)
 #define PF_NCLOSE 175               // (pair type, base before the 3' end, base after the 5' end) of a closing pair
 
-// C, M and their outside twins by rows, M1 and M1o by columns (as MfeTabHbm)
+// C, M and their outside twins by rows, M1 and M1o by columns (as MfeTabHbm).  pf_cell and pf_out_cell are templates over such a
+// view; besides the six cell accessors a view says which cells it has: hi(i), one past the largest q of a cell (i,q); lo(j), the
+// smallest h of a cell (h,j); has(p,q).  This one, the full view, has every cell of the sequence (PfTabBand of rafft_pf_span.hip:
+// the cells with q - p < W).  The outside sums run over hi / lo / has and read no cell the view does not have; the inside sums of a
+// cell (i,j) stay within (i,j) and need no bound.
 struct PfTab {
     double *C, *M, *M1T, *Co, *Mo, *M1oT;
     int L;
+    __device__ __forceinline__ int hi(int) const { return L; }
+    __device__ __forceinline__ int lo(int) const { return 0; }
+    __device__ __forceinline__ bool has(int, int) const { return true; }
     __device__ __forceinline__ double &c(int i, int j) const { return C[(size_t)i * L + j]; }
     __device__ __forceinline__ double &m(int i, int j) const { return M[(size_t)i * L + j]; }
     __device__ __forceinline__ double &m1(int i, int j) const { return M1T[(size_t)j * L + i]; }
@@ -72,7 +81,8 @@ __global__ __launch_bounds__(64) void pf_powers_kernel(const EnergyTables *ET, c
 }
 
 // one wavefront fills cell (i,j) of the three inside tables; every cell of a smaller j - i is there
-__device__ inline void pf_cell(const PfTab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
+template <class TB>
+__device__ inline void pf_cell(const TB &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
                                double beta, int i, int j, int lane)
 {
     const int d = j - i;
@@ -180,21 +190,38 @@ __global__ __launch_bounds__(64) void pf_exterior_kernel(const EnergyTables *ET,
     }
 }
 
-// one wavefront fills cell (i,j) of the three outside tables; every cell of a larger j - i is there.  wcl: w(close) scale^-2 by
-// (type of the closing pair, the base before its 3' end, the base after its 5' end)
-__device__ inline void pf_out_cell(const PfTab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
-                                   const double *gF, const double *gFr, const double *wcl, double beta, int i, int j, int lane)
+// the exterior sums as pf_out_cell reads them: F[i] w Fr[j + 1], the weight of the exterior loop around a stem (i,j) of weight w
+struct PfExtPlain {
+    const double *gF, *gFr;
+    __device__ __forceinline__ double operator()(int i, int j, double w) const { return gF[i] * w * gFr[j + 1]; }
+};
+
+// w(close) scale^-2 by (type of the closing pair, the base before its 3' end, the base after its 5' end), by a workgroup of PF_NT
+__device__ inline void pf_fill_wcl(double *wcl, const SmallT *T, double beta, double ps2)
+{
+    for (int x = threadIdx.x; x < PF_NCLOSE; x += PF_NT) {
+        const int t = x / 25;
+        wcl[x] = t ? pf_w(T->ml_closing + e_stem(T, rtype(t), (x / 5) % 5, x % 5, false), beta) * ps2 : 0.0;
+    }
+    __syncthreads();
+}
+
+// one wavefront fills cell (i,j) of the three outside tables; every cell of a larger j - i that the view has is there.  wcl: the
+// table of pf_fill_wcl; ex: the exterior sums
+template <class TB, class EX>
+__device__ inline void pf_out_cell(const TB &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
+                                   const EX &ex, const double *wcl, double beta, int i, int j, int lane)
 {
     double a = 0.0;
     if (i >= 1)
-        for (int q = j + 6 + lane; q < L; q += 64) {
+        for (int q = j + 6 + lane, qe = tb.hi(i - 1); q < qe; q += 64) {
             const double x = tb.co(i - 1, q);
             if (x != 0.0) a += x * wcl[(pair_type(S[i - 1], S[q]) * 5 + S[q - 1]) * 5 + S[i]] * tb.m1(j + 1, q - 1);
         }
-    for (int q = j + 5 + lane; q < L; q += 64) a += tb.mo(i, q) * tb.m1(j + 1, q);
+    for (int q = j + 5 + lane, qe = tb.hi(i); q < qe; q += 64) a += tb.mo(i, q) * tb.m1(j + 1, q);
     const double mo = pf_wave_sum(a);
     a = 0.0;
-    for (int h = lane; h < i; h += 64) {
+    for (int h = tb.lo(j) + lane; h < i; h += 64) {
         const double x = tb.mo(h, j);
         if (x == 0.0) continue;
         double left = pb[i - h];
@@ -202,20 +229,20 @@ __device__ inline void pf_out_cell(const PfTab &tb, const SmallT *T, const BigT 
         a += x * left;
     }
     if (j + 1 < L)
-        for (int h = lane; h <= i - 6; h += 64) {
+        for (int h = tb.lo(j + 1) + lane; h <= i - 6; h += 64) {
             const double x = tb.co(h, j + 1);
             if (x != 0.0) a += x * wcl[(pair_type(S[h], S[j + 1]) * 5 + S[j]) * 5 + S[h + 1]] * tb.m(h + 1, i - 1);
         }
     double m1o = mo + pf_wave_sum(a);
-    if (j + 1 < L) m1o += pb[1] * tb.m1o(i, j + 1);
+    if (j + 1 < L && tb.has(i, j + 1)) m1o += pb[1] * tb.m1o(i, j + 1);
     double co = 0.0;
     const int t = pair_type(S[i], S[j]);
     if (t) {
         a = 0.0;
-        if (lane == 0) a = gF[i] * pf_w(mfe_stem_ext(T, S, L, i, j), beta) * gFr[j + 1] + pf_w(mfe_stem_ml(T, S, L, i, j), beta) * m1o;
+        if (lane == 0) a = ex(i, j, pf_w(mfe_stem_ext(T, S, L, i, j), beta)) + pf_w(mfe_stem_ml(T, S, L, i, j), beta) * m1o;
         for (int x = lane; x < MFE_NIL; x += 64) {
             const int n12 = mfe_il.v[x], n1 = n12 >> 8, n2 = n12 & 255, p = i - 1 - n1, q = j + 1 + n2;
-            if (p < 0 || q >= L) continue;
+            if (p < 0 || q >= L || !tb.has(p, q)) continue;
             const int t2 = pair_type(S[p], S[q]);
             if (!t2) continue;
             const double cc = tb.co(p, q);
@@ -237,14 +264,11 @@ __global__ __launch_bounds__(PF_NT) void pf_out_diag_kernel(const EnergyTables *
     if (d >= L) return;
     const double *ps = aux + q.aux_off, *pb = ps + L + 1, *gF = pb + L + 1, *gFr = gF + L + 1;
     const SmallT *T = &ET->s;
-    for (int x = threadIdx.x; x < PF_NCLOSE; x += PF_NT) {
-        const int t = x / 25;
-        wcl[x] = t ? pf_w(T->ml_closing + e_stem(T, rtype(t), (x / 5) % 5, x % 5, false), beta) * ps[2] : 0.0;
-    }
-    __syncthreads();
+    pf_fill_wcl(wcl, T, beta, ps[2]);
     const PfTab tb = pf_tab(tabs + q.tab_off, L);
     const uint8_t *S = codes + q.code_off;
-    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, T, &ET->b, S, L, ps, pb, gF, gFr, wcl, beta, i, i + d, lane);
+    const PfExtPlain ex{gF, gFr};
+    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
 }
 
 // P(i,j) into the Co table, which then has the shape of the caller's buffer (0 below j - i = 4 and below the diagonal), and the

@@ -17,11 +17,14 @@ from .utils import structures_from_rows
 class PfResult:
     """energy: ensemble free energy -kT ln Z in kcal/mol; centroid: the dot-bracket row of the pairs with P > 0.5; mfe_frequency:
     the share of the MFE structure in the ensemble; mfe_energy: that structure's energy in kcal/mol; probs: L x L numpy array,
-    P(i pairs j) at [i][j] for i < j (None when not asked for).  str_struct: the centroid, so that the scorers take it as a row."""
-    __slots__ = ("energy", "centroid", "mfe_frequency", "mfe_energy", "probs")
+    P(i pairs j) at [i][j] for i < j (None when not asked for; from pf_span_batch it is banded, shape (L, W), P(i, i+d) at [i][d]);
+    unpaired: numpy array of the L unpaired probabilities (pf_span_batch; else None).  str_struct: the centroid, so that the scorers
+    take it as a row."""
+    __slots__ = ("energy", "centroid", "mfe_frequency", "mfe_energy", "probs", "unpaired")
 
-    def __init__(self, energy, centroid, mfe_frequency, mfe_energy, probs=None):
+    def __init__(self, energy, centroid, mfe_frequency, mfe_energy, probs=None, unpaired=None):
         self.energy, self.centroid, self.mfe_frequency, self.mfe_energy, self.probs = energy, centroid, mfe_frequency, mfe_energy, probs
+        self.unpaired = unpaired
 
     @property
     def str_struct(self):
@@ -67,6 +70,78 @@ def pf_batch(sequences, temp=37.0, probs=True, raise_errors=True):
 
 def pf(sequence, temp=37.0, probs=True):
     return pf_batch([sequence], temp, probs)[0]
+
+
+# ---- under a base-pair span (rafft_pf_span_batch)
+
+def pf_span_batch_raw(sequences, max_span, temp=37.0, scale_factor=0.0, workspace_bytes=0, probs=True, unpaired=True):
+    """(rows, records, probs, unpaired) of rafft_pf_span_batch: the centroid rows, one dict per sequence with the fields of
+    rafft_pf_seq (mfe_dcal: the span MFE), with probs=True one BANDED (L, W) numpy array per sequence, W = min(max_span, L), P(i, i+d)
+    at [i][d] (None for a sequence longer than RAFFT_MFE_SPAN_MAX_LEN), and with unpaired=True one array of L unpaired
+    probabilities per sequence (None likewise); nothing is raised for a sequence's own error (its row is all dots, its numbers are
+    0)."""
+    L = N.lib()
+    _params_mod.ensure_default_params()
+    n, max_span = len(sequences), int(max_span)
+    enc, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
+    rec = (N.PfSeq * n)()
+    fits = [len(e) <= N.MFE_SPAN_MAX_LEN for e in enc]
+    width = max(1, min(max_span, N.MFE_MAX_LEN))       # (an argument the library refuses gets buffers of a legal shape)
+    pr = ptrs = un = uptrs = None
+    if probs:
+        pr = [np.zeros((len(e), min(width, len(e))), dtype=np.float64) if ok else None for e, ok in zip(enc, fits)]
+        ptrs = (C.c_void_p * n)(*[p.ctypes.data if p is not None and p.size else None for p in pr])
+    if unpaired:
+        un = [np.zeros(len(e), dtype=np.float64) if ok else None for e, ok in zip(enc, fits)]
+        uptrs = (C.c_void_p * n)(*[u.ctypes.data if u is not None and u.size else None for u in un])
+    N.check(L.rafft_pf_span_batch(n, arr, lens, float(temp), float(scale_factor), max_span, int(workspace_bytes), rec, out, ptrs, uptrs))
+    recs = [{k: getattr(r, k) for k, _ in N.PfSeq._fields_} for r in rec]
+    return [b.value.decode("ascii") for b in bufs], recs, pr, un
+
+
+def pf_span_batch(sequences, max_span, temp=37.0, probs=True, raise_errors=True):
+    """The ensemble of every sequence under `max_span`, as a list of PfResult whose probs are banded, shape (L, W), and which
+    hold `unpaired`.  A sequence with an error raises what fold_batch raises for it (raise_errors=False: its entry is None)."""
+    rows, recs, pr, un = pf_span_batch_raw(sequences, max_span, temp, probs=probs)
+    out = []
+    for k, s in enumerate(sequences):
+        st = recs[k]["status"]
+        if st != N.OK:
+            if raise_errors:
+                raise_for_status(st, s, k, "pf_span_batch", "RAFFT_MFE_SPAN_MAX_LEN", "the scaled partition function left the fp64 range")
+            out.append(None)
+        else:
+            out.append(PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None, un[k]))
+    return out
+
+
+def pf_span(sequence, max_span, temp=37.0, probs=True):
+    return pf_span_batch([sequence], max_span, temp, probs)[0]
+
+
+def band_to_dense(band):
+    """The L x L matrix of a banded (L, W) array: band[i][d] at [i][i + d] (for short sequences: L x L doubles)"""
+    band = np.asarray(band)
+    L, W = band.shape
+    dense = np.zeros((L, L), dtype=band.dtype)
+    for d in range(min(W, L)):
+        dense[np.arange(L - d), np.arange(d, L)] = band[:L - d, d]
+    return dense
+
+
+def band_pairs(band, cutoff=1e-5):
+    """[(i, j, p)] of the pairs with p >= cutoff in a banded (L, W) array, 0-based, i ascending then j"""
+    band = np.asarray(band)
+    L = band.shape[0]
+    i, d = np.nonzero(band >= cutoff)                  # row-major: i ascending, then d
+    keep = i + d < L
+    return [(int(a), int(a + b), float(band[a, b])) for a, b in zip(i[keep], d[keep])]
+
+
+def dense_pairs(dense, cutoff=1e-5):
+    """band_pairs for an L x L matrix (P at [i][j], i < j)"""
+    i, j = np.nonzero(np.triu(np.asarray(dense), 1) >= cutoff)
+    return [(int(a), int(b), float(dense[a, b])) for a, b in zip(i, j)]
 
 
 def _seeds_of(seeds, n):
