@@ -1,21 +1,32 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
-// workspace budget: kin_batch (folding kinetics of many graphs), mfe_batch (minimum-free-energy folds), mfe_span_batch (the same under a base-pair span, to 32768 nt), pf_span_batch (partition function and pair probabilities under a span, to 32768 nt), pf_batch (partition
-// function and pair probabilities), mea_batch and mea_probs_batch (maximum-expected-accuracy structures), sample_batch (structures drawn from the ensemble), subopt_batch (every structure within an
-// energy band), findpath_batch (folding barriers between structure pairs) descend_batch (gradient walks to local minima), barriers_batch (exact barrier trees of energy bands) and kinfold_batch (stochastic folding trajectories), with their *_WORKSPACE budgets.  What they plan without the device - the chunks, the sequence pack, the graph
-// pack, the solve order of a chunk, and for the four sequence drivers every offset their kernels dereference (mfe_layout, pf_layout,
-// sample_layout, subopt_layout) - is in rafft_hostpure.h, where the CPU suite checks it: here are the allocations, the copies and
-// the launches.  The sequence drivers share their opening (SeqCall) and their view of a chunk (ChunkView).
+// workspace budget (workspace_budget).  Thirteen of them:
+//   kin_batch                    folding kinetics of many graphs
+//   mfe_batch, mfe_span_batch    minimum-free-energy folds; the same under a base-pair span, to 32768 nt
+//   pf_batch, pf_span_batch      partition function and pair probabilities; the same under a span, to 32768 nt
+//   mea_batch, mea_probs_batch   maximum-expected-accuracy structures, of sequences and of given probabilities
+//   sample_batch                 structures drawn from the ensemble
+//   subopt_batch                 every structure within an energy band
+//   findpath_batch               folding barriers between structure pairs
+//   descend_batch, barriers_batch, kinfold_batch    the row drivers: gradient walks to local minima, exact barrier trees of
+//                                energy bands, stochastic folding trajectories
+// What they plan without the device - the chunks, the sequence pack, the graph pack, the solve order of a chunk, the scale of a
+// partition function, and every offset their kernels dereference (the *_layout functions) - is in rafft_hostpure.h, where the CPU
+// suite checks it: here are the allocations, the copies and the launches.  The drivers that take sequences share their opening
+// (SeqCall) and their view of a chunk (ChunkView); the fold drivers also share the MFE of a pack under the caller's guard
+// (mfe_held, mfe_span_held) and their tails (mfe_results, pf_results).
 // Part of the single translation unit of rafft_api.hip (included there, after rafft_seam.h, whose SeamGuard and DevScratch they use).
 #pragma once
 
 namespace {
 
+// the workspace budget of a call: its workspace_bytes, or the default of every batch call when that is 0
+constexpr size_t DEFAULT_WORKSPACE = (size_t)512 << 20;
+size_t workspace_budget(long long workspace_bytes) { return workspace_bytes > 0 ? (size_t)workspace_bytes : DEFAULT_WORKSPACE; }
+
 // ---- kinetics of a batch of graphs
 
 // rafft_kin_batch (arguments validated by the entry point).  Two passes over the device: structure identity for every graph, then -
 // the numbers of unique structures being known - rates and integration for chunks of graphs whose matrices fit the workspace budget.
-constexpr size_t KIN_BATCH_WORKSPACE = (size_t)512 << 20;
-
 int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *const *step_size, const char *const *rows, const int *row_stride,
               const double *const *energy, double kt, int n_times, const int *m, const double *h, long long workspace_bytes,
               rafft_kin_graph *rec, int *uid_out, int *first_row_out, double *pop_out, double *const *rate_out)
@@ -104,7 +115,7 @@ int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *cons
         for (int r = 0; r < G.n_rows; r++) uid_out[G.row0 + r] = first_row_out[G.row0 + r] = -1;
     }
     // chunks of consecutive graphs: three S x S blocks per graph and the populations of the chunk within the budget (one graph at least)
-    const size_t budget = workspace_bytes > 0 ? (size_t)workspace_bytes : KIN_BATCH_WORKSPACE;
+    const size_t budget = workspace_budget(workspace_bytes);
     std::vector<int> S(n_graphs);
     std::vector<size_t> mat_bytes(n_graphs), pop_bytes(n_graphs);
     for (int g = 0; g < n_graphs; g++) {
@@ -164,7 +175,7 @@ int kin_batch(int n_graphs, const int *lens, const int *n_steps, const int *cons
     return 0;
 }
 
-// ---- what the four sequence drivers share
+// ---- what the drivers that take sequences share
 
 // as the fold's entry (validate_params): before any sequence is looked at, so a batch of nothing but erroneous sequences fails too
 int check_temp(double temp)
@@ -217,8 +228,6 @@ void pf_left_range(int s, int &status, std::string &err, void *zero, size_t byte
 
 // ---- minimum-free-energy folds
 
-constexpr size_t MFE_WORKSPACE = (size_t)512 << 20;
-
 // The HBM-class tables of a chunk (its sequences' numbers in d_qs): one launch per anti-diagonal, stream order being the
 // synchronisation.  mfe_held and subopt_batch fill their tables through this.
 int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const ChunkView &v, const uint8_t *d_codes, int *d_ws)
@@ -231,6 +240,27 @@ int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const ChunkView &v, const
     return 0;
 }
 
+// What mfe_held and mfe_span_held end with: the tracebacks' records and the n_db bytes of rows come down, one synchronise, and
+// every sequence without an error gets its dcal, its n_pairs and - db_out may be null (no rows wanted) - its row.
+template <class Seq>
+int mfe_results(hipStream_t st, const std::vector<Seq> &qs, const int4 *d_rec, const char *d_db, unsigned long long n_db, rafft_mfe_seq *seq_out,
+                char *const *db_out)
+{
+    const int n_seq = (int)qs.size();
+    std::vector<int4> rec(n_seq);
+    std::vector<char> db(n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
+        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
+        if (db_out) memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    return 0;
+}
+
 // The MFE folds of a pack, under the caller's guard: the device tables are scaled for the call's temp, d_codes is the device copy
 // of pk.codes, seq_out[s].status is set.  Sequences up to `lds_len` go through mfe_lds_kernel in one launch, the others through
 // the HBM class in chunks whose tables fit the workspace budget (one sequence at least; mfe_layout): per chunk one launch per
@@ -238,8 +268,7 @@ int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const ChunkView &v, const
 // rows wanted).
 int mfe_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, int lds_len, long long workspace_bytes, rafft_mfe_seq *seq_out, char *const *db_out)
 {
-    const int n_seq = (int)pk.L.size();
-    const MfeLayout y = mfe_layout(pk, lds_len, workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE);
+    const MfeLayout y = mfe_layout(pk, lds_len, workspace_budget(workspace_bytes));
     const std::vector<MfeSeq> &qs = y.qs;
     DevScratch mem;
     MfeSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr;
@@ -264,18 +293,7 @@ int mfe_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, int lds_
         hipLaunchKernelGGL(mfe_traceback_kernel, dim3(v.ny), dim3(64), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d_stack, d_db, d_rec);
         HIPCHK(hipGetLastError());
     }
-    std::vector<int4> rec(n_seq);
-    std::vector<char> db(y.n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int s = 0; s < n_seq; s++) {
-        if (seq_out[s].status) continue;
-        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
-        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
-        if (db_out) memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
-    }
-    return 0;
+    return mfe_results(st, qs, d_rec, d_db, y.n_db, seq_out, db_out);
 }
 
 // rafft_mfe_batch (arguments validated by the entry point)
@@ -301,27 +319,16 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
 
 // ---- minimum-free-energy folds under a base-pair span
 
-// rafft_mfe_span_batch (arguments validated by the entry point).  Chunks of whole sequences in input order whose banded tables fit
-// the workspace budget (one sequence at least; mfe_span_layout): per chunk one launch per anti-diagonal of its widest band, then
-// the exterior loop and the traceback, a wavefront a sequence each.  One synchronise at the end.
-int mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int max_span, long long workspace_bytes, rafft_mfe_seq *seq_out,
-                   char *const *db_out)
+// The MFE folds of a pack under a base-pair span, under the caller's guard as mfe_held: seq_out[s].status is set, db_out may be
+// null.  Chunks of whole sequences in input order whose banded tables fit the workspace budget (one sequence at least;
+// mfe_span_layout): per chunk one launch per anti-diagonal of its widest band, then the exterior loop and the traceback, a
+// wavefront a sequence each.  One synchronise at the end; its device buffers are freed on return.
+int mfe_span_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, int max_span, long long workspace_bytes, rafft_mfe_seq *seq_out,
+                  char *const *db_out)
 {
-    if (int rc = check_temp(temp)) return rc;
-    if (n_seq == 0) return 0;
-    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_SPAN_MAX_LEN, "RAFFT_MFE_SPAN_MAX_LEN");
-    for (int s = 0; s < n_seq; s++) {
-        seq_out[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
-        dot_row(db_out[s], pk.len[s]);
-    }
-    g_err = pk.first_err;
-    if (pk.fold.empty()) return 0;
-    SeqCall sc;
-    DevScratch mem;
-    if (int rc = sc.open(mem, pk, temp)) return rc;
-    hipStream_t st = sc.st;
-    const MfeSpanLayout y = mfe_span_layout(pk, max_span, workspace_bytes > 0 ? (size_t)workspace_bytes : MFE_WORKSPACE);
+    const MfeSpanLayout y = mfe_span_layout(pk, max_span, workspace_budget(workspace_bytes));
     const std::vector<MfeSpanSeq> &qs = y.qs;
+    DevScratch mem;
     MfeSpanSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_f, *d_ws;
     if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSpanSeq))) return rc;
     if (int rc = mem.alloc(d_f, y.n_f * 4 + 16)) return rc;
@@ -337,36 +344,43 @@ int mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, double t
     HIPCHK(hipFuncSetAttribute((const void *)mfe_span_traceback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mfe_span_lds_bytes(RAFFT_MFE_SPAN_MAX_LEN)));
     for (const ChunkPlan::Range &c : y.plan.chunks) {
         const ChunkView v = chunk_view(c, d_order, pk.fold, pk);
-        const int Wmax = mfe_span_chunk_wmax(c, pk.fold, qs);
+        const int Wmax = chunk_wmax(c, pk.fold, qs);
         for (int d = 0; d < Wmax; d++) {
             const unsigned nx = (unsigned)std::min((v.Lmax - d + MFE_SPAN_NT / 64 - 1) / (MFE_SPAN_NT / 64), 2048);
-            hipLaunchKernelGGL(mfe_span_diag_kernel, dim3(nx, v.ny), dim3(MFE_SPAN_NT), 0, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d);
+            hipLaunchKernelGGL(mfe_span_diag_kernel, dim3(nx, v.ny), dim3(MFE_SPAN_NT), 0, st, g.T, d_qs, v.ord, d_codes, d_ws, d);
         }
         HIPCHK(hipGetLastError());
         const size_t lds = (size_t)mfe_span_lds_bytes(v.Lmax);
         hipLaunchKernelGGL(mfe_span_exterior_kernel, dim3(v.ny), dim3(64), lds, st, d_qs, v.ord, d_ws, d_f);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(mfe_span_traceback_kernel, dim3(v.ny), dim3(64), lds, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d_f, d_stack, d_db, d_rec);
+        hipLaunchKernelGGL(mfe_span_traceback_kernel, dim3(v.ny), dim3(64), lds, st, g.T, d_qs, v.ord, d_codes, d_ws, d_f, d_stack, d_db, d_rec);
         HIPCHK(hipGetLastError());
     }
-    std::vector<int4> rec(n_seq);
-    std::vector<char> db(y.n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    return mfe_results(st, qs, d_rec, d_db, y.n_db, seq_out, db_out);
+}
+
+// rafft_mfe_span_batch (arguments validated by the entry point)
+int mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int max_span, long long workspace_bytes, rafft_mfe_seq *seq_out,
+                   char *const *db_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_SPAN_MAX_LEN, "RAFFT_MFE_SPAN_MAX_LEN");
     for (int s = 0; s < n_seq; s++) {
-        if (seq_out[s].status) continue;
-        if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
-        seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
-        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+        seq_out[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+        dot_row(db_out[s], pk.len[s]);
     }
+    g_err = pk.first_err;
+    if (pk.fold.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    if (int rc = mfe_span_held(sc.st, pk, sc.d_codes, max_span, workspace_bytes, seq_out, db_out)) return rc;
     g_err = pk.first_err;
     return 0;
 }
 
 // ---- partition function and pair probabilities
-
-constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
 
 // The front rafft_pf_batch and rafft_sample_batch share, under the caller's SeqCall: the MFE of every sequence (mfe_held: its energy
 // gives the scale; its device buffers are freed before the tables here are allocated), the scales and their powers, and the plan of
@@ -374,7 +388,7 @@ constexpr size_t PF_WORKSPACE = (size_t)512 << 20;
 // workspace budget (one sequence at least; pf_layout).  Then, per chunk, pf_front_inside: one launch per anti-diagonal upwards and
 // the exterior sums.  The buffers live in the caller's DevScratch.
 struct PfFront {
-    double kt, beta;
+    PfTemp t;
     std::vector<rafft_mfe_seq> mfe;
     std::vector<PfSeq> qs;
     ChunkPlan plan;
@@ -392,14 +406,9 @@ int pf_front(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp,
     f.mfe.resize(n_seq);
     for (int s = 0; s < n_seq; s++) f.mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
     if (int rc = mfe_held(st, pk, f.d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, f.mfe.data(), nullptr)) return rc;
-    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
-    f.kt = kt; f.beta = beta;
-    PfLayout y = pf_layout(pk, n_tabs, cost2, workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE);
-    for (int s = 0; s < n_seq; s++) {
-        PfSeq &q = y.qs[s];
-        const double ln_scale = q.L ? -sf * ((double)f.mfe[s].dcal / 100.0) / (kt * (double)q.L) : 0.0;
-        q.mfe_dcal = f.mfe[s].dcal; q.scale = std::exp(ln_scale); q.ln_scale = std::log(q.scale);
-    }
+    f.t = pf_temp(temp);
+    PfLayout y = pf_layout(pk, n_tabs, cost2, workspace_budget(workspace_bytes));
+    for (int s = 0; s < n_seq; s++) pf_set_scale(y.qs[s], f.mfe[s].dcal, f.t.kt, scale_factor);
     f.qs = std::move(y.qs); f.plan = std::move(y.plan); f.n_db = y.n_db;
     const std::vector<PfSeq> &qs = f.qs;
     if (int rc = mem.alloc(f.d_qs, qs.size() * sizeof(PfSeq))) return rc;
@@ -411,7 +420,7 @@ int pf_front(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp,
     HIPCHK(hipMemcpyAsync(f.d_qs, qs.data(), qs.size() * sizeof(PfSeq), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(f.d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(f.d_rec, 0, qs.size() * sizeof(PfRec), st));
-    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, f.d_qs, n_seq, f.d_aux, beta);
+    hipLaunchKernelGGL(pf_powers_kernel, dim3((unsigned)((n_seq + 63) / 64)), dim3(64), 0, st, g.T, f.d_qs, n_seq, f.d_aux, f.t.beta);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -423,9 +432,9 @@ unsigned pf_diag_blocks(int Lmax, int d) { return (unsigned)std::min((Lmax - d +
 int pf_front_inside(hipStream_t st, const PfFront &f, const ChunkView &v)
 {
     for (int d = 0; d < v.Lmax; d++)
-        hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
+        hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, d);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(pf_exterior_kernel, dim3(v.ny), dim3(64), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, f.kt, f.d_db, f.d_rec);
+    hipLaunchKernelGGL(pf_exterior_kernel, dim3(v.ny), dim3(64), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, f.t.kt, f.d_db, f.d_rec);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -436,7 +445,7 @@ int pf_front_inside(hipStream_t st, const PfFront &f, const ChunkView &v)
 int pf_outside_probs(hipStream_t st, const PfFront &f, const ChunkView &v, const ChunkPlan::Range &c, const std::vector<int> &order, double *const *prob_out)
 {
     for (int d = v.Lmax - 1; d >= 4; d--)
-        hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, d);
+        hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, d);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
     HIPCHK(hipGetLastError());
@@ -446,6 +455,36 @@ int pf_outside_probs(hipStream_t st, const PfFront &f, const ChunkView &v, const
             if (prob_out[order[k]])
                 HIPCHK(hipMemcpyAsync(prob_out[order[k]], f.d_ws + q.tab_off + 3 * (size_t)q.L * q.L, (size_t)q.L * q.L * sizeof(double), hipMemcpyDeviceToHost, st));
         }
+    return 0;
+}
+
+// What pf_batch and pf_span_batch end with: the records and the n_db bytes of centroid rows come down, one synchronise.  A
+// sequence whose tables left the fp64 range takes pf_left_range, and zero_numbers(s) zeroes what the caller was given for its
+// numbers; every other one without an error gets n_pairs, energy, mfe_frequency and its row.  Sets the call's error text.
+template <class Seq, class Zero>
+int pf_results(hipStream_t st, const SeqPack &pk, const std::vector<Seq> &qs, const PfRec *d_rec, const char *d_db, unsigned long long n_db,
+               rafft_pf_seq *seq_out, char *const *db_out, Zero zero_numbers)
+{
+    const int n_seq = (int)qs.size();
+    std::vector<PfRec> rec(n_seq);
+    std::vector<char> db(n_db + 16);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(db.data(), d_db, n_db, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::string err = pk.first_err;
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_out[s].status) continue;
+        if (rec[s].status || rec[s].bad) {
+            pf_left_range(s, seq_out[s].status, err, nullptr, 0);
+            zero_numbers(s);
+            continue;
+        }
+        seq_out[s].n_pairs = rec[s].n_pairs;
+        seq_out[s].energy = rec[s].energy;
+        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
+        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
+    }
+    g_err = err;
     return 0;
 }
 
@@ -480,34 +519,19 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
         if (int rc = pf_front_inside(st, f, v)) return rc;
         if (int rc = pf_outside_probs(st, f, v, c, order, prob_out)) return rc;
     }
-    std::vector<PfRec> rec(n_seq);
-    std::vector<char> db(f.n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), f.d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), f.d_db, f.n_db, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::string err = pk.first_err;
-    for (int s = 0; s < n_seq; s++) {
-        if (seq_out[s].status) continue;
-        if (rec[s].status || rec[s].bad) {
-            pf_left_range(s, seq_out[s].status, err, prob_out ? prob_out[s] : nullptr, (size_t)qs[s].L * qs[s].L * sizeof(double));
-            continue;
-        }
-        seq_out[s].n_pairs = rec[s].n_pairs;
-        seq_out[s].energy = rec[s].energy;
-        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
-        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
-    }
-    g_err = err;
-    return 0;
+    return pf_results(st, pk, qs, f.d_rec, f.d_db, f.n_db, seq_out, db_out, [&](int s) {
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)qs[s].L * qs[s].L * sizeof(double));
+    });
 }
 
 // ---- partition function and pair probabilities under a base-pair span
 
-// rafft_pf_span_batch (arguments validated by the entry point).  mfe_span_batch first, as any caller runs it: its energies give the
-// scales and the mfe_dcal of the records.  Then one guard and one upload of the bases; chunks of whole sequences in input order
-// whose banded tables fit the workspace budget (one sequence at least; pf_span_layout); per chunk one launch per anti-diagonal of
-// its widest band upwards, the exterior sums, one launch per anti-diagonal downwards, the probabilities, and the copies of P and
-// of unpaired the caller asked for.  One synchronise at the end.
+// rafft_pf_span_batch (arguments validated by the entry point).  One pack, one guard, one upload of the bases.  The span MFE of
+// every sequence first (mfe_span_held: its energies give the scales and the mfe_dcal of the records; its device buffers are freed
+// before the tables here are allocated).  Then chunks of whole sequences in input order whose banded tables fit the workspace
+// budget (one sequence at least; pf_span_layout); per chunk one launch per anti-diagonal of its widest band upwards, the exterior
+// sums, one launch per anti-diagonal downwards, the probabilities, and the copies of P and of unpaired the caller asked for.  One
+// synchronise at the end.
 int pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, int max_span, long long workspace_bytes,
                   rafft_pf_seq *seq_out, char *const *db_out, double *const *prob_out, double *const *unpaired_out)
 {
@@ -525,27 +549,17 @@ int pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double te
     g_err = pk.first_err;
     const std::vector<int> &order = pk.fold;
     if (order.empty()) return 0;
-    std::vector<rafft_mfe_seq> mfe(n_seq);
-    {
-        std::vector<char> rows;
-        std::vector<char *> row_ptr(n_seq);
-        size_t at = 0;
-        for (int s = 0; s < n_seq; s++) at += (size_t)pk.len[s] + 1;
-        rows.resize(at);
-        at = 0;
-        for (int s = 0; s < n_seq; s++) { row_ptr[s] = rows.data() + at; at += (size_t)pk.len[s] + 1; }
-        if (int rc = mfe_span_batch(n_seq, seqs, lens, temp, max_span, workspace_bytes, mfe.data(), row_ptr.data())) return rc;
-    }
     SeqCall sc;
     DevScratch mem;
     if (int rc = sc.open(mem, pk, temp)) return rc;
     hipStream_t st = sc.st;
-    const double kt = (temp + 273.15) * PF_GAS, beta = 1.0 / (100.0 * kt), sf = scale_factor > 0.0 ? scale_factor : 1.07;
-    PfSpanLayout y = pf_span_layout(pk, max_span, workspace_bytes > 0 ? (size_t)workspace_bytes : PF_WORKSPACE);
+    std::vector<rafft_mfe_seq> mfe(n_seq);
+    for (int s = 0; s < n_seq; s++) mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+    if (int rc = mfe_span_held(st, pk, sc.d_codes, max_span, workspace_bytes, mfe.data(), nullptr)) return rc;
+    const auto [kt, beta] = pf_temp(temp);
+    PfSpanLayout y = pf_span_layout(pk, max_span, workspace_budget(workspace_bytes));
     for (int s = 0; s < n_seq; s++) {
-        PfSpanSeq &q = y.qs[s];
-        const double ln_scale = q.L ? -sf * ((double)mfe[s].dcal / 100.0) / (kt * (double)q.L) : 0.0;
-        q.mfe_dcal = mfe[s].dcal; q.scale = std::exp(ln_scale); q.ln_scale = std::log(q.scale);
+        pf_set_scale(y.qs[s], mfe[s].dcal, kt, scale_factor);
         seq_out[s].mfe_dcal = mfe[s].dcal;
     }
     const std::vector<PfSpanSeq> &qs = y.qs;
@@ -564,7 +578,7 @@ int pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double te
     HIPCHK(hipGetLastError());
     for (const ChunkPlan::Range &c : y.plan.chunks) {
         const ChunkView v = chunk_view(c, d_order, order, pk);
-        const int Wmax = pf_span_chunk_wmax(c, order, qs);
+        const int Wmax = chunk_wmax(c, order, qs);
         for (int d = 0; d < Wmax; d++)
             hipLaunchKernelGGL(pf_span_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, d_qs, v.ord, sc.d_codes, d_ws, d_aux, beta, d);
         HIPCHK(hipGetLastError());
@@ -584,31 +598,14 @@ int pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double te
                 HIPCHK(hipMemcpyAsync(unpaired_out[s], d_aux + q.aux_off + 2 * ((size_t)q.W + 2) + 2 * ((size_t)q.L + 1), (size_t)q.L * sizeof(double), hipMemcpyDeviceToHost, st));
         }
     }
-    std::vector<PfRec> rec(n_seq);
-    std::vector<char> db(y.n_db + 16);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, qs.size() * sizeof(PfRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db.data(), d_db, y.n_db, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::string err = pk.first_err;
-    for (int s = 0; s < n_seq; s++) {
-        if (seq_out[s].status) continue;
-        if (rec[s].status || rec[s].bad) {
-            pf_left_range(s, seq_out[s].status, err, prob_out ? prob_out[s] : nullptr, (size_t)pf_span_table_doubles(qs[s].L, qs[s].W) * sizeof(double));
-            if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, (size_t)qs[s].L * sizeof(double));
-            continue;
-        }
-        seq_out[s].n_pairs = rec[s].n_pairs;
-        seq_out[s].energy = rec[s].energy;
-        seq_out[s].mfe_frequency = rec[s].mfe_frequency;
-        memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
-    }
-    g_err = err;
-    return 0;
+    return pf_results(st, pk, qs, d_rec, d_db, y.n_db, seq_out, db_out, [&](int s) {
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)pf_span_table_doubles(qs[s].L, qs[s].W) * sizeof(double));
+        if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, (size_t)qs[s].L * sizeof(double));
+    });
 }
 
 // ---- maximum-expected-accuracy structures
 
-constexpr size_t MEA_WORKSPACE = (size_t)512 << 20;
 static_assert(MEA_NT == PF_NT, "pf_diag_blocks counts the workgroups of mea_diag_kernel too");
 
 // The recursion on the P tables of chunk v: q, WT and the diversity's shares, one launch per anti-diagonal upwards, the traceback.
@@ -634,6 +631,7 @@ int mea_bad(int s, int bad)
 // rafft_mea_batch (arguments validated by the entry point; gamma > 0).  rafft_pf_batch's call - the shared front, per chunk the
 // inside pass, the outside pass and the probabilities - and then, per chunk, mea_chunk on table 3 with WT, E and ET in the dead
 // tables 0, 1, 2 (mea_layout), and one eval_kernel launch on the pair tables the traceback left.  One synchronise at the end.
+// Its tail is its own: it fills rafft_mea_seq from three record arrays, where pf_results fills rafft_pf_seq from one.
 int mea_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, long long workspace_bytes, double gamma,
               rafft_mea_seq *seq_out, char *const *db_out, double *const *prob_out, double *const *unpaired_out)
 {
@@ -728,7 +726,7 @@ int mea_probs_batch(int n, const int *lens, const double *const *prob_in, double
                     char *const *db_out, double *const *unpaired_out)
 {
     if (n == 0) return 0;
-    const MeaProbsLayout y = mea_probs_layout(n, lens, workspace_bytes > 0 ? (size_t)workspace_bytes : MEA_WORKSPACE);
+    const MeaProbsLayout y = mea_probs_layout(n, lens, workspace_budget(workspace_bytes));
     for (int s : y.order) {
         int bi = 0, bj = 0;
         const char *why = nullptr;
@@ -832,7 +830,7 @@ int sample_batch(int n_seq, const char *const *seqs, const int *lens, double tem
         if (int rc = pf_front_inside(st, f, v)) return rc;
         if (n_samples > 0) {
             hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n_samples + SAMPLE_NT / 64 - 1) / (SAMPLE_NT / 64)), v.ny), dim3(SAMPLE_NT),
-                               (size_t)sample_lds_bytes(v.Lmax), st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.beta, f.d_rec, d_smp, n_samples,
+                               (size_t)sample_lds_bytes(v.Lmax), st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, f.d_rec, d_smp, n_samples,
                                v.Lmax, d_rows, d_dcal, d_bad);
             HIPCHK(hipGetLastError());
         }
@@ -861,7 +859,6 @@ int sample_batch(int n_seq, const char *const *seqs, const int *lens, double tem
 
 // ---- every structure within an energy band
 
-constexpr size_t SUBOPT_WORKSPACE = (size_t)512 << 20;
 constexpr int SUBOPT_POLL_LEVELS = 8;       // levels between two reads of the chunk's "sequences that go on" word
 
 // what a rafft_subopt_result points into; rafft_subopt_free deletes it
@@ -912,7 +909,7 @@ int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double tem
     if (int rc = sc.open(mem, pk, temp)) return rc;
     hipStream_t st = sc.st;
     const uint8_t *d_codes = sc.d_codes;
-    const SuboptLayout y = subopt_layout(pk, max_structs, workspace_bytes > 0 ? (size_t)workspace_bytes : SUBOPT_WORKSPACE);
+    const SuboptLayout y = subopt_layout(pk, max_structs, workspace_budget(workspace_bytes));
     const std::vector<SuboptSeq> &qs = y.qs;
     const ChunkPlan &plan = y.plan;
     MfeSeq *d_mq; SuboptSeq *d_qs; SuboptRec *d_rec; int *d_order, *d_ws, *d_f, *d_open; unsigned char *d_front;
@@ -1011,8 +1008,6 @@ int subopt_batch(int n_seq, const char *const *seqs, const int *lens, double tem
 
 // ---- folding barriers between structure pairs
 
-constexpr size_t FINDPATH_WORKSPACE = (size_t)512 << 20;
-
 // of the last call: chunks, levels over all chunks, kernel launches, problems that ran
 long long g_findpath_counters[4];
 
@@ -1055,8 +1050,7 @@ int findpath_batch(int n_paths, const char *const *seqs, const int *lens, const 
     DevScratch mem;
     if (int rc = sc.open(mem, pk, temp)) return rc;
     hipStream_t st = sc.st;
-    const FpLayout y = findpath_layout(n_paths, run, pk.L.data(), d.data(), n_rem.data(), widths, pk.code_off.data(),
-                                       workspace_bytes > 0 ? (size_t)workspace_bytes : FINDPATH_WORKSPACE);
+    const FpLayout y = findpath_layout(n_paths, run, pk.L.data(), d.data(), n_rem.data(), widths, pk.code_off.data(), workspace_budget(workspace_bytes));
     FpProb *d_ps; FpRec *d_rec; int *d_order; unsigned char *d_in, *d_out, *d_ws;
     if (int rc = mem.alloc(d_ps, y.ps.size() * sizeof(FpProb))) return rc;
     if (int rc = mem.alloc(d_rec, y.ps.size() * sizeof(FpRec))) return rc;
@@ -1138,8 +1132,6 @@ static int restage_row(const SeqPack &pk, const char *const *rows, const int *ro
 
 // ---- gradient walks to local minima
 
-constexpr size_t DESCEND_WORKSPACE = (size_t)512 << 20;
-
 // of the last call: chunks, kernel launches, walks that ran, steps over all walks
 long long g_descend_counters[4];
 
@@ -1190,8 +1182,7 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
     DevScratch mem;
     if (int rc = sc.open(mem, pk, temp)) return rc;
     hipStream_t st = sc.st;
-    const DsLayout y = descend_layout(run.size(), wL.data(), wbound.data(), wcode.data(), wmoves.data(),
-                                      workspace_bytes > 0 ? (size_t)workspace_bytes : DESCEND_WORKSPACE);
+    const DsLayout y = descend_layout(run.size(), wL.data(), wbound.data(), wcode.data(), wmoves.data(), workspace_budget(workspace_bytes));
     DsWalk *d_ws; DsRec *d_rec; unsigned char *d_io, *d_mv = nullptr;
     if (int rc = mem.alloc(d_ws, run.size() * sizeof(DsWalk))) return rc;
     if (int rc = mem.alloc(d_rec, run.size() * sizeof(DsRec))) return rc;
@@ -1239,7 +1230,6 @@ int descend_batch(int n_seq, const char *const *seqs, const int *lens, const int
 
 // ---- exact barrier trees of energy bands
 
-constexpr size_t BARRIERS_WORKSPACE = (size_t)512 << 20;
 constexpr size_t BARRIERS_WORKSPACE_MAX = (size_t)64 << 30;        // (a chunk's rows are numbered in 31 bits: at 56 bytes a row and more, this holds them)
 
 // what a rafft_barriers_result points into; rafft_barriers_free deletes it
@@ -1268,7 +1258,7 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
     std::unique_ptr<BarriersOwner> own(new BarriersOwner);
     own->seq.resize(n_seq); own->minima.resize(n_seq); own->edges.resize(n_seq); own->basin.resize(n_seq);
     const SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_BARRIERS_MAX_LEN);
-    const size_t budget = std::min(workspace_bytes > 0 ? (size_t)workspace_bytes : BARRIERS_WORKSPACE, BARRIERS_WORKSPACE_MAX);
+    const size_t budget = std::min(workspace_budget(workspace_bytes), BARRIERS_WORKSPACE_MAX);
     FirstError err(pk);                 // (no items: every error is its sequence's)
     auto note = [&](int s, int status, const std::string &msg) {
         own->seq[s].status = status;
@@ -1434,8 +1424,6 @@ int barriers_batch(int n_seq, const char *const *seqs, const int *lens, const in
 
 // ---- stochastic folding trajectories
 
-constexpr size_t KINFOLD_WORKSPACE = (size_t)512 << 20;
-
 // of the last call: chunks, kernel launches, trajectories that ran, steps over all trajectories
 long long g_kinfold_counters[4];
 
@@ -1513,7 +1501,7 @@ int kinfold_batch(int n_seq, const char *const *seqs, const int *lens, const int
     if (int rc = sc.open(mem, pk, temp)) return rc;
     hipStream_t st = sc.st;
     const KfLayout y = kinfold_layout(run.size(), wL.data(), wk.data(), wcode.data(), wwt.data(), wseed.data(), wnw.data(), wns.data(), wlog.data(),
-                                      bound, n_times, workspace_bytes > 0 ? (size_t)workspace_bytes : KINFOLD_WORKSPACE);
+                                      bound, n_times, workspace_budget(workspace_bytes));
     KfTraj *d_ws; KfRec *d_rec; KfSample *d_smp; unsigned char *d_io, *d_log = nullptr;
     unsigned long long *d_wtab; double *d_times; int16_t *d_watch;
     if (int rc = mem.alloc(d_ws, run.size() * sizeof(KfTraj))) return rc;

@@ -1,7 +1,10 @@
-// rafft_batch_layout.h - what the host and the device of the sequence drivers must agree on: the per-sequence records the kernels
-// of rafft_mfe.hip, rafft_mfe_span.hip, rafft_pf.hip, rafft_pf_span.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip, rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides
-// compute (the LDS of the MFE and sampling kernels, a state of the enumeration, its packed copy, the buffers of a findpath problem and of a gradient walk, the work area of a barrier tree, the buffers of a folding trajectory).  The layouts that fill the records are in
-// rafft_hostpure.h.  Plain C++, no HIP include: g++ compiles it with tests/hostcheck/hostpure_check.cpp, hipcc with the kernels.
+// rafft_batch_layout.h - what the host and the device of the batch drivers must agree on: the per-item records the kernels of
+// rafft_mfe.hip, rafft_mfe_span.hip, rafft_pf.hip, rafft_pf_span.hip, rafft_mea.hip, rafft_sample.hip, rafft_subopt.hip,
+// rafft_findpath.hip, rafft_descend.hip, rafft_barriers.hip and rafft_kinfold.hip read and write, and the sizes both sides compute:
+// the LDS of the MFE and sampling kernels, the banded tables and aux arrays of the span folds, the aux and stack of an MEA
+// structure, a state of the enumeration and its packed copy, the buffers of a findpath problem and of a gradient walk, the work
+// area of a barrier tree, the buffers of a folding trajectory.  The layouts that fill the records are in rafft_hostpure.h.
+// Plain C++, no HIP include: g++ compiles it with the programs of tests/hostcheck, hipcc with the kernels.
 #pragma once
 
 #ifdef __HIPCC__

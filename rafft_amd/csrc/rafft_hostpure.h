@@ -1,9 +1,11 @@
 // rafft_hostpure.h - host helpers that need neither HIP nor the global context: base codes, the dot-bracket parsers, the loop
-// that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers
-// (chunks within a budget, the sequence pack, the graph pack, the solve order, the layouts of the four sequence drivers: every
-// offset their kernels dereference, as records of rafft_batch_layout.h - the moves, conflict masks and layout of findpath, the rows and layout of descend, the layout and the tree of barriers, the weight table, argument checks and layout of kinfold).
-// Plain C++ (g++ compiles it alone: tests/hostcheck/hostpure_check.cpp, findpath_check.cpp, descend_check.cpp, barriers_check.cpp, kinfold_check.cpp).  Part of the single translation unit
-// of rafft_api.hip (included there, before the kernels).
+// that encloses a region, the lane cut of a batch, the row layout of the scoring calls and the planning of the batch drivers of
+// rafft_batch.h: chunks within a budget, the sequence pack, the graph pack, the solve order, the scale of a partition function,
+// and the layouts - every offset the drivers' kernels dereference, as records of rafft_batch_layout.h - with, for the drivers
+// that need them, the moves and conflict masks of findpath, the row intake of descend, barriers and kinfold, the tree of
+// barriers, the weight table and argument checks of kinfold.
+// Plain C++ (g++ compiles it alone: the programs of tests/hostcheck).  Part of the single translation unit of rafft_api.hip
+// (included there, before the kernels).
 #pragma once
 
 #include "../../include/rafft_hip.h"
@@ -256,6 +258,27 @@ static int chunk_lmax(const ChunkPlan::Range &c, const std::vector<int> &order, 
     for (size_t k = c.a; k < c.b; k++) Lmax = std::max(Lmax, L[order[k]]);
     return Lmax;
 }
+// the widest band of the sequences order[a .. b) of a chunk of banded tables: the anti-diagonals its passes launch
+template <class Seq>
+static int chunk_wmax(const ChunkPlan::Range &c, const std::vector<int> &order, const std::vector<Seq> &qs)
+{
+    int Wmax = 0;
+    for (size_t k = c.a; k < c.b; k++) Wmax = std::max(Wmax, qs[order[k]].W);
+    return Wmax;
+}
+
+// What a layout of tables ends with.  The sequences of `order` own tab_bytes(record) bytes of tables each: the chunks of the order
+// within the budget (cost2: a second cost per sequence of the order, or null), and in every record tab_off, the first element of
+// the sequence's tables in its chunk's workspace, an element being `elem` bytes.
+template <class Seq, class TabBytes>
+static ChunkPlan plan_tables(const std::vector<int> &order, std::vector<Seq> &qs, TabBytes tab_bytes, size_t elem, const size_t *cost2, size_t budget)
+{
+    std::vector<size_t> cost(order.size());
+    for (size_t k = 0; k < order.size(); k++) cost[k] = tab_bytes(qs[order[k]]);
+    ChunkPlan plan = plan_chunks(order.size(), cost.data(), cost2, budget, 65535);
+    for (size_t k = 0; k < order.size(); k++) qs[order[k]].tab_off = plan.off[k] / elem;
+    return plan;
+}
 
 // rafft_mfe_batch: sequences up to lds_len in the LDS class, the longest first (the workgroups of a launch that run last are the
 // short ones), the others in the HBM class in input order, in chunks (plan: over hbm_order) of three L x L int32 tables a sequence;
@@ -279,10 +302,7 @@ static MfeLayout mfe_layout(const SeqPack &pk, int lds_len, size_t budget)
         (len <= lds_len ? y.lds_order : y.hbm_order).push_back(s);
     }
     std::stable_sort(y.lds_order.begin(), y.lds_order.end(), [&](int a, int b) { return pk.L[a] > pk.L[b]; });
-    std::vector<size_t> tab_bytes(y.hbm_order.size());
-    for (size_t k = 0; k < y.hbm_order.size(); k++) tab_bytes[k] = 3 * (size_t)pk.L[y.hbm_order[k]] * pk.L[y.hbm_order[k]] * 4;
-    y.plan = plan_chunks(y.hbm_order.size(), tab_bytes.data(), nullptr, budget, 65535);
-    for (size_t k = 0; k < y.hbm_order.size(); k++) y.qs[y.hbm_order[k]].tab_off = y.plan.off[k] / 4;
+    y.plan = plan_tables(y.hbm_order, y.qs, [](const MfeSeq &q) { return 3 * (size_t)q.L * q.L * 4; }, 4, nullptr, budget);
     y.order = y.lds_order;
     y.order.insert(y.order.end(), y.hbm_order.begin(), y.hbm_order.end());
     return y;
@@ -307,19 +327,8 @@ static MfeSpanLayout mfe_span_layout(const SeqPack &pk, int max_span, size_t bud
         if (!L) continue;
         y.n_f += (unsigned long long)L + 1; y.n_stack += (unsigned long long)L + 8; y.n_db += (unsigned long long)L + 1;
     }
-    const std::vector<int> &order = pk.fold;
-    std::vector<size_t> tab_bytes(order.size());
-    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)(MFE_SPAN_TABLES * mfe_span_table_ints(y.qs[order[k]].L, y.qs[order[k]].W) * 4);
-    y.plan = plan_chunks(order.size(), tab_bytes.data(), nullptr, budget, 65535);
-    for (size_t k = 0; k < order.size(); k++) y.qs[order[k]].tab_off = y.plan.off[k] / 4;
+    y.plan = plan_tables(pk.fold, y.qs, [](const MfeSpanSeq &q) { return (size_t)(MFE_SPAN_TABLES * mfe_span_table_ints(q.L, q.W) * 4); }, 4, nullptr, budget);
     return y;
-}
-// the widest band of the sequences order[a .. b) of a chunk: the anti-diagonals its fill launches
-static int mfe_span_chunk_wmax(const ChunkPlan::Range &c, const std::vector<int> &order, const std::vector<MfeSpanSeq> &qs)
-{
-    int Wmax = 0;
-    for (size_t k = c.a; k < c.b; k++) Wmax = std::max(Wmax, qs[order[k]].W);
-    return Wmax;
 }
 
 // rafft_pf_batch / rafft_sample_batch: chunks (plan: over pk.fold) of n_tabs L x L fp64 tables a sequence and, with cost2, a second
@@ -341,12 +350,22 @@ static PfLayout pf_layout(const SeqPack &pk, int n_tabs, const size_t *cost2, si
         if (!L) continue;
         y.n_aux += 4 * ((unsigned long long)L + 1); y.n_db += (unsigned long long)L + 1;
     }
-    const std::vector<int> &order = pk.fold;
-    std::vector<size_t> tab_bytes(order.size());
-    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)n_tabs * pk.L[order[k]] * pk.L[order[k]] * sizeof(double);
-    y.plan = plan_chunks(order.size(), tab_bytes.data(), cost2, budget, 65535);
-    for (size_t k = 0; k < order.size(); k++) y.qs[order[k]].tab_off = y.plan.off[k] / sizeof(double);
+    y.plan = plan_tables(pk.fold, y.qs, [n_tabs](const PfSeq &q) { return (size_t)n_tabs * q.L * q.L * sizeof(double); }, sizeof(double), cost2, budget);
     return y;
+}
+
+// The scale of a sequence's partition function: kT in kcal/mol and 1 / (100 kT) per dcal of a call's temp;
+// from the sequence's MFE, exp(-scale_factor MFE / (kT L)) a position (scale_factor 0: 1.07) into mfe_dcal, scale and ln_scale of
+// its record - ln_scale the logarithm of the scale as stored, not the exponent it came from.
+#define PF_GAS 1.98717e-3           // kcal / (mol K)
+struct PfTemp { double kt, beta; };
+static PfTemp pf_temp(double temp) { const double kt = (temp + 273.15) * PF_GAS; return PfTemp{kt, 1.0 / (100.0 * kt)}; }
+template <class Seq>
+static void pf_set_scale(Seq &q, int mfe_dcal, double kt, double scale_factor)
+{
+    const double sf = scale_factor > 0.0 ? scale_factor : 1.07;
+    const double ln_scale = q.L ? -sf * ((double)mfe_dcal / 100.0) / (kt * (double)q.L) : 0.0;
+    q.mfe_dcal = mfe_dcal; q.scale = std::exp(ln_scale); q.ln_scale = std::log(q.scale);
 }
 
 // rafft_pf_span_batch: every sequence has W = min(max_span, L) cells a row and PF_SPAN_TABLES tables of L x W fp64; chunks (plan:
@@ -368,19 +387,9 @@ static PfSpanLayout pf_span_layout(const SeqPack &pk, int max_span, size_t budge
         if (!L) continue;
         y.n_aux += pf_span_aux_doubles(L, W); y.n_exp += pf_span_exp_ints(L); y.n_db += (unsigned long long)L + 1;
     }
-    const std::vector<int> &order = pk.fold;
-    std::vector<size_t> tab_bytes(order.size());
-    for (size_t k = 0; k < order.size(); k++) tab_bytes[k] = (size_t)(PF_SPAN_TABLES * pf_span_table_doubles(y.qs[order[k]].L, y.qs[order[k]].W) * sizeof(double));
-    y.plan = plan_chunks(order.size(), tab_bytes.data(), nullptr, budget, 65535);
-    for (size_t k = 0; k < order.size(); k++) y.qs[order[k]].tab_off = y.plan.off[k] / sizeof(double);
+    y.plan = plan_tables(pk.fold, y.qs, [](const PfSpanSeq &q) { return (size_t)(PF_SPAN_TABLES * pf_span_table_doubles(q.L, q.W) * sizeof(double)); },
+                         sizeof(double), nullptr, budget);
     return y;
-}
-// the widest band of the sequences order[a .. b) of a chunk: the anti-diagonals its passes launch
-static int pf_span_chunk_wmax(const ChunkPlan::Range &c, const std::vector<int> &order, const std::vector<PfSpanSeq> &qs)
-{
-    int Wmax = 0;
-    for (size_t k = c.a; k < c.b; k++) Wmax = std::max(Wmax, qs[order[k]].W);
-    return Wmax;
 }
 
 // rafft_sample_batch.  The rows of pk.fold[k], n_samples of L + 1 bytes: the second cost of its plan
@@ -756,7 +765,7 @@ static void barriers_tree(int n_minima, const std::vector<rafft_barriers_edge> &
 
 // ---- rafft_kinfold_batch: the weight table, the call's own arguments and the layout of a call
 
-#define KINFOLD_GAS 1.98717e-3      // kcal / (mol K), as PF_GAS of rafft_pf.hip
+#define KINFOLD_GAS 1.98717e-3      // kcal / (mol K), as PF_GAS
 
 // kT of a call in kcal/mol: kt, or the gas constant times the absolute temperature when kt is 0
 static double kinfold_kT(double temp, double kt) { return kt != 0.0 ? kt : KINFOLD_GAS * (temp + 273.15); }

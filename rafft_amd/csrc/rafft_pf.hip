@@ -32,7 +32,6 @@
 #include "rafft_batch_layout.h"     // PfSeq, PfRec
 
 #define PF_NT 256
-#define PF_GAS 1.98717e-3           // kcal / (mol K)
 #define PF_NCLOSE 175               // (pair type, base before the 3' end, base after the 5' end) of a closing pair
 
 // C, M and their outside twins by rows, M1 and M1o by columns (as MfeTabHbm).  pf_cell and pf_out_cell are templates over such a

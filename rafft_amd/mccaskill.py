@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _native as N
 from . import params as _params_mod
-from .rafft import raise_for_status
+from .rafft import _per_sequence
 from .utils import structures_from_rows
 
 
@@ -34,6 +34,16 @@ class PfResult:
         return f"PfResult({self.centroid!r}, energy={self.energy:.2f}, mfe_frequency={self.mfe_frequency:.4g})"
 
 
+_LEFT_RANGE = "the scaled partition function left the fp64 range"      # what RAFFT_ERR_CAPACITY of a sequence says in the calls below
+
+
+def _fp64_buffers(shapes):
+    """One zeroed fp64 numpy array per shape (None: no array for that sequence) and the array of pointers a call takes for them
+    (null where there is no array or an empty one)"""
+    bufs = [np.zeros(sh, dtype=np.float64) if sh is not None else None for sh in shapes]
+    return bufs, (C.c_void_p * len(bufs))(*[b.ctypes.data if b is not None and b.size else None for b in bufs])
+
+
 def pf_batch_raw(sequences, temp=37.0, scale_factor=0.0, workspace_bytes=0, probs=True):
     """(rows, records, probs) of rafft_pf_batch: the centroid rows, one dict per sequence with the fields of rafft_pf_seq, and -
     with probs=True - one L x L numpy array per sequence (None for a sequence longer than RAFFT_PF_MAX_LEN); nothing is raised
@@ -43,10 +53,7 @@ def pf_batch_raw(sequences, temp=37.0, scale_factor=0.0, workspace_bytes=0, prob
     n = len(sequences)
     enc, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
     rec = (N.PfSeq * n)()
-    pr, ptrs = None, None
-    if probs:
-        pr = [np.zeros((len(e), len(e)), dtype=np.float64) if len(e) <= N.PF_MAX_LEN else None for e in enc]
-        ptrs = (C.c_void_p * n)(*[p.ctypes.data if p is not None and p.size else None for p in pr])
+    pr, ptrs = _fp64_buffers([(len(e), len(e)) if len(e) <= N.PF_MAX_LEN else None for e in enc]) if probs else (None, None)
     N.check(L.rafft_pf_batch(n, arr, lens, float(temp), float(scale_factor), int(workspace_bytes), rec, out, ptrs))
     recs = [{k: getattr(r, k) for k, _ in N.PfSeq._fields_} for r in rec]
     return [b.value.decode("ascii") for b in bufs], recs, pr
@@ -56,16 +63,10 @@ def pf_batch(sequences, temp=37.0, probs=True, raise_errors=True):
     """The ensemble of every sequence, as a list of PfResult.  A sequence with an error raises what fold_batch raises for it
     (raise_errors=False: its entry is None)."""
     rows, recs, pr = pf_batch_raw(sequences, temp, probs=probs)
-    out = []
-    for k, s in enumerate(sequences):
-        st = recs[k]["status"]
-        if st != N.OK:
-            if raise_errors:
-                raise_for_status(st, s, k, "pf_batch", "RAFFT_PF_MAX_LEN", "the scaled partition function left the fp64 range")
-            out.append(None)
-        else:
-            out.append(PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None))
-    return out
+
+    def make(k):
+        return PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None)
+    return _per_sequence(sequences, [r["status"] for r in recs], raise_errors, make, "pf_batch", "RAFFT_PF_MAX_LEN", _LEFT_RANGE)
 
 
 def pf(sequence, temp=37.0, probs=True):
@@ -87,13 +88,8 @@ def pf_span_batch_raw(sequences, max_span, temp=37.0, scale_factor=0.0, workspac
     rec = (N.PfSeq * n)()
     fits = [len(e) <= N.MFE_SPAN_MAX_LEN for e in enc]
     width = max(1, min(max_span, N.MFE_MAX_LEN))       # (an argument the library refuses gets buffers of a legal shape)
-    pr = ptrs = un = uptrs = None
-    if probs:
-        pr = [np.zeros((len(e), min(width, len(e))), dtype=np.float64) if ok else None for e, ok in zip(enc, fits)]
-        ptrs = (C.c_void_p * n)(*[p.ctypes.data if p is not None and p.size else None for p in pr])
-    if unpaired:
-        un = [np.zeros(len(e), dtype=np.float64) if ok else None for e, ok in zip(enc, fits)]
-        uptrs = (C.c_void_p * n)(*[u.ctypes.data if u is not None and u.size else None for u in un])
+    pr, ptrs = _fp64_buffers([(len(e), min(width, len(e))) if ok else None for e, ok in zip(enc, fits)]) if probs else (None, None)
+    un, uptrs = _fp64_buffers([len(e) if ok else None for e, ok in zip(enc, fits)]) if unpaired else (None, None)
     N.check(L.rafft_pf_span_batch(n, arr, lens, float(temp), float(scale_factor), max_span, int(workspace_bytes), rec, out, ptrs, uptrs))
     recs = [{k: getattr(r, k) for k, _ in N.PfSeq._fields_} for r in rec]
     return [b.value.decode("ascii") for b in bufs], recs, pr, un
@@ -103,16 +99,10 @@ def pf_span_batch(sequences, max_span, temp=37.0, probs=True, raise_errors=True)
     """The ensemble of every sequence under `max_span`, as a list of PfResult whose probs are banded, shape (L, W), and which
     hold `unpaired`.  A sequence with an error raises what fold_batch raises for it (raise_errors=False: its entry is None)."""
     rows, recs, pr, un = pf_span_batch_raw(sequences, max_span, temp, probs=probs)
-    out = []
-    for k, s in enumerate(sequences):
-        st = recs[k]["status"]
-        if st != N.OK:
-            if raise_errors:
-                raise_for_status(st, s, k, "pf_span_batch", "RAFFT_MFE_SPAN_MAX_LEN", "the scaled partition function left the fp64 range")
-            out.append(None)
-        else:
-            out.append(PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None, un[k]))
-    return out
+
+    def make(k):
+        return PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None, un[k])
+    return _per_sequence(sequences, [r["status"] for r in recs], raise_errors, make, "pf_span_batch", "RAFFT_MFE_SPAN_MAX_LEN", _LEFT_RANGE)
 
 
 def pf_span(sequence, max_span, temp=37.0, probs=True):
@@ -186,16 +176,8 @@ def sample_batch(sequences, n_samples, seeds=None, temp=37.0, raise_errors=True)
     """n_samples structures drawn from the Boltzmann ensemble of every sequence, as a list of lists of utils.Structure (in the
     order drawn, repeats included).  A sequence with an error raises what fold_batch raises for it (raise_errors=False: None)."""
     recs, rows, dcal = sample_batch_raw(sequences, n_samples, seeds, temp)
-    out = []
-    for k, s in enumerate(sequences):
-        st = recs[k]["status"]
-        if st != N.OK:
-            if raise_errors:
-                raise_for_status(st, s, k, "sample_batch", "RAFFT_PF_MAX_LEN", "the scaled partition function left the fp64 range")
-            out.append(None)
-        else:
-            out.append(structures_from_rows(rows[k], dcal[k], len(s)))
-    return out
+    return _per_sequence(sequences, [r["status"] for r in recs], raise_errors, lambda k: structures_from_rows(rows[k], dcal[k], len(sequences[k])),
+                         "sample_batch", "RAFFT_PF_MAX_LEN", _LEFT_RANGE)
 
 
 def sample(sequence, n_samples, seed=None, temp=37.0):
@@ -232,12 +214,8 @@ def mea_batch_raw(sequences, gamma=1.0, temp=37.0, scale_factor=0.0, workspace_b
     n = len(sequences)
     enc, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
     rec = (N.MeaSeq * n)()
-    pr, ptrs = None, None
-    if probs:
-        pr = [np.zeros((len(e), len(e)), dtype=np.float64) if len(e) <= N.PF_MAX_LEN else None for e in enc]
-        ptrs = (C.c_void_p * n)(*[p.ctypes.data if p is not None and p.size else None for p in pr])
-    un = [np.zeros(len(e), dtype=np.float64) for e in enc]
-    uptrs = (C.c_void_p * n)(*[u.ctypes.data if u.size else None for u in un])
+    pr, ptrs = _fp64_buffers([(len(e), len(e)) if len(e) <= N.PF_MAX_LEN else None for e in enc]) if probs else (None, None)
+    un, uptrs = _fp64_buffers([len(e) for e in enc])
     N.check(L.rafft_mea_batch(n, arr, lens, float(temp), float(scale_factor), int(workspace_bytes), float(gamma), rec, out, ptrs, uptrs))
     recs = [{k: getattr(r, k) for k, _ in N.MeaSeq._fields_} for r in rec]
     return [b.value.decode("ascii") for b in bufs], recs, pr, un
@@ -247,17 +225,10 @@ def mea_batch(sequences, gamma=1.0, temp=37.0, probs=False, raise_errors=True):
     """The MEA structure of every sequence, as a list of MeaResult.  A sequence with an error raises what fold_batch raises for it
     (raise_errors=False: its entry is None)."""
     rows, recs, pr, un = mea_batch_raw(sequences, gamma, temp, probs=probs)
-    out = []
-    for k, s in enumerate(sequences):
-        st = recs[k]["status"]
-        if st != N.OK:
-            if raise_errors:
-                raise_for_status(st, s, k, "mea_batch", "RAFFT_PF_MAX_LEN", "the scaled partition function left the fp64 range")
-            out.append(None)
-        else:
-            out.append(MeaResult(rows[k], recs[k]["mea"], recs[k]["dcal"] / 100.0, recs[k]["energy"], recs[k]["diversity"], un[k],
-                                 pr[k] if pr is not None else None))
-    return out
+
+    def make(k):
+        return MeaResult(rows[k], recs[k]["mea"], recs[k]["dcal"] / 100.0, recs[k]["energy"], recs[k]["diversity"], un[k], pr[k] if pr is not None else None)
+    return _per_sequence(sequences, [r["status"] for r in recs], raise_errors, make, "mea_batch", "RAFFT_PF_MAX_LEN", _LEFT_RANGE)
 
 
 def mea(sequence, gamma=1.0, temp=37.0):
@@ -276,8 +247,7 @@ def mea_from_probs_raw(matrices, gamma=1.0, workspace_bytes=0):
     ptrs = (C.c_void_p * n)(*[m.ctypes.data if m.size else None for m in mats])
     bufs = [C.create_string_buffer(m.shape[0] + 1) for m in mats]
     out = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
-    un = [np.zeros(m.shape[0], dtype=np.float64) for m in mats]
-    uptrs = (C.c_void_p * n)(*[u.ctypes.data if u.size else None for u in un])
+    un, uptrs = _fp64_buffers([m.shape[0] for m in mats])
     rec = (N.MeaProbsSeq * n)()
     N.check(L.rafft_mea_probs_batch(n, lens, ptrs, float(gamma), int(workspace_bytes), rec, out, uptrs))
     recs = [{k: getattr(r, k) for k, _ in N.MeaProbsSeq._fields_} for r in rec]

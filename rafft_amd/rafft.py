@@ -45,6 +45,20 @@ def raise_for_status(status, sequence, index, call, limit, capacity=None):
     _raise_like_reference(status, sequence)
 
 
+def _per_sequence(sequences, status, raise_errors, make, call, limit, capacity=None):
+    """The list a batch call `call` returns: make(k) for sequence k with status[k] RAFFT_OK; another status raises what
+    raise_for_status raises for it (raise_errors=False: its entry is None)."""
+    out = []
+    for k, s in enumerate(sequences):
+        if status[k] == N.OK:
+            out.append(make(k))
+        elif raise_errors:
+            raise_for_status(status[k], s, k, call, limit, capacity)
+        else:
+            out.append(None)
+    return out
+
+
 class _Owner:
     """keeps a rafft_result alive while any view of it exists; frees it with the last one"""
     __slots__ = ("res", "lib")

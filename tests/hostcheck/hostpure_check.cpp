@@ -393,6 +393,30 @@ static void check_pf_layout()
     CHECK(y.qs[4].aux_off == 56 && y.qs[4].db_off == 14);         // (aux and rows are the whole call's, not a chunk's)
 }
 
+// the scale of a partition function (pf_temp, pf_set_scale), bit for bit against the formula of DESIGN.md section 10 spelled out
+static void check_pf_scale()
+{
+    volatile double temp_in = 37.0;                                  // (volatile: both sides call exp and log at run time)
+    volatile int L_in = 77, dcal_in = -2470;
+    const double temp = temp_in, kt = (temp + 273.15) * 1.98717e-3, beta = 1.0 / (100.0 * kt);
+    const PfTemp t = pf_temp(temp);
+    CHECK(t.kt == kt && t.beta == beta);
+    PfSeq none{0, 0, 0, 0, 0, 7, 5.0, 5.0};                          // L = 0: the exponent is 0 whatever the MFE says
+    pf_set_scale(none, -1230, kt, 0.0);
+    CHECK(none.mfe_dcal == -1230 && none.scale == std::exp(0.0) && none.ln_scale == std::log(std::exp(0.0)) && none.scale == 1.0 && none.ln_scale == 0.0);
+    const int L = L_in, dcal = dcal_in;
+    for (const double scale_factor : {0.0, 1.3}) {                   // 0: the default, 1.07
+        const double sf = scale_factor > 0.0 ? scale_factor : 1.07;
+        const double ln_scale = -sf * ((double)dcal / 100.0) / (kt * (double)L), scale = std::exp(ln_scale);
+        PfSeq q{0, 0, 0, 0, L, 0, 0.0, 0.0};
+        PfSpanSeq b{0, 0, 0, 0, 0, L, 30, 0, 0, 0.0, 0.0};
+        pf_set_scale(q, dcal, kt, scale_factor);
+        pf_set_scale(b, dcal, kt, scale_factor);
+        CHECK(q.mfe_dcal == dcal && q.scale == scale && q.ln_scale == std::log(scale) && q.scale > 1.0);
+        CHECK(b.mfe_dcal == dcal && b.scale == scale && b.ln_scale == std::log(scale));
+    }
+}
+
 static void check_sample_layout()
 {
     const SeqPack pk = pack_of({0, 5, 7, 0, 6});
@@ -490,6 +514,7 @@ int main()
     check_chunk_lmax();
     check_mfe_layout();
     check_pf_layout();
+    check_pf_scale();
     check_sample_layout();
     check_subopt_layout();
     printf("hostpure: %d failures\n", fails);

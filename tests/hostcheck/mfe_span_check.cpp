@@ -38,12 +38,12 @@ static void check_layout()
         CHECK(y.qs[2].db_off == 11 && y.qs[5].db_off == 42 && y.n_db == 53);
         CHECK(y.qs[2].code_off == 10 && y.qs[4].code_off == 30);
         const ChunkPlan::Range c = y.plan.chunks[0];
-        CHECK(mfe_span_chunk_wmax(c, pk.fold, y.qs) == 12 && chunk_lmax(c, pk.fold, pk.L) == 20);
+        CHECK(chunk_wmax(c, pk.fold, y.qs) == 12 && chunk_lmax(c, pk.fold, pk.L) == 20);
     }
     {   // exactly fitting: 10 and 20 together, then 9 and 10; one byte less: 10 alone, 20 with 9, 10 alone
         const MfeSpanLayout y = mfe_span_layout(pk, 12, t10 + t20);
         CHECK(y.plan.chunks.size() == 2 && y.plan.chunks[0].b == 2 && y.plan.chunks[1].b == 4 && y.qs[4].tab_off == 0 && y.qs[5].tab_off == 324);
-        CHECK(mfe_span_chunk_wmax(y.plan.chunks[1], pk.fold, y.qs) == 10);
+        CHECK(chunk_wmax(y.plan.chunks[1], pk.fold, y.qs) == 10);
         CHECK(y.qs[4].f_off == 32);                                                     // (what is not in the workspace is laid out for the whole call)
         const MfeSpanLayout z = mfe_span_layout(pk, 12, t10 + t20 - 1);
         CHECK(z.plan.chunks.size() == 3 && z.plan.chunks[0].b == 1 && z.plan.chunks[1].b == 3 && z.qs[2].tab_off == 0 && z.qs[4].tab_off == 960 && z.qs[5].tab_off == 0);

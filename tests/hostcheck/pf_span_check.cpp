@@ -66,13 +66,13 @@ static void check_layout()
         CHECK(y.qs[2].exp_off == 22 && y.qs[4].exp_off == 64 && y.qs[5].exp_off == 84 && y.n_exp == 106);
         CHECK(y.qs[2].db_off == 11 && y.qs[5].db_off == 42 && y.n_db == 53);
         CHECK(y.qs[2].code_off == 10 && y.qs[4].code_off == 30);
-        CHECK(pf_span_chunk_wmax(y.plan.chunks[0], pk.fold, y.qs) == 12 && chunk_lmax(y.plan.chunks[0], pk.fold, pk.L) == 20);
+        CHECK(chunk_wmax(y.plan.chunks[0], pk.fold, y.qs) == 12 && chunk_lmax(y.plan.chunks[0], pk.fold, pk.L) == 20);
         check_disjoint(pk, y);
     }
     {   // exactly fitting: 10 and 20 together, then 9 and 10; one byte less: 10 alone, 20 with 9, 10 alone
         const PfSpanLayout y = pf_span_layout(pk, 12, t10 + t20);
         CHECK(y.plan.chunks.size() == 2 && y.plan.chunks[0].b == 2 && y.plan.chunks[1].b == 4 && y.qs[4].tab_off == 0 && y.qs[5].tab_off == 486);
-        CHECK(pf_span_chunk_wmax(y.plan.chunks[1], pk.fold, y.qs) == 10);
+        CHECK(chunk_wmax(y.plan.chunks[1], pk.fold, y.qs) == 10);
         CHECK(y.qs[4].aux_off == 146);                                                  // (what is not in the workspace is laid out for the whole call)
         check_disjoint(pk, y);
         const PfSpanLayout z = pf_span_layout(pk, 12, t10 + t20 - 1);
