@@ -31,7 +31,8 @@ enum {
     RAFFT_ERR_PARAM = 6,         /* unsupported parameter combination (e.g. max_branch+2*max_stack too large) */
     RAFFT_ERR_HIP = 7,           /* HIP runtime error; see rafft_last_error() */
     RAFFT_ERR_STRUCT = 8,        /* malformed dot-bracket / non-canonical pair in rafft_eval_structure */
-    RAFFT_ERR_NO_DEVICE = 9
+    RAFFT_ERR_NO_DEVICE = 9,
+    RAFFT_ERR_INFEASIBLE = 10    /* rafft_mfe_constrained_batch: no structure satisfies the sequence's hard constraints */
 };
 
 #define RAFFT_MAX_LEN 32768
@@ -367,6 +368,54 @@ int rafft_mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, do
                          int max_span,               /* 1 .. RAFFT_MFE_MAX_LEN */
                          long long workspace_bytes,  /* 0: 512 MiB; one sequence at least */
                          rafft_mfe_seq *seq_out, char *const *db_out /* db_out[s]: lens[s] + 1 bytes, NUL terminated */);
+
+/* Minimum-free-energy structures under hard constraints and soft terms (what `RNAfold -C
+ * --enforceConstraint` and `RNAfold --shape` are used for), for the two size classes of rafft_mfe_batch.  Every sequence may carry
+ * any of three inputs; an absent one (a null array, a null entry) is neutral.
+ * constraints[s]: a NUL-terminated string of lens[s] characters, all of them enforced:
+ *     .  nothing            x  unpaired            |  paired, any partner
+ *     <  paired with a partner downstream (the 5' end of its pair)       >  paired with a partner upstream
+ *     ( ) matched brackets: this pair is in the structure
+ * The ensemble is exactly the set of structures of rafft_mfe_batch (canonical pairs, hairpins of at least 3, interior loops of at
+ * most 30) that satisfy every character.
+ * soft_unpaired[s] (u) and soft_stack[s] (b): lens[s] values in dcal each, |value| <= RAFFT_MFE_SOFT_MAX.  u[k] is added for every
+ * unpaired position k; b follows the Deigan convention: a pair (i,j) stacked directly on (i+1,j-1) adds b[i] + b[j] + b[i+1] + b[j-1].
+ * With up(k): constraints[k] is . or x; free(a,b): up on all of a..b (the empty range is free); U(a,b) = u[a] + .. + u[b];
+ * ok(i,j): canonical, j - i - 1 >= 3, constraints[i] one of . | < or a ( whose partner is j, constraints[j] one of . | > or a )
+ * whose partner is i - the recurrences of rafft_mfe_batch become (a cell with !ok(i,j) has C = no structure):
+ *     C[i][j]:  the hairpin only if free(i+1,j-1), plus U(i+1,j-1); an interior loop with (p,q) only if free(i+1,p-1) and
+ *               free(q+1,j-1), plus both U terms, plus the stack term when p = i+1 and q = j-1; the multiloop term unchanged
+ *     M1[i][j] = min(C[i][j] + stem, M1[i][j-1] + ml_base + u[j] if up(j))
+ *     M[i][j]  = min(M1[i][j], M[i+1][j] + ml_base + u[i] if up(i), splits)
+ *     F[j]     = min(F[j-1] + u[j] if up(j), stems),  F[-1] = 0
+ * A pair that crosses a forced pair needs no test: one end of the forced pair lies inside it and can neither pair nor stay unpaired.
+ * dcal is the minimum of rafft_eval_structure(row) + soft terms(row) over the ensemble and may be positive; pseudo_dcal is the soft
+ * part of dcal for the returned row, so rafft_eval_structure(row) == dcal - pseudo_dcal.  The traceback's candidate order is
+ * rafft_mfe_batch's; a candidate the constraints remove is not a candidate.  A sequence without any constraint, or with an all-'.'
+ * string and zero arrays, gets the row, dcal and n_pairs of rafft_mfe_batch byte for byte, and the result of a sequence is a
+ * function of the sequence, its constraints, the energy tables and temp - not of the batch, its order, the size class or the chunks.
+ * Size classes, max_lds_len, workspace_bytes, outputs and the errors of a sequence as rafft_mfe_batch.  Errors of that sequence
+ * only as well (all-dot row, the call returns RAFFT_OK, rafft_last_error() names the first): RAFFT_ERR_STRUCT, found on the host - a
+ * string of another length than the sequence, a character outside the seven, unbalanced brackets, a bracket pair that is not
+ * canonical or encloses fewer than 3 positions; RAFFT_ERR_INFEASIBLE - no structure satisfies the constraints.  RAFFT_ERR_PARAM,
+ * before anything is launched: as rafft_mfe_batch, and a soft value beyond RAFFT_MFE_SOFT_MAX (at 4096 nt a position counts once in
+ * u or at most twice in b: 4096 x 2 x 20000 = 1.6e8 stays below the 5e8 guard of section 9).  RAFFT_ERR_TEMP as for the fold. */
+#define RAFFT_MFE_SOFT_MAX 20000
+typedef struct {
+    int32_t status;
+    int32_t length;
+    int32_t dcal;        /* the objective: loop energies plus soft terms of the row, in dcal/mol */
+    int32_t n_pairs;     /* pairs of the row */
+    int32_t pseudo_dcal; /* the soft terms of the row */
+    int32_t _pad;
+} rafft_mfe_con_seq;     /* 24 bytes */
+int rafft_mfe_constrained_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                                const char *const *constraints,      /* may be NULL; entries may be NULL */
+                                const int32_t *const *soft_unpaired, /* may be NULL; entries may be NULL; lens[s] dcal values */
+                                const int32_t *const *soft_stack,    /* the same */
+                                int max_lds_len,            /* as rafft_mfe_batch */
+                                long long workspace_bytes,  /* 0: 512 MiB */
+                                rafft_mfe_con_seq *seq_out, char *const *db_out /* db_out[s]: lens[s] + 1 bytes, NUL terminated */);
 
 /* Partition function, base-pair probabilities and centroid structures of a batch (McCaskill).  Replaces:
  * RNA.fold_compound(seq, md).pf() / bpp(), the calls beside the RNA.fold of benchmark_results/src/vrna_mfe.py:25.

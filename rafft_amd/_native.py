@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RAFFT_LIB") or os.path.join(_HERE, "libraffthip.so")      # (RAFFT_LIB: another build of the library, for A/B measurements)
 
-OK, ERR_BAD_CHAR, ERR_EMPTY, ERR_TOO_LONG, ERR_TEMP, ERR_CAPACITY, ERR_PARAM, ERR_HIP, ERR_STRUCT, ERR_NO_DEVICE = range(10)
+OK, ERR_BAD_CHAR, ERR_EMPTY, ERR_TOO_LONG, ERR_TEMP, ERR_CAPACITY, ERR_PARAM, ERR_HIP, ERR_STRUCT, ERR_NO_DEVICE, ERR_INFEASIBLE = range(11)
 
 
 class Params(C.Structure):
@@ -56,7 +56,14 @@ class MfeSeq(C.Structure):
     _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("dcal", C.c_int32), ("n_pairs", C.c_int32)]
 
 
+class MfeConSeq(C.Structure):
+    """rafft_mfe_con_seq: one record per sequence of rafft_mfe_constrained_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("dcal", C.c_int32), ("n_pairs", C.c_int32), ("pseudo_dcal", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
 MFE_MAX_LEN = 4096               # RAFFT_MFE_MAX_LEN
+MFE_SOFT_MAX = 20000             # RAFFT_MFE_SOFT_MAX (dcal)
 MFE_SPAN_MAX_LEN = 32768         # RAFFT_MFE_SPAN_MAX_LEN (RAFFT_MAX_LEN)
 
 
@@ -176,7 +183,7 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
            "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters", "rafft_barriers_batch",
            "rafft_barriers_free", "rafft_barriers_counters", "rafft_kinfold_batch", "rafft_kinfold_weights", "rafft_kinfold_counters",
-           "rafft_mea_batch", "rafft_mea_probs_batch", "rafft_mfe_span_batch", "rafft_pf_span_batch"]
+           "rafft_mea_batch", "rafft_mea_probs_batch", "rafft_mfe_span_batch", "rafft_pf_span_batch", "rafft_mfe_constrained_batch"]
 
 _lib = None
 
@@ -267,6 +274,9 @@ def lib():
     L.rafft_mfe_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_longlong, C.POINTER(MfeSeq),
                                   C.POINTER(C.c_void_p)]
     L.rafft_mfe_lds_len.argtypes = []
+    L.rafft_mfe_constrained_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_char_p),
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(MfeConSeq),
+                                              C.POINTER(C.c_void_p)]
     L.rafft_mfe_span_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_longlong, C.POINTER(MfeSeq),
                                        C.POINTER(C.c_void_p)]
     L.rafft_pf_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.POINTER(PfSeq),

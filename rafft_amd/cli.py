@@ -56,6 +56,17 @@ _OPTIONS = [
                                                 "mfe_scores.csv.  Works with -s SEQ and with -sf FILE --batch")),
     (("--span",), dict(type=int, default=None, metavar="W", help="with --mfe: only pairs (i, j) with j - i + 1 <= W, 1 <= W <= 4096 (rafft_amd.mfe_span_batch; as\n"
                                                                  "`RNAfold --maxBPspan W`), for sequences of up to 32768 nt.  Output and --scores as --mfe")),
+    (("-C", "--constraint"), dict(action="store_true", dest="constraint",
+                                  help="with --mfe: fold under hard constraints (rafft_amd.mfe_constrained_batch; as `RNAfold -C --enforceConstraint`).\n"
+                                       "After each sequence of the -sf file, or on stdin after -s SEQ, comes a constraint line of the sequence's\n"
+                                       "length: . nothing, x unpaired, | paired, < > paired with a partner downstream / upstream, ( ) this pair.\n"
+                                       "Output as --mfe, with the pseudo-energy (kcal/mol) as one more column.  Not with --span")),
+    (("--shape",), dict(default=None, metavar="FILE", help="with --mfe: SHAPE-directed folding (Deigan's pseudo-energies on stacked pairs, as `RNAfold --shape FILE`).\n"
+                                                           "FILE holds lines `position reactivity`, 1-based; a missing position or a negative value means no\n"
+                                                           "data.  With --batch one block per sequence, each introduced by a `>name` line, in the -sf file's\n"
+                                                           "order.  Output as -C.  Not with --span")),
+    (("--shape-slope",), dict(type=float, default=1.8, metavar="M", dest="shape_slope", help="with --shape: m of m ln(reactivity + 1) + b, kcal/mol (default 1.8)")),
+    (("--shape-intercept",), dict(type=float, default=-0.6, metavar="B", dest="shape_intercept", help="with --shape: b, kcal/mol (default -0.6)")),
     (("--pf",), dict(action="store_true", help="no RAFFT fold: the partition function of every sequence on the GPU (rafft_amd.pf_batch; the ensemble of --mfe),\n"
                                                "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
                                                "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
@@ -256,11 +267,82 @@ def format_mfe_line(sequence, struct):
     return f"{sequence} {len(sequence)} {struct.str_struct} {struct.energy} {struct.str_struct.count('(')}"
 
 
-def main_mfe(args, seqs, known, names, mfe_batch=None, scorer=None):
+def read_constrained_fasta(path):
+    """(sequences, constraints, names) of a file for --mfe -C: per record an optional `>name` line, the sequence on one line and its
+    constraint line, as `RNAfold -C` reads them"""
+    seqs, cons, names, name = [], [], [], ""
+    lines = [l.strip() for l in open(path)]
+    body = []
+    for l in lines + [">"]:
+        if l.startswith(">"):
+            if len(body) % 2:
+                raise SystemExit(f"{path}: -C needs a constraint line after every sequence")
+            for k in range(0, len(body), 2):
+                seqs.append(body[k].replace("T", "U")); cons.append(body[k + 1]); names.append(name)
+            body, name = [], l[1:].strip()
+        elif l:
+            body.append(l)
+    return seqs, cons, names
+
+
+def read_shape(path, lens, batch):
+    """The reactivities of a --shape file, one float array per sequence (NaN: no data): lines `position reactivity`, 1-based.  With
+    `batch` one block per sequence, each introduced by a `>name` line, in the sequences' order; else one block, no `>` line needed."""
+    import numpy as np
+    blocks, cur = [], None
+    for n, l in enumerate(open(path), 1):
+        l = l.strip()
+        if not l or l.startswith("#"):
+            continue
+        if l.startswith(">"):
+            cur = []
+            blocks.append(cur)
+            continue
+        if cur is None:
+            if batch:
+                raise SystemExit(f"{path}:{n}: with --batch every block of --shape begins with a `>name` line")
+            cur = []
+            blocks.append(cur)
+        f = l.split()
+        try:
+            cur.append((int(f[0]), float(f[1])))
+        except (ValueError, IndexError):
+            raise SystemExit(f"{path}:{n}: --shape expects `position reactivity`")
+    if not blocks and not batch:
+        blocks.append([])
+    if len(blocks) != len(lens):
+        raise SystemExit(f"{path}: {len(blocks)} blocks of reactivities for {len(lens)} sequences")
+    out = []
+    for k, (block, L) in enumerate(zip(blocks, lens)):
+        r = np.full(L, np.nan)
+        for pos, val in block:
+            if not 1 <= pos <= L:
+                raise SystemExit(f"{path}: position {pos} outside sequence {k} of {L} nt")
+            r[pos - 1] = val
+        out.append(r)
+    return out
+
+
+def format_mfe_constrained_line(sequence, struct):
+    """the line of --mfe and the pseudo-energy of the structure in kcal/mol"""
+    return f"{format_mfe_line(sequence, struct)} {struct.pseudo_dcal / 100.0}"
+
+
+def main_mfe(args, seqs, known, names, mfe_batch=None, scorer=None, constraints=None, mfe_constrained_batch=None):
     """--mfe: the MFE structures instead of the fold.  `scorer`: the callable (rows per sequence, known) -> score table that stands
-    in for scoring.score_rows_gpu."""
+    in for scoring.score_rows_gpu.  With -C (`constraints`: one string per sequence) or --shape the constrained fold."""
     if args.kin or args.traj:
         raise SystemExit("--mfe gives one structure per sequence: no --kin, no --traj")
+    line = format_mfe_line
+    if args.constraint or args.shape is not None:
+        soft = None
+        if args.shape is not None:
+            from .zuker import shape_deigan
+            soft = [shape_deigan(r, args.shape_slope, args.shape_intercept) for r in read_shape(args.shape, [len(s) for s in seqs], args.batch)]
+        if mfe_constrained_batch is None:
+            from .zuker import mfe_constrained_batch
+        mfe_batch = lambda sequences, temp: mfe_constrained_batch(sequences, constraints, None, soft, temp)
+        line = format_mfe_constrained_line
     if mfe_batch is None and args.span is not None:
         from .zuker import mfe_span_batch
         mfe_batch = lambda sequences, temp: mfe_span_batch(sequences, args.span, temp)
@@ -274,7 +356,7 @@ def main_mfe(args, seqs, known, names, mfe_batch=None, scorer=None):
         write_scores(args.scores, seqs, names, beams, scorer(beams, known), "energy")
         if not args.output:
             return
-    text = "".join(format_mfe_line(s, st) + "\n" for s, st in zip(seqs, structs))
+    text = "".join(line(s, st) + "\n" for s, st in zip(seqs, structs))
     if args.output:
         with open(args.output, "w") as out:
             out.write(text)
@@ -649,15 +731,21 @@ def _table_note():
                          "for ViennaRNA's own values (RAFFT_QUIET=1 silences this)\n")
 
 
-def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None, mea_batch=None):
+def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None, mea_batch=None,
+         mfe_constrained_batch=None):
     """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch` / `subopt_batch`: injection points for tests (the fold, the
     callable (results, known) -> score table that stands in for scoring.score_batch_gpu - with --mfe, --pf and --sample for
     scoring.score_rows_gpu -, the callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable
     (sequences, temp) that stands in for zuker.mfe_batch, the callable (sequences, temp) that stands in for mccaskill.pf_batch,
     the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch, and the callable (sequences, delta,
     max_structs, temp) that stands in for wuchty.subopt_batch; `mea_batch`: the callable (sequences, gamma, temp) that stands in for
-    mccaskill.mea_batch)."""
+    mccaskill.mea_batch; `mfe_constrained_batch`: the callable (sequences, constraints, soft_unpaired, soft_stack, temp) that stands in
+    for zuker.mfe_constrained_batch)."""
     args = parse_arguments(argv)
+    if (args.constraint or args.shape is not None) and not args.mfe:
+        raise SystemExit("-C and --shape FILE constrain the fold of --mfe: they need --mfe")
+    if (args.constraint or args.shape is not None) and args.span is not None:
+        raise SystemExit("-C and --shape FILE do not combine with --span")
     if args.span is not None and not args.mfe:
         raise SystemExit("--span W restricts the pairs of --mfe: it needs --mfe")
     if args.span is not None and not 1 <= args.span <= 4096:
@@ -676,7 +764,22 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
         raise SystemExit("--barriers needs --subopt DELTA: the tree is that of the band")
     if args.descend and args.sample is None and args.subopt is None:
         return main_descend(args)
-    seqs, known, names = read_records(args)
+    constraints = None
+    if args.constraint and args.sequence is not None:
+        seqs, known, names, constraints = [args.sequence], None, None, [sys.stdin.readline().strip()]
+    elif args.constraint and args.scores:              # the CSV of --scores (with a header line) carries the constraints in a column `constraint`
+        import csv
+        seqs, known, names = read_records(args)
+        with open(args.seq_file, newline="") as fh:
+            rd = csv.DictReader(fh)
+            if "constraint" not in (rd.fieldnames or []):
+                raise SystemExit(f"{args.seq_file}: -C with --scores needs a column 'constraint' (columns: {rd.fieldnames})")
+            constraints = [(r["constraint"] or "").strip() for r in rd if r[args.csv_column].strip()]
+    elif args.constraint:
+        seqs, constraints, names = read_constrained_fasta(args.seq_file)
+        known = None
+    else:
+        seqs, known, names = read_records(args)
     if args.kinfold is not None:
         return main_kinfold(args, seqs, names)
     if args.mea is not None and (args.mfe or args.pf or args.subopt is not None or args.kin or args.traj):
@@ -705,7 +808,7 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     if args.pf:
         return main_pf(args, seqs, known, names, pf_batch, scorer)
     if args.mfe:
-        return main_mfe(args, seqs, known, names, mfe_batch, scorer)
+        return main_mfe(args, seqs, known, names, mfe_batch, scorer, constraints, mfe_constrained_batch)
     if fold_batch is None:
         from .rafft import fold_batch
     results = fold_batch(seqs, args.n_mode, args.max_stack, args.max_branch, args.min_hp, args.min_nrj, args.traj,

@@ -1,7 +1,8 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
-// workspace budget (workspace_budget).  Thirteen of them:
+// workspace budget (workspace_budget).  Fourteen of them:
 //   kin_batch                    folding kinetics of many graphs
 //   mfe_batch, mfe_span_batch    minimum-free-energy folds; the same under a base-pair span, to 32768 nt
+//   mfe_con_batch                the folds of mfe_batch under hard constraints and soft terms
 //   pf_batch, pf_span_batch      partition function and pair probabilities; the same under a span, to 32768 nt
 //   mea_batch, mea_probs_batch   maximum-expected-accuracy structures, of sequences and of given probabilities
 //   sample_batch                 structures drawn from the ensemble
@@ -241,10 +242,11 @@ int mfe_fill_chunk(hipStream_t st, const MfeSeq *d_qs, const ChunkView &v, const
 }
 
 // What mfe_held and mfe_span_held end with: the tracebacks' records and the n_db bytes of rows come down, one synchronise, and
-// every sequence without an error gets its dcal, its n_pairs and - db_out may be null (no rows wanted) - its row.
+// every sequence without an error gets its dcal, its n_pairs, - db_out may be null (no rows wanted) - its row and - soft_out may
+// be null - the soft part of its dcal (mfe_con_held).
 template <class Seq>
 int mfe_results(hipStream_t st, const std::vector<Seq> &qs, const int4 *d_rec, const char *d_db, unsigned long long n_db, rafft_mfe_seq *seq_out,
-                char *const *db_out)
+                char *const *db_out, int *soft_out = nullptr)
 {
     const int n_seq = (int)qs.size();
     std::vector<int4> rec(n_seq);
@@ -256,6 +258,7 @@ int mfe_results(hipStream_t st, const std::vector<Seq> &qs, const int4 *d_rec, c
         if (seq_out[s].status) continue;
         if (rec[s].z) return fail(RAFFT_ERR_HIP, "internal: sequence " + std::to_string(s) + ": the traceback found no candidate for a cell");
         seq_out[s].dcal = rec[s].x; seq_out[s].n_pairs = rec[s].y;
+        if (soft_out) soft_out[s] = rec[s].w;
         if (db_out) memcpy(db_out[s], db.data() + qs[s].db_off, (size_t)qs[s].L + 1);
     }
     return 0;
@@ -314,6 +317,98 @@ int mfe_batch(int n_seq, const char *const *seqs, const int *lens, double temp, 
     if (int rc = sc.open(mem, pk, temp)) return rc;
     if (int rc = mfe_held(sc.st, pk, sc.d_codes, lds_len, workspace_bytes, seq_out, db_out)) return rc;
     g_err = pk.first_err;
+    return 0;
+}
+
+// ---- minimum-free-energy folds under constraints and soft terms
+
+// The constrained MFE folds of a pack, under the caller's guard, as mfe_held: the same layout, classes and chunks, the mfe_con_*
+// kernels in place of the mfe_* ones, the packs of `cp` (constraint_pack; no sequence of it has an error that pk does not know)
+// in device memory.  mfe[s] gets dcal and n_pairs - a dcal of MFE_INF: the sequence has no structure and its row is all dots -
+// and soft[s] the soft part of dcal.
+int mfe_con_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, const ConstraintPack &cp, int lds_len, long long workspace_bytes,
+                 rafft_mfe_seq *mfe, int *soft, char *const *db_out)
+{
+    const MfeLayout y = mfe_layout(pk, lds_len, workspace_budget(workspace_bytes));
+    const std::vector<MfeSeq> &qs = y.qs;
+    DevScratch mem;
+    MfeSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr, *d_packs; unsigned long long *d_off;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSeq))) return rc;
+    if (int rc = mem.alloc(d_stack, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_db, y.n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
+    if (int rc = mem.alloc(d_order, y.order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_packs, cp.data.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_off, cp.off.size() * 8)) return rc;
+    if (y.plan.max_cost) if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, y.order.data(), y.order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_packs, cp.data.data(), cp.data.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_off, cp.off.data(), cp.off.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
+    if (!y.lds_order.empty()) {
+        HIPCHK(hipFuncSetAttribute((const void *)mfe_con_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MFE_CON_LDS_BYTES));
+        hipLaunchKernelGGL(mfe_con_lds_kernel, dim3((unsigned)y.lds_order.size()), dim3(MFE_LDS_NT), (size_t)mfe_con_lds_bytes(qs[y.lds_order[0]].L), st, g.T, d_qs,
+                           d_order, d_codes, d_off, d_packs, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        const ChunkView v = chunk_view(c, d_order + y.lds_order.size(), y.hbm_order, pk);
+        for (int d = 0; d < v.Lmax; d++) {
+            const unsigned nx = (unsigned)std::min((v.Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
+            hipLaunchKernelGGL(mfe_con_diag_kernel, dim3(nx, v.ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, v.ord, d_codes, d_off, d_packs, d_ws, d);
+        }
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mfe_con_traceback_kernel, dim3(v.ny), dim3(64), 0, st, g.T, d_qs, v.ord, d_codes, d_off, d_packs, d_ws, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    return mfe_results(st, qs, d_rec, d_db, y.n_db, mfe, db_out, soft);
+}
+
+// rafft_mfe_constrained_batch (arguments validated by the entry point)
+int mfe_con_batch(int n_seq, const char *const *seqs, const int *lens, double temp, const char *const *constraints, const int32_t *const *soft_unpaired,
+                  const int32_t *const *soft_stack, int lds_len, long long workspace_bytes, rafft_mfe_con_seq *seq_out, char *const *db_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    const ConstraintPack cp = constraint_pack(n_seq, pk.L.data(), pk.codes.data(), pk.code_off.data(), constraints, soft_unpaired, soft_stack);
+    if (cp.param_seq >= 0) return fail(RAFFT_ERR_PARAM, cp.first_err);
+    // an error of a sequence's constraints is an error of the sequence: it is not folded, and the first error in input order is named
+    if (cp.first_seq >= 0) {
+        int first = 0;
+        while (first < n_seq && !pk.status[first]) first++;
+        if (cp.first_seq < first) pk.first_err = cp.first_err;
+        for (int s = 0; s < n_seq; s++)
+            if (cp.status[s]) { pk.status[s] = cp.status[s]; pk.L[s] = 0; }
+        pk.fold.erase(std::remove_if(pk.fold.begin(), pk.fold.end(), [&](int s) { return cp.status[s] != 0; }), pk.fold.end());
+    }
+    for (int s = 0; s < n_seq; s++) {
+        seq_out[s] = rafft_mfe_con_seq{pk.status[s], pk.len[s], 0, 0, 0, 0};
+        dot_row(db_out[s], pk.len[s]);
+    }
+    g_err = pk.first_err;
+    if (pk.fold.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    std::vector<rafft_mfe_seq> mfe(n_seq);
+    std::vector<int> soft(n_seq, 0);
+    for (int s = 0; s < n_seq; s++) mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+    if (int rc = mfe_con_held(sc.st, pk, sc.d_codes, cp, lds_len, workspace_bytes, mfe.data(), soft.data(), db_out)) return rc;
+    std::string err = pk.first_err;
+    int first = 0;
+    while (first < n_seq && !pk.status[first]) first++;
+    for (int s = 0; s < n_seq; s++) {
+        if (pk.status[s]) continue;
+        if (mfe[s].dcal >= MFE_INFH) {
+            seq_out[s].status = RAFFT_ERR_INFEASIBLE;
+            if (s < first) { first = s; err = "sequence " + std::to_string(s) + ": no structure satisfies its constraints"; }
+            continue;
+        }
+        seq_out[s].dcal = mfe[s].dcal; seq_out[s].n_pairs = mfe[s].n_pairs; seq_out[s].pseudo_dcal = soft[s];
+    }
+    g_err = err;
     return 0;
 }
 

@@ -29,6 +29,25 @@ struct MfeSeq {
     int L, pad;
 };
 
+// ---- the same under constraints and soft terms (the mfe_con_* kernels of rafft_mfe.hip)
+
+// A sequence's constraint pack, mfe_con_pack_ints(L) int32 back to back: code[L] - the partner of a position with a bracket, else
+// one of MFE_CON_*; must[L + 1] - must[k] = positions before k that have to pair (neither . nor x), so a..b may stay unpaired iff
+// must[b + 1] == must[a]; usum[L + 1] - usum[k] = the sum of soft_unpaired before k; b[L] - soft_stack.  A sequence without any
+// constraint has no pack: its offset is MFE_CON_NONE.
+#define MFE_CON_ANY (-1)            // .
+#define MFE_CON_UNPAIRED (-2)       // x
+#define MFE_CON_PAIRED (-3)         // |
+#define MFE_CON_DOWN (-4)           // <  paired with a partner downstream
+#define MFE_CON_UP (-5)             // >  paired with a partner upstream
+#define MFE_CON_NONE (~0ull)
+RAFFT_HD constexpr int mfe_con_pack_ints(int L) { return 4 * L + 2; }
+// LDS class: the pack behind the bases.  More than the 128 KiB of the unconstrained kernel at RAFFT_MFE_LDS_LEN, within the
+// 160 KiB a workgroup may have: the LDS bound is the same for both entry points
+#define MFE_CON_LDS_BYTES (160 << 10)
+RAFFT_HD constexpr int mfe_con_lds_bytes(int L) { return mfe_lds_bytes(L) + ((4 * mfe_con_pack_ints(L) + 15) & ~15); }
+static_assert(mfe_con_lds_bytes(RAFFT_MFE_LDS_LEN) <= MFE_CON_LDS_BYTES, "the constraint pack of RAFFT_MFE_LDS_LEN positions fits the LDS of a workgroup");
+
 // ---- minimum-free-energy folds under a base-pair span (rafft_mfe_span.hip)
 
 // What a sequence of L positions folded with pairs of at most max_span positions has on the device.  W = min(max_span, L) cells

@@ -3,7 +3,7 @@
 // rafft_batch.h: chunks within a budget, the sequence pack, the graph pack, the solve order, the scale of a partition function,
 // and the layouts - every offset the drivers' kernels dereference, as records of rafft_batch_layout.h - with, for the drivers
 // that need them, the moves and conflict masks of findpath, the row intake of descend, barriers and kinfold, the tree of
-// barriers, the weight table and argument checks of kinfold.
+// barriers, the weight table and argument checks of kinfold, the constraint packs of the constrained MFE folds.
 // Plain C++ (g++ compiles it alone: the programs of tests/hostcheck).  Part of the single translation unit of rafft_api.hip
 // (included there, before the kernels).
 #pragma once
@@ -27,6 +27,8 @@ struct BaseCodeTable {
     uint8_t operator[](unsigned char c) const { return v[c]; }
 };
 static const BaseCodeTable kBaseCode;
+// two base codes that form a canonical pair: CG GC GU UG AU UA
+static bool fp_canonical(int a, int b) { return (a == 2 && b == 3) || (a == 3 && b == 2) || (a == 3 && b == 4) || (a == 4 && b == 3) || (a == 1 && b == 4) || (a == 4 && b == 1); }
 
 // pair table of a plain dot-bracket string (0-based partners, -1 = unpaired); false: malformed
 static bool parse_db(const char *db, int L, std::vector<int16_t> &pt)
@@ -308,6 +310,78 @@ static MfeLayout mfe_layout(const SeqPack &pk, int lds_len, size_t budget)
     return y;
 }
 
+// rafft_mfe_constrained_batch: the constraint packs of a call, as the kernels read them (the layout is
+// stated in rafft_batch_layout.h).  Per sequence s of L[s] positions (0: it has an error already and is not looked at) whose
+// bases lie at codes + code_off[s]: constraints[s], a string of . x | < > ( ), soft_unpaired[s] and soft_stack[s], L[s] dcal values
+// each; every one of the three arrays and every entry may be null.  A sequence with an error, or with no constraint at all, takes no
+// space and points at nothing (off[s] = MFE_CON_NONE).  status[s] = RAFFT_ERR_STRUCT for a string of another length than the
+// sequence, a character outside the seven, unbalanced brackets, a bracket pair that is not canonical or encloses fewer than 3
+// positions: an error of that sequence (first_seq, first_err: the first of them).  param_seq >= 0: that sequence has a soft value
+// beyond RAFFT_MFE_SOFT_MAX, an error of the call - nothing else of the pack is valid then.
+struct ConstraintPack {
+    std::vector<int> status;
+    std::vector<unsigned long long> off;    // first int of the sequence's pack in `data`, or MFE_CON_NONE
+    std::vector<int32_t> data;              // 16 bytes of zeros behind the last pack
+    int first_seq = -1, param_seq = -1;
+    std::string first_err;
+};
+static ConstraintPack constraint_pack(int n_seq, const int *L, const uint8_t *codes, const unsigned long long *code_off, const char *const *constraints,
+                                      const int32_t *const *soft_unpaired, const int32_t *const *soft_stack)
+{
+    ConstraintPack p;
+    p.status.assign(n_seq, 0);
+    p.off.assign(n_seq, MFE_CON_NONE);
+    std::vector<int> stk;
+    for (int s = 0; s < n_seq; s++) {
+        const int len = L[s];
+        const char *con = constraints ? constraints[s] : nullptr;
+        const int32_t *u = soft_unpaired ? soft_unpaired[s] : nullptr, *b = soft_stack ? soft_stack[s] : nullptr;
+        if (!len || (!con && !u && !b)) continue;
+        for (const int32_t *soft : {u, b})
+            for (int k = 0; soft && k < len; k++)
+                if (soft[k] > RAFFT_MFE_SOFT_MAX || soft[k] < -RAFFT_MFE_SOFT_MAX) {
+                    p.param_seq = s;
+                    p.first_err = "sequence " + std::to_string(s) + ": a soft constraint beyond RAFFT_MFE_SOFT_MAX at position " + std::to_string(k);
+                    return p;
+                }
+        const size_t at = p.data.size();
+        p.data.resize(at + (size_t)mfe_con_pack_ints(len), 0);
+        int32_t *code = p.data.data() + at, *must = code + len, *usum = must + len + 1, *bb = usum + len + 1;
+        const uint8_t *S = codes + code_off[s];
+        const char *why = nullptr;
+        if (con && strnlen(con, (size_t)len + 1) != (size_t)len) why = "a constraint string of another length than the sequence";
+        stk.clear();
+        for (int k = 0; k < len && !why; k++) {
+            const char c = con ? con[k] : '.';
+            code[k] = c == '.' ? MFE_CON_ANY : c == 'x' ? MFE_CON_UNPAIRED : c == '|' ? MFE_CON_PAIRED : c == '<' ? MFE_CON_DOWN : c == '>' ? MFE_CON_UP : 0;
+            if (c == '(') stk.push_back(k);
+            else if (c == ')') {
+                if (stk.empty()) { why = "unbalanced brackets in the constraint"; break; }
+                const int i = stk.back();
+                stk.pop_back();
+                if (!fp_canonical(S[i], S[k])) why = "a forced pair that is not canonical";
+                else if (k - i - 1 < 3) why = "a forced pair that encloses fewer than 3 positions";
+                code[i] = k; code[k] = i;
+            } else if (!code[k]) why = "a constraint character outside . x | < > ( )";
+        }
+        if (!why && !stk.empty()) why = "unbalanced brackets in the constraint";
+        if (why) {
+            p.data.resize(at);
+            p.status[s] = RAFFT_ERR_STRUCT;
+            if (p.first_seq < 0) { p.first_seq = s; p.first_err = "sequence " + std::to_string(s) + ": " + why; }
+            continue;
+        }
+        for (int k = 0; k < len; k++) {
+            must[k + 1] = must[k] + (code[k] != MFE_CON_ANY && code[k] != MFE_CON_UNPAIRED);
+            usum[k + 1] = usum[k] + (u ? u[k] : 0);
+            bb[k] = b ? b[k] : 0;
+        }
+        p.off[s] = at;
+    }
+    p.data.resize(p.data.size() + 4, 0);
+    return p;
+}
+
 // rafft_mfe_span_batch: every sequence has W = min(max_span, L) cells a row and MFE_SPAN_TABLES tables of L x W int32; chunks
 // (plan: over pk.fold) of whole sequences in input order.  n_f ints of exterior energies, n_stack words of traceback stacks, n_db
 // bytes of rows over the whole call.
@@ -547,7 +621,6 @@ struct FpMoves {
     std::vector<uint64_t> conf;         // (d - n_rem) x fp_mask_words(d)
     int n_rem = 0, d = 0;
 };
-static bool fp_canonical(int a, int b) { return (a == 2 && b == 3) || (a == 3 && b == 2) || (a == 3 && b == 4) || (a == 4 && b == 3) || (a == 1 && b == 4) || (a == 4 && b == 1); }
 static int findpath_moves(const uint8_t *codes, int L, const char *a, const char *b, FpMoves &o)
 {
     o = FpMoves{};

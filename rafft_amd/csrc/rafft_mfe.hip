@@ -15,6 +15,10 @@
 // Two size classes share mfe_cell and mfe_traceback through a table view: triangular tables in LDS (mfe_lds_kernel, one workgroup per
 // sequence, a barrier per anti-diagonal) and full L x L tables in HBM (mfe_diag_kernel, one launch per anti-diagonal: stream order
 // is the synchronisation; mfe_traceback_kernel).
+// Constraints are a policy handed through mfe_interior, mfe_cell, mfe_exterior and mfe_traceback beside the
+// table view: which pairs may close, which ranges may stay unpaired, and what the soft terms add.  MfeConNone allows everything,
+// adds nothing and compiles away; MfeConPack reads a sequence's constraint pack (constraint_pack of rafft_hostpure.h).  The
+// mfe_con_* kernels are the two size classes again with a pack per sequence, in LDS behind the bases or in device memory.
 #pragma once
 
 #include "rafft_batch_layout.h"     // MfeSeq, RAFFT_MFE_LDS_LEN, MFE_LDS_BYTES, mfe_lds_bytes
@@ -79,9 +83,46 @@ __device__ __forceinline__ int mfe_stem_ext(const SmallT *T, const uint8_t *S, i
 {
     return e_stem(T, pair_type(S[i], S[j]), i > 0 ? (int)S[i - 1] : -1, j < L - 1 ? (int)S[j + 1] : -1, true);
 }
-// interior-loop candidate x of the pair (i,j) of type t: its energy with C[p][q], MFE_INF when there is no such loop
-template <class Tab>
-__device__ __forceinline__ int mfe_interior(const Tab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int i, int j, int t, int x, int &p, int &q)
+// constraint policies.  ok(i,j): the pair may close (that it is canonical and spans a hairpin is the caller's test); up(k): k may
+// stay unpaired; free(a,b): every position of a..b may (the empty range is free); u(k), U(a,b): what k, what a..b add when
+// unpaired; stack(i,j,p,q): what the stack of (i,j) on (p,q) = (i+1,j-1) adds.  `on`: false for the policy that compiles away.
+struct MfeConNone {
+    static constexpr bool on = false;
+    __device__ __forceinline__ bool ok(int, int) const { return true; }
+    __device__ __forceinline__ bool up(int) const { return true; }
+    __device__ __forceinline__ bool free(int, int) const { return true; }
+    __device__ __forceinline__ int u(int) const { return 0; }
+    __device__ __forceinline__ int U(int, int) const { return 0; }
+    __device__ __forceinline__ int stack(int, int, int, int) const { return 0; }
+};
+// over a sequence's pack (mfe_con_pack_ints(L) ints, LDS or device memory): code[L] (the partner of a bracket, else MFE_CON_*),
+// must[L + 1] (must[k]: positions before k that have to pair), usum[L + 1] (the sum of u before k), b[L]
+struct MfeConPack {
+    static constexpr bool on = true;
+    const int *code, *must, *usum, *b;
+    __device__ __forceinline__ MfeConPack(const int *pack, int L) : code(pack), must(pack + L), usum(pack + 2 * L + 1), b(pack + 3 * L + 2) {}
+    __device__ __forceinline__ bool ok(int i, int j) const
+    {
+        const int ci = code[i], cj = code[j];
+        return (ci == MFE_CON_ANY || ci == MFE_CON_PAIRED || ci == MFE_CON_DOWN || ci == j) && (cj == MFE_CON_ANY || cj == MFE_CON_PAIRED || cj == MFE_CON_UP || cj == i);
+    }
+    __device__ __forceinline__ bool up(int k) const { return must[k + 1] == must[k]; }
+    __device__ __forceinline__ bool free(int a, int b_) const { return must[b_ + 1] == must[a]; }
+    __device__ __forceinline__ int u(int k) const { return usum[k + 1] - usum[k]; }
+    __device__ __forceinline__ int U(int a, int b_) const { return usum[b_ + 1] - usum[a]; }
+    __device__ __forceinline__ int stack(int i, int j, int p, int q) const { return b[i] + b[j] + b[p] + b[q]; }
+};
+
+// the soft part of the loop between (i,j) and (p,q): its unpaired positions, and the stack term when there are none
+template <class Con>
+__device__ __forceinline__ int mfe_interior_soft(const Con &cn, int i, int j, int p, int q)
+{
+    return cn.U(i + 1, p - 1) + cn.U(q + 1, j - 1) + (p == i + 1 && q == j - 1 ? cn.stack(i, j, p, q) : 0);
+}
+// interior-loop candidate x of the pair (i,j) of type t: its energy with C[p][q], MFE_INF when there is no such loop.  A lane
+// whose candidate the constraints remove returns MFE_INF like any other that has none: it stays in the minimum and the ballots
+template <class Tab, class Con>
+__device__ __forceinline__ int mfe_interior(const Tab &tb, const Con &cn, const SmallT *T, const BigT *B, const uint8_t *S, int i, int j, int t, int x, int &p, int &q)
 {
     const int n12 = mfe_il.v[x], n1 = n12 >> 8, n2 = n12 & 255;
     p = i + 1 + n1; q = j - 1 - n2;
@@ -90,8 +131,9 @@ __device__ __forceinline__ int mfe_interior(const Tab &tb, const SmallT *T, cons
     if (!t2) return MFE_INF;
     const int cc = tb.c(p, q);
     if (cc >= MFE_INFH) return MFE_INF;
+    if (!cn.free(i + 1, p - 1) || !cn.free(q + 1, j - 1)) return MFE_INF;
     int g = 0;
-    return e_intloop(T, B, n1, n2, t, rtype(t2), S[i + 1], S[j - 1], S[p - 1], S[q + 1], g) + cc;
+    return e_intloop(T, B, n1, n2, t, rtype(t2), S[i + 1], S[j - 1], S[p - 1], S[q + 1], g) + cc + mfe_interior_soft(cn, i, j, p, q);
 }
 // what closing a multiloop with (i,j) of type t adds to its inside M[i+1][k-1] + M1[k][j-1]
 __device__ __forceinline__ int mfe_ml_close(const SmallT *T, const uint8_t *S, int i, int j, int t)
@@ -100,19 +142,19 @@ __device__ __forceinline__ int mfe_ml_close(const SmallT *T, const uint8_t *S, i
 }
 
 // one wavefront fills cell (i,j) of the three tables; every cell of a smaller j - i is there
-template <class Tab>
-__device__ inline void mfe_cell(const Tab &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, int i, int j, int lane)
+template <class Tab, class Con>
+__device__ inline void mfe_cell(const Tab &tb, const Con &cn, const SmallT *T, const BigT *B, const uint8_t *S, int L, int i, int j, int lane)
 {
     const int d = j - i;
     int c = MFE_INF, m1 = MFE_INF, m = MFE_INF;
     if (d >= 4) {
         const int t = pair_type(S[i], S[j]);
-        if (t) {
+        if (t && cn.ok(i, j)) {
             int best = MFE_INF;
-            if (lane == 0) best = e_hairpin(T, B, d - 1, t, S, i, j);
+            if (lane == 0 && cn.free(i + 1, j - 1)) best = e_hairpin(T, B, d - 1, t, S, i, j) + cn.U(i + 1, j - 1);
             for (int x = lane; x < MFE_NIL; x += 64) {
                 int p, q;
-                best = min(best, mfe_interior(tb, T, B, S, i, j, t, x, p, q));
+                best = min(best, mfe_interior(tb, cn, T, B, S, i, j, t, x, p, q));
             }
             int ml = MFE_INF;                       // a stem takes five positions: k - 1 >= i + 5, k <= j - 5
             for (int k = i + 6 + lane; k <= j - 5; k += 64) {
@@ -125,10 +167,10 @@ __device__ inline void mfe_cell(const Tab &tb, const SmallT *T, const BigT *B, c
         }
         const int mlb = T->ml_base;
         const int prev = tb.m1(i, j - 1);
-        if (prev < MFE_INFH) m1 = min(m1, prev + mlb);
+        if (prev < MFE_INFH && cn.up(j)) m1 = min(m1, prev + mlb + cn.u(j));
         m = m1;
         const int nx = tb.m(i + 1, j);
-        if (nx < MFE_INFH) m = min(m, nx + mlb);
+        if (nx < MFE_INFH && cn.up(i)) m = min(m, nx + mlb + cn.u(i));
         int sp = MFE_INF;
         for (int k = i + 5 + lane; k <= j - 4; k += 64) {
             const int a = tb.m(i, k - 1), b = tb.m1(k, j);
@@ -154,9 +196,10 @@ struct MfeWalkFull {
     }
 };
 
-// One wavefront: the exterior loop.  F: L + 1 ints of LDS, F[j + 1] = exterior energy of 0..j
-template <class Tab, class Walk>
-__device__ inline void mfe_exterior(const Tab &tb, const Walk &wk, const SmallT *T, const uint8_t *S, int L, int *F, int lane)
+// One wavefront: the exterior loop.  F: L + 1 ints of LDS, F[j + 1] = exterior energy of 0..j (under constraints MFE_INF where
+// 0..j has no structure)
+template <class Tab, class Walk, class Con>
+__device__ inline void mfe_exterior(const Tab &tb, const Walk &wk, const Con &cn, const SmallT *T, const uint8_t *S, int L, int *F, int lane)
 {
     if (lane == 0) F[0] = 0;
     wave_sync();
@@ -164,39 +207,46 @@ __device__ inline void mfe_exterior(const Tab &tb, const Walk &wk, const SmallT 
         int best = MFE_INF;
         for (int i = wk.lo(j) + lane; i <= j - 4; i += 64) {
             const int e = wk.ext(tb, T, S, L, i, j);
-            if (e < MFE_INFH) best = min(best, F[i] + e);
+            if (e < MFE_INFH && (!Con::on || F[i] < MFE_INFH)) best = min(best, F[i] + e);
         }
         best = mfe_wave_min(best);
         const int prev = F[j];
-        if (lane == 0) F[j + 1] = min(prev, best);
+        if (lane == 0) F[j + 1] = !Con::on ? min(prev, best) : prev < MFE_INFH && cn.up(j) ? min(prev + cn.u(j), best) : best;
         wave_sync();
     }
 }
 
 // One wavefront: the traceback from the F of mfe_exterior, with an explicit stack of (i, j, table) words; F holds the pair table
 // once the exterior loop is traced.  `stack`: `cap` words only lane 0 touches.
-// rec = (dcal, pairs, 1 when no candidate reproduced a cell - an internal error, 0)
-template <class Tab, class Walk>
-__device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT *T, const BigT *B, const uint8_t *S, int L, int *F, uint32_t *stack, int cap,
-                                     char *db, int4 *rec, int lane)
+// rec = (dcal, pairs, 1 when no candidate reproduced a cell - an internal error, the soft part of dcal for the row: 0 without
+// constraints).  Under constraints a sequence without a structure gets a row of dots and rec = (MFE_INF, 0, 0, 0).
+template <class Tab, class Walk, class Con>
+__device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const Con &cn, const SmallT *T, const BigT *B, const uint8_t *S, int L, int *F, uint32_t *stack,
+                                     int cap, char *db, int4 *rec, int lane)
 {
     const int mfe = F[L];
-    int sp = 0, npairs = 0, bad = 0;
+    if (Con::on && mfe >= MFE_INFH) {
+        for (int x = lane; x < L; x += 64) db[x] = '.';
+        if (lane == 0) { db[L] = 0; *rec = make_int4(MFE_INF, 0, 0, 0); }
+        return;
+    }
+    int sp = 0, npairs = 0, bad = 0, soft = 0;
     auto push = [&](int i, int j, int kind) {
         if (sp >= cap) { bad = 1; return; }
         if (lane == 0) stack[sp] = wk.pack(i, j, kind);
         sp++;
     };
-    for (int j = L - 1; j >= 4 && !bad;) {
+    int rest = L - 1;                                   // the 3' end of what the exterior loop has not traced yet
+    for (int j = rest; j >= 4 && !bad; rest = j) {
         const int v = F[j + 1];
-        if (v == F[j]) { j--; continue; }
+        if (!Con::on ? v == F[j] : F[j] < MFE_INFH && cn.up(j) && v == F[j] + cn.u(j)) { soft += cn.u(j); j--; continue; }
         int found = -1;
         for (int i0 = wk.lo(j); i0 <= j - 4 && found < 0; i0 += 64) {
             const int i = i0 + lane;
             bool hit = false;
             if (i <= j - 4) {
                 const int e = wk.ext(tb, T, S, L, i, j);
-                hit = e < MFE_INFH && F[i] + e == v;
+                hit = e < MFE_INFH && (!Con::on || F[i] < MFE_INFH) && F[i] + e == v;
             }
             const unsigned long long bal = __ballot(hit);
             if (bal) found = i0 + __ffsll((long long)bal) - 1;
@@ -205,6 +255,7 @@ __device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT
         push(found, j, MFE_K_C);
         j = found - 1;
     }
+    if (Con::on && rest >= 0) soft += cn.U(0, rest);    // what is left of the 5' end holds no pair
     wave_sync();
     int *pt = F;
     for (int x = lane; x < L; x += 64) pt[x] = -1;
@@ -223,7 +274,7 @@ __device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT
                 if (tb.m1(i, j) == v) { kind = MFE_K_M1; break; }
                 if (j > i) {
                     const int nx = tb.m(i + 1, j);
-                    if (nx < MFE_INFH && nx + mlb == v) { i++; continue; }
+                    if (nx < MFE_INFH && cn.up(i) && nx + mlb + cn.u(i) == v) { soft += cn.u(i); i++; continue; }
                 }
                 int found = -1;
                 for (int k0 = i + 5; k0 <= j - 4 && found < 0; k0 += 64) {
@@ -248,7 +299,7 @@ __device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT
                 if (c < MFE_INFH && c + mfe_stem_ml(T, S, L, i, j) == v) { kind = MFE_K_C; break; }
                 if (j > i) {
                     const int prev = tb.m1(i, j - 1);
-                    if (prev < MFE_INFH && prev + mlb == v) { j--; continue; }
+                    if (prev < MFE_INFH && cn.up(j) && prev + mlb + cn.u(j) == v) { soft += cn.u(j); j--; continue; }
                 }
                 bad = 1;
                 break;
@@ -259,18 +310,19 @@ __device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT
         npairs++;
         const int v = tb.c(i, j), t = pair_type(S[i], S[j]);
         if (!t || v >= MFE_INFH) { bad = 1; continue; }
-        if (e_hairpin(T, B, j - i - 1, t, S, i, j) == v) continue;
+        if (cn.free(i + 1, j - 1) && e_hairpin(T, B, j - i - 1, t, S, i, j) + cn.U(i + 1, j - 1) == v) { soft += cn.U(i + 1, j - 1); continue; }
         int found = -1;
         for (int x0 = 0; x0 < MFE_NIL && found < 0; x0 += 64) {
             const int x = x0 + lane;
             int p, q;
-            const bool hit = x < MFE_NIL && mfe_interior(tb, T, B, S, i, j, t, x, p, q) == v;
+            const bool hit = x < MFE_NIL && mfe_interior(tb, cn, T, B, S, i, j, t, x, p, q) == v;
             const unsigned long long bal = __ballot(hit);
             if (bal) found = x0 + __ffsll((long long)bal) - 1;
         }
         if (found >= 0) {
-            const int n12 = mfe_il.v[found];
-            push(i + 1 + (n12 >> 8), j - 1 - (n12 & 255), MFE_K_C);
+            const int n12 = mfe_il.v[found], p = i + 1 + (n12 >> 8), q = j - 1 - (n12 & 255);
+            soft += mfe_interior_soft(cn, i, j, p, q);
+            push(p, q, MFE_K_C);
             continue;
         }
         const int close = mfe_ml_close(T, S, i, j, t);
@@ -290,57 +342,120 @@ __device__ inline void mfe_traceback(const Tab &tb, const Walk &wk, const SmallT
     }
     wave_sync();
     for (int x = lane; x < L; x += 64) { const int y = pt[x]; db[x] = y < 0 ? '.' : y > x ? '(' : ')'; }
-    if (lane == 0) { db[L] = 0; *rec = make_int4(mfe, npairs, bad, 0); }
+    if (lane == 0) { db[L] = 0; *rec = make_int4(mfe, npairs, bad, soft); }
 }
 
-// LDS class: workgroup b folds sequence order[b]
+// LDS class: a workgroup folds sequence s, its tables, F and bases (already there, a barrier behind them) in LDS
+template <class Con>
+__device__ __forceinline__ void mfe_lds_fold(const MfeTabLds &tb, const Con &cn, const EnergyTables *ET, const MfeSeq &q, int *F, const uint8_t *S, uint32_t *stacks,
+                                             char *db, int4 *rec)
+{
+    const int L = q.L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const SmallT *T = &ET->s;
+    const BigT *B = &ET->b;
+    for (int d = 0; d < L; d++) {
+        for (int i = wave; i + d < L; i += MFE_LDS_NT / 64) mfe_cell(tb, cn, T, B, S, L, i, i + d, lane);
+        __syncthreads();
+    }
+    if (wave == 0) {
+        mfe_exterior(tb, MfeWalkFull(), cn, T, S, L, F, lane);
+        mfe_traceback(tb, MfeWalkFull(), cn, T, B, S, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec, lane);
+    }
+}
+// workgroup b folds sequence order[b]
 __global__ __launch_bounds__(MFE_LDS_NT) void mfe_lds_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes,
                                                             uint32_t *stacks, char *db, int4 *rec)
 {
     extern __shared__ __align__(16) int mfe_lds[];
     const int s = order[blockIdx.x];
     const MfeSeq q = seqs[s];
-    const int L = q.L, N = L * (L + 1) / 2, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int L = q.L, N = L * (L + 1) / 2, tid = threadIdx.x;
     const MfeTabLds tb{mfe_lds, mfe_lds + N, mfe_lds + 2 * N, L};
     int *F = mfe_lds + 3 * N;
     uint8_t *S = (uint8_t *)(F + L + 1);
     for (int x = tid; x < L; x += MFE_LDS_NT) S[x] = codes[q.code_off + x];
     __syncthreads();
-    const SmallT *T = &ET->s;
-    const BigT *B = &ET->b;
-    for (int d = 0; d < L; d++) {
-        for (int i = wave; i + d < L; i += MFE_LDS_NT / 64) mfe_cell(tb, T, B, S, L, i, i + d, lane);
-        __syncthreads();
-    }
-    if (wave == 0) {
-        mfe_exterior(tb, MfeWalkFull(), T, S, L, F, lane);
-        mfe_traceback(tb, MfeWalkFull(), T, B, S, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, lane);
-    }
+    mfe_lds_fold(tb, MfeConNone(), ET, q, F, S, stacks, db, rec + s);
+}
+// the same under constraints: con_off[s] is where the sequence's pack lies in `packs` (MFE_CON_NONE: it has none and is folded
+// as mfe_lds_kernel folds it); the pack goes to LDS behind the bases (mfe_con_lds_bytes)
+__global__ __launch_bounds__(MFE_LDS_NT) void mfe_con_lds_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes,
+                                                                const unsigned long long *con_off, const int *packs, uint32_t *stacks, char *db, int4 *rec)
+{
+    extern __shared__ __align__(16) int mfe_lds[];
+    const int s = order[blockIdx.x];
+    const MfeSeq q = seqs[s];
+    const unsigned long long co = con_off[s];
+    const int L = q.L, N = L * (L + 1) / 2, tid = threadIdx.x;
+    const MfeTabLds tb{mfe_lds, mfe_lds + N, mfe_lds + 2 * N, L};
+    int *F = mfe_lds + 3 * N;
+    uint8_t *S = (uint8_t *)(F + L + 1);
+    int *pack = mfe_lds + mfe_lds_bytes(L) / 4;
+    for (int x = tid; x < L; x += MFE_LDS_NT) S[x] = codes[q.code_off + x];
+    if (co != MFE_CON_NONE)
+        for (int x = tid; x < mfe_con_pack_ints(L); x += MFE_LDS_NT) pack[x] = packs[co + x];
+    __syncthreads();
+    if (co != MFE_CON_NONE) mfe_lds_fold(tb, MfeConPack(pack, L), ET, q, F, S, stacks, db, rec + s);
+    else mfe_lds_fold(tb, MfeConNone(), ET, q, F, S, stacks, db, rec + s);
 }
 
-// HBM class: anti-diagonal d of the sequences order[0 .. gridDim.y), four cells per workgroup and round
-__global__ __launch_bounds__(MFE_HBM_NT) void mfe_diag_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes, int *tabs, int d)
+// HBM class: anti-diagonal d of a sequence, four cells per workgroup and round
+template <class Con>
+__device__ __forceinline__ void mfe_diag_fill(const Con &cn, const EnergyTables *ET, const MfeSeq &q, const uint8_t *codes, int *tabs, int d)
 {
-    const MfeSeq q = seqs[order[blockIdx.y]];
     const int L = q.L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (d >= L) return;
     int *t0 = tabs + q.tab_off;
     const size_t LL = (size_t)L * L;
     const MfeTabHbm tb{t0, t0 + LL, t0 + 2 * LL, L};
     const uint8_t *S = codes + q.code_off;
-    for (int i = blockIdx.x * (MFE_HBM_NT / 64) + wave; i + d < L; i += gridDim.x * (MFE_HBM_NT / 64)) mfe_cell(tb, &ET->s, &ET->b, S, L, i, i + d, lane);
+    for (int i = blockIdx.x * (MFE_HBM_NT / 64) + wave; i + d < L; i += gridDim.x * (MFE_HBM_NT / 64)) mfe_cell(tb, cn, &ET->s, &ET->b, S, L, i, i + d, lane);
+}
+// of the sequences order[0 .. gridDim.y)
+__global__ __launch_bounds__(MFE_HBM_NT) void mfe_diag_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes, int *tabs, int d)
+{
+    const MfeSeq q = seqs[order[blockIdx.y]];
+    if (d >= q.L) return;
+    mfe_diag_fill(MfeConNone(), ET, q, codes, tabs, d);
+}
+// the same under constraints, the packs read where they lie in device memory
+__global__ __launch_bounds__(MFE_HBM_NT) void mfe_con_diag_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes,
+                                                                 const unsigned long long *con_off, const int *packs, int *tabs, int d)
+{
+    const int s = order[blockIdx.y];
+    const MfeSeq q = seqs[s];
+    if (d >= q.L) return;
+    const unsigned long long co = con_off[s];
+    if (co != MFE_CON_NONE) mfe_diag_fill(MfeConPack(packs + co, q.L), ET, q, codes, tabs, d);
+    else mfe_diag_fill(MfeConNone(), ET, q, codes, tabs, d);
 }
 
+// the exterior loop and the traceback of a sequence of the HBM class, one wavefront; F: L + 1 ints of LDS
+template <class Con>
+__device__ __forceinline__ void mfe_hbm_trace(const Con &cn, const EnergyTables *ET, const MfeSeq &q, const uint8_t *codes, int *tabs, int *F, uint32_t *stacks,
+                                              char *db, int4 *rec)
+{
+    const int L = q.L;
+    int *t0 = tabs + q.tab_off;
+    const size_t LL = (size_t)L * L;
+    const MfeTabHbm tb{t0, t0 + LL, t0 + 2 * LL, L};
+    mfe_exterior(tb, MfeWalkFull(), cn, &ET->s, codes + q.code_off, L, F, (int)threadIdx.x);
+    mfe_traceback(tb, MfeWalkFull(), cn, &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec, (int)threadIdx.x);
+}
 __global__ __launch_bounds__(64) void mfe_traceback_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes, int *tabs,
                                                           uint32_t *stacks, char *db, int4 *rec)
 {
     __shared__ int F[RAFFT_MFE_MAX_LEN + 1];
     const int s = order[blockIdx.x];
     const MfeSeq q = seqs[s];
-    const int L = q.L;
-    int *t0 = tabs + q.tab_off;
-    const size_t LL = (size_t)L * L;
-    const MfeTabHbm tb{t0, t0 + LL, t0 + 2 * LL, L};
-    mfe_exterior(tb, MfeWalkFull(), &ET->s, codes + q.code_off, L, F, (int)threadIdx.x);
-    mfe_traceback(tb, MfeWalkFull(), &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, (int)threadIdx.x);
+    mfe_hbm_trace(MfeConNone(), ET, q, codes, tabs, F, stacks, db, rec + s);
+}
+__global__ __launch_bounds__(64) void mfe_con_traceback_kernel(const EnergyTables *ET, const MfeSeq *seqs, const int *order, const uint8_t *codes,
+                                                              const unsigned long long *con_off, const int *packs, int *tabs, uint32_t *stacks, char *db, int4 *rec)
+{
+    __shared__ int F[RAFFT_MFE_MAX_LEN + 1];
+    const int s = order[blockIdx.x];
+    const MfeSeq q = seqs[s];
+    const unsigned long long co = con_off[s];
+    if (co != MFE_CON_NONE) mfe_hbm_trace(MfeConPack(packs + co, q.L), ET, q, codes, tabs, F, stacks, db, rec + s);
+    else mfe_hbm_trace(MfeConNone(), ET, q, codes, tabs, F, stacks, db, rec + s);
 }
