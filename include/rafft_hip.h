@@ -454,6 +454,48 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
                    double *const *prob_out     /* may be NULL, and so may prob_out[s]: lens[s] x lens[s] doubles, row-major,
                                                   P(i pairs j) at [i][j] for i < j, 0 elsewhere */);
 
+/* Partition function, base-pair probabilities, centroid and unpaired probabilities under hard constraints and soft terms (DESIGN.md
+ * section 21; what `RNAfold -p -C --enforceConstraint` and `RNAfold -p --shape` are used for): how sure each pair is given what is
+ * known, and the modelled accessibility to set beside a probe.  constraints, soft_unpaired (u) and soft_stack (b) are those of
+ * rafft_mfe_constrained_batch, an absent one neutral; scale_factor, workspace_bytes, seq_out, db_out and prob_out those of
+ * rafft_pf_batch.
+ * The ensemble is the one rafft_mfe_constrained_batch minimises over: every one of the seven characters is enforced.  The weight of
+ * a structure is exp(-(rafft_eval_structure(row) + soft(row)) / (100 kT)), soft = u[k] for every unpaired position k plus Deigan's
+ * b[i] + b[j] + b[i+1] + b[j-1] for every pair (i,j) stacked directly on (i+1,j-1); |value| <= RAFFT_MFE_SOFT_MAX.
+ * With w(e) = exp(-e / (100 kT)), b = w(ml_base) and ok, up, free, U, stack of rafft_mfe_constrained_batch, the sums of
+ * rafft_pf_batch become:
+ *     C[i][j]    0 unless ok(i,j); the hairpin only if free(i+1,j-1): w(hairpin + U(i+1,j-1)); an interior loop with (p,q) only if
+ *                free(i+1,p-1) and free(q+1,j-1): w(interior + both U + stack when p = i+1, q = j-1) C[p][q]; the multiloop term unchanged
+ *     M1[i][j]   = C[i][j] w(stem) + [up(j)] M1[i][j-1] b w(u[j])
+ *     M[i][j]    = sum_{k=i..j} ([free(i,k-1)] b^(k-i) w(U(i,k-1)) + M[i][k-1]) M1[k][j]
+ *     F[j]       = [up(j)] F[j-1] w(u[j]) + sum_i F[i-1] C[i][j] w(stem_ext);  Fr the same from the 3' end
+ *     Mo         unchanged
+ *     M1o[k][j]  = [up(j+1)] b w(u[j+1]) M1o[k][j+1] + (the Co term, unchanged) + sum_{i<=k} Mo[i][j] ([free(i,k-1)] b^(k-i) w(U(i,k-1)) + M[i][k-1])
+ *     Co[i][j]   0 unless ok(i,j) - a weight there would leak into the pairs inside a removed pair; else F[i-1] w(stem_ext) Fr[j+1]
+ *                + sum over enclosing (p,q) with free(p+1,i-1) and free(j+1,q-1) of Co[p][q] w(interior + soft) + w(stem) M1o[i][j]
+ *     P(i,j)     = C[i][j] Co[i][j] / Z;   unpaired[k] = 1 - sum_j P(k,j) - sum_i P(i,k)
+ * A pair that every structure holds has P = 1 up to rounding; under constraints a P above 1 is returned as 1.0.
+ * Outputs: seq_out[s].mfe_dcal is the constrained objective (dcal of rafft_mfe_constrained_batch; the call runs that fold first and
+ * takes the scale from it), energy = -kT ln Z, mfe_frequency the share of that optimum.  The centroid row holds every pair with
+ * P > 0.5; it need NOT satisfy a `|` (a position that must pair may have no partner above one half).  unpaired_out may be NULL and
+ * so may unpaired_out[s], else lens[s] doubles, each summed in an order that lens[s] fixes.  rafft_mea_probs_batch over prob_out is
+ * the MEA row under the data.
+ * Errors of a sequence (all-dot row, zeros, the call returns RAFFT_OK): those of rafft_pf_batch and of
+ * rafft_mfe_constrained_batch - RAFFT_ERR_STRUCT, found on the host; RAFFT_ERR_INFEASIBLE, from the MFE front: such a sequence takes
+ * no part in the sums.  Soft terms far from physical values can push the scaled sums out of the fp64 range: RAFFT_ERR_CAPACITY for
+ * that sequence, never a silent inf or nan.  RAFFT_ERR_PARAM, before anything is launched: the cases of both calls.
+ * A sequence with no constraint, or with an all-'.' string and zero arrays, gets the bits of rafft_pf_batch - energy, share, every P
+ * and the row; a sequence's bits depend on the sequence, its constraints, the energy tables, temp and scale_factor - not on the
+ * batch, its order or the workspace. */
+int rafft_pf_constrained_batch(int n_seq, const char *const *seqs, const int *lens, double temp,
+                               const char *const *constraints,      /* as rafft_mfe_constrained_batch */
+                               const int32_t *const *soft_unpaired,
+                               const int32_t *const *soft_stack,
+                               double scale_factor,        /* as rafft_pf_batch */
+                               long long workspace_bytes,
+                               rafft_pf_seq *seq_out, char *const *db_out, double *const *prob_out,
+                               double *const *unpaired_out /* may be NULL, entries may be NULL: lens[s] doubles */);
+
 /* Partition function, base-pair probabilities, centroid and unpaired probabilities under a maximum base-pair span, for sequences
  * of up to RAFFT_MFE_SPAN_MAX_LEN nt (what `RNAfold -p --maxBPspan` and `RNAplfold -L` are used for on long
  * RNAs).  The ensemble is rafft_pf_batch's restricted to the structures whose pairs (i, j), i < j, all have j - i + 1 <= max_span;

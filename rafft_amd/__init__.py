@@ -12,6 +12,7 @@ from .zuker import mfe, mfe_batch, mfe_span, mfe_span_batch, mfe_span_batch_raw 
 from .zuker import mfe_constrained, mfe_constrained_batch, mfe_constrained_batch_raw, shape_deigan  # noqa: F401
 from .mccaskill import pf, pf_batch, sample, sample_batch  # noqa: F401
 from .mccaskill import pf_span, pf_span_batch, pf_span_batch_raw, band_to_dense, band_pairs  # noqa: F401
+from .mccaskill import pf_constrained, pf_constrained_batch, pf_constrained_batch_raw  # noqa: F401
 from .mccaskill import MeaResult, mea, mea_batch, mea_from_probs, pair_frequencies  # noqa: F401
 from .wuchty import subopt, subopt_batch, subopt_batch_raw  # noqa: F401
 # (`rafft_amd.findpath` stays the module; its single-problem form is findpath.findpath)

@@ -183,7 +183,8 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_sample_batch", "rafft_subopt_batch", "rafft_subopt_free", "rafft_subopt_counters", "rafft_findpath_batch",
            "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters", "rafft_barriers_batch",
            "rafft_barriers_free", "rafft_barriers_counters", "rafft_kinfold_batch", "rafft_kinfold_weights", "rafft_kinfold_counters",
-           "rafft_mea_batch", "rafft_mea_probs_batch", "rafft_mfe_span_batch", "rafft_pf_span_batch", "rafft_mfe_constrained_batch"]
+           "rafft_mea_batch", "rafft_mea_probs_batch", "rafft_mfe_span_batch", "rafft_pf_span_batch", "rafft_mfe_constrained_batch",
+           "rafft_pf_constrained_batch"]
 
 _lib = None
 
@@ -283,6 +284,9 @@ def lib():
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_pf_span_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_int, C.c_longlong,
                                       C.POINTER(PfSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rafft_pf_constrained_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_char_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double, C.c_longlong, C.POINTER(PfSeq),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_mea_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.c_double,
                                   C.POINTER(MeaSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rafft_mea_probs_batch.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_double, C.c_longlong, C.POINTER(MeaProbsSeq),

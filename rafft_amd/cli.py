@@ -57,11 +57,11 @@ _OPTIONS = [
     (("--span",), dict(type=int, default=None, metavar="W", help="with --mfe: only pairs (i, j) with j - i + 1 <= W, 1 <= W <= 4096 (rafft_amd.mfe_span_batch; as\n"
                                                                  "`RNAfold --maxBPspan W`), for sequences of up to 32768 nt.  Output and --scores as --mfe")),
     (("-C", "--constraint"), dict(action="store_true", dest="constraint",
-                                  help="with --mfe: fold under hard constraints (rafft_amd.mfe_constrained_batch; as `RNAfold -C --enforceConstraint`).\n"
+                                  help="with --mfe or --pf: fold under hard constraints (rafft_amd.mfe_constrained_batch / pf_constrained_batch; as `RNAfold -C\n--enforceConstraint`).\n"
                                        "After each sequence of the -sf file, or on stdin after -s SEQ, comes a constraint line of the sequence's\n"
                                        "length: . nothing, x unpaired, | paired, < > paired with a partner downstream / upstream, ( ) this pair.\n"
                                        "Output as --mfe, with the pseudo-energy (kcal/mol) as one more column.  Not with --span")),
-    (("--shape",), dict(default=None, metavar="FILE", help="with --mfe: SHAPE-directed folding (Deigan's pseudo-energies on stacked pairs, as `RNAfold --shape FILE`).\n"
+    (("--shape",), dict(default=None, metavar="FILE", help="with --mfe or --pf: SHAPE-directed folding (Deigan's pseudo-energies on stacked pairs, as `RNAfold --shape FILE`).\n"
                                                            "FILE holds lines `position reactivity`, 1-based; a missing position or a negative value means no\n"
                                                            "data.  With --batch one block per sequence, each introduced by a `>name` line, in the -sf file's\n"
                                                            "order.  Output as -C.  Not with --span")),
@@ -285,6 +285,18 @@ def read_constrained_fasta(path):
     return seqs, cons, names
 
 
+def read_constraint_line():
+    """The constraint of -s SEQ -C: one line on stdin, for --pf as for --mfe.  A stdin that gives none (closed, empty, not
+    readable) is an error here, not a malformed constraint further down"""
+    try:
+        line = sys.stdin.readline().strip()
+    except OSError:
+        line = ""
+    if not line:
+        raise SystemExit("-C after -s SEQ reads the constraint line from stdin, for --pf as for --mfe: none came")
+    return line
+
+
 def read_shape(path, lens, batch):
     """The reactivities of a --shape file, one float array per sequence (NaN: no data): lines `position reactivity`, 1-based.  With
     `batch` one block per sequence, each introduced by a `>name` line, in the sequences' order; else one block, no `>` line needed."""
@@ -368,21 +380,32 @@ def format_pf_line(sequence, res):
     return f"{sequence} {len(sequence)} {res.centroid} {res.energy:.2f} {res.centroid.count('(')} {res.mfe_frequency:.4g}"
 
 
-def write_bpp(path, names, results, cutoff):
-    """--bpp: `name i j p` per pair with p >= cutoff, 1-based; a result's probs are banded (L, W) under --pf-span, else L x L"""
+def write_bpp(path, names, results, cutoff, dense=False):
+    """--bpp: `name i j p` per pair with p >= cutoff, 1-based; a result's probs are banded (L, W) under --pf-span, else L x L
+    (`dense`: L x L although the results hold `unpaired`: those of pf_constrained_batch)"""
     from .mccaskill import band_pairs, dense_pairs
     with open(path, "w") as out:
         for k, r in enumerate(results):
             name = names[k] if names is not None and names[k] else str(k + 1)
-            banded = r.unpaired is not None                 # (what pf_span_batch alone fills)
+            banded = r.unpaired is not None and not dense   # (what pf_span_batch fills)
             for i, j, p in (band_pairs if banded else dense_pairs)(r.probs, cutoff):
                 out.write(f"{name} {i + 1} {j + 1} {p:.6g}\n")
 
 
-def main_pf(args, seqs, known, names, pf_batch=None, scorer=None):
-    """--pf: centroid, ensemble free energy and MFE share instead of the fold.  `scorer` as for main_mfe."""
+def main_pf(args, seqs, known, names, pf_batch=None, scorer=None, constraints=None, pf_constrained_batch=None):
+    """--pf: centroid, ensemble free energy and MFE share instead of the fold.  `scorer` as for main_mfe.  With -C (`constraints`: one
+    string per sequence) or --shape the ensemble under them; the line is that of --pf."""
     if args.mfe or args.kin or args.traj:
         raise SystemExit("--pf gives the ensemble of every sequence: no --mfe, no --kin, no --traj")
+    constrained = args.constraint or args.shape is not None
+    if constrained:
+        soft = None
+        if args.shape is not None:
+            from .zuker import shape_deigan
+            soft = [shape_deigan(r, args.shape_slope, args.shape_intercept) for r in read_shape(args.shape, [len(s) for s in seqs], args.batch)]
+        if pf_constrained_batch is None:
+            from .mccaskill import pf_constrained_batch
+        pf_batch = lambda sequences, temp: pf_constrained_batch(sequences, constraints, None, soft, temp, probs=bool(args.bpp))
     if pf_batch is None and args.pf_span is not None:
         from .mccaskill import pf_span_batch
         pf_batch = lambda sequences, temp: pf_span_batch(sequences, args.pf_span, temp, probs=bool(args.bpp))
@@ -391,7 +414,7 @@ def main_pf(args, seqs, known, names, pf_batch=None, scorer=None):
         pf_batch = lambda sequences, temp: _pf(sequences, temp, probs=bool(args.bpp))
     results = pf_batch(seqs, args.temp)
     if args.bpp:
-        write_bpp(args.bpp, names, results, args.bpp_cutoff)
+        write_bpp(args.bpp, names, results, args.bpp_cutoff, dense=bool(constrained))
     if args.scores:
         if scorer is None:
             from .scoring import score_rows_gpu as scorer
@@ -732,7 +755,7 @@ def _table_note():
 
 
 def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None, mea_batch=None,
-         mfe_constrained_batch=None):
+         mfe_constrained_batch=None, pf_constrained_batch=None):
     """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch` / `subopt_batch`: injection points for tests (the fold, the
     callable (results, known) -> score table that stands in for scoring.score_batch_gpu - with --mfe, --pf and --sample for
     scoring.score_rows_gpu -, the callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable
@@ -740,12 +763,15 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     the callable (sequences, n_samples, seed, temp) that stands in for mccaskill.sample_batch, and the callable (sequences, delta,
     max_structs, temp) that stands in for wuchty.subopt_batch; `mea_batch`: the callable (sequences, gamma, temp) that stands in for
     mccaskill.mea_batch; `mfe_constrained_batch`: the callable (sequences, constraints, soft_unpaired, soft_stack, temp) that stands in
-    for zuker.mfe_constrained_batch)."""
+    for zuker.mfe_constrained_batch; `pf_constrained_batch`: the callable (sequences, constraints, soft_unpaired, soft_stack, temp,
+    probs=) that stands in for mccaskill.pf_constrained_batch)."""
     args = parse_arguments(argv)
-    if (args.constraint or args.shape is not None) and not args.mfe:
-        raise SystemExit("-C and --shape FILE constrain the fold of --mfe: they need --mfe")
+    if (args.constraint or args.shape is not None) and not (args.mfe or args.pf):
+        raise SystemExit("-C and --shape FILE constrain the fold of --mfe or the ensemble of --pf: they need --mfe or --pf")
     if (args.constraint or args.shape is not None) and args.span is not None:
         raise SystemExit("-C and --shape FILE do not combine with --span")
+    if (args.constraint or args.shape is not None) and args.pf_span is not None:
+        raise SystemExit("-C and --shape FILE do not combine with --pf-span")
     if args.span is not None and not args.mfe:
         raise SystemExit("--span W restricts the pairs of --mfe: it needs --mfe")
     if args.span is not None and not 1 <= args.span <= 4096:
@@ -766,7 +792,7 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
         return main_descend(args)
     constraints = None
     if args.constraint and args.sequence is not None:
-        seqs, known, names, constraints = [args.sequence], None, None, [sys.stdin.readline().strip()]
+        seqs, known, names, constraints = [args.sequence], None, None, [read_constraint_line()]
     elif args.constraint and args.scores:              # the CSV of --scores (with a header line) carries the constraints in a column `constraint`
         import csv
         seqs, known, names = read_records(args)
@@ -806,7 +832,7 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
     if args.mea is not None:
         return main_mea(args, seqs, known, names, mea_batch, scorer)
     if args.pf:
-        return main_pf(args, seqs, known, names, pf_batch, scorer)
+        return main_pf(args, seqs, known, names, pf_batch, scorer, constraints, pf_constrained_batch)
     if args.mfe:
         return main_mfe(args, seqs, known, names, mfe_batch, scorer, constraints, mfe_constrained_batch)
     if fold_batch is None:

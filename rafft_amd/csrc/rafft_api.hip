@@ -53,7 +53,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, mfe_con_batch, mfe_span_batch, pf_batch, pf_span_batch, mea_batch, mea_probs_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch, kinfold_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, mfe_con_batch, mfe_span_batch, pf_batch, pf_con_batch, pf_span_batch, mea_batch, mea_probs_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch, kinfold_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -384,6 +384,16 @@ int rafft_pf_batch(int n_seq, const char *const *seqs, const int *lens, double t
     if (n_seq < 0 || workspace_bytes < 0 || !std::isfinite(scale_factor) || scale_factor < 0.0) return fail(RAFFT_ERR_PARAM, "bad argument");
     if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
     return pf_batch(n_seq, seqs, lens, temp, scale_factor, workspace_bytes, seq_out, db_out, prob_out);
+}
+
+int rafft_pf_constrained_batch(int n_seq, const char *const *seqs, const int *lens, double temp, const char *const *constraints,
+                               const int32_t *const *soft_unpaired, const int32_t *const *soft_stack, double scale_factor, long long workspace_bytes,
+                               rafft_pf_seq *seq_out, char *const *db_out, double *const *prob_out, double *const *unpaired_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || workspace_bytes < 0 || !std::isfinite(scale_factor) || scale_factor < 0.0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
+    return pf_con_batch(n_seq, seqs, lens, temp, constraints, soft_unpaired, soft_stack, scale_factor, workspace_bytes, seq_out, db_out, prob_out, unpaired_out);
 }
 
 int rafft_pf_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, double scale_factor, int max_span, long long workspace_bytes,

@@ -4,6 +4,7 @@
 //   mfe_batch, mfe_span_batch    minimum-free-energy folds; the same under a base-pair span, to 32768 nt
 //   mfe_con_batch                the folds of mfe_batch under hard constraints and soft terms
 //   pf_batch, pf_span_batch      partition function and pair probabilities; the same under a span, to 32768 nt
+//   pf_con_batch                 the same under hard constraints and soft terms
 //   mea_batch, mea_probs_batch   maximum-expected-accuracy structures, of sequences and of given probabilities
 //   sample_batch                 structures drawn from the ensemble
 //   subopt_batch                 every structure within an energy band
@@ -489,18 +490,16 @@ struct PfFront {
     ChunkPlan plan;
     unsigned long long n_db = 0;
     const uint8_t *d_codes; PfSeq *d_qs; double *d_aux, *d_ws; char *d_db; PfRec *d_rec; int *d_order;
+    const unsigned long long *d_con_off = nullptr; const int *d_packs = nullptr;    // under constraints: the packs, for the pf_con_* kernels
 };
 
-int pf_front(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp, double scale_factor, long long workspace_bytes, int n_tabs,
-             const size_t *cost2, PfFront &f)
+// what pf_front does once f.mfe is there
+int pf_front_tables(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp, double scale_factor, long long workspace_bytes, int n_tabs,
+                    const size_t *cost2, PfFront &f)
 {
     const int n_seq = (int)pk.L.size();
     const std::vector<int> &order = pk.fold;
     hipStream_t st = sc.st;
-    f.d_codes = sc.d_codes;
-    f.mfe.resize(n_seq);
-    for (int s = 0; s < n_seq; s++) f.mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
-    if (int rc = mfe_held(st, pk, f.d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, f.mfe.data(), nullptr)) return rc;
     f.t = pf_temp(temp);
     PfLayout y = pf_layout(pk, n_tabs, cost2, workspace_budget(workspace_bytes));
     for (int s = 0; s < n_seq; s++) pf_set_scale(y.qs[s], f.mfe[s].dcal, f.t.kt, scale_factor);
@@ -520,6 +519,49 @@ int pf_front(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp,
     return 0;
 }
 
+int pf_front(const SeqCall &sc, DevScratch &mem, const SeqPack &pk, double temp, double scale_factor, long long workspace_bytes, int n_tabs,
+             const size_t *cost2, PfFront &f)
+{
+    const int n_seq = (int)pk.L.size();
+    f.d_codes = sc.d_codes;
+    f.mfe.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) f.mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+    if (int rc = mfe_held(sc.st, pk, f.d_codes, RAFFT_MFE_LDS_LEN, workspace_bytes, f.mfe.data(), nullptr)) return rc;
+    return pf_front_tables(sc, mem, pk, temp, scale_factor, workspace_bytes, n_tabs, cost2, f);
+}
+
+// The front under constraints: mfe_con_held in place of mfe_held - the constrained objective gives the
+// scale -, the packs of `cp` on the device for the chunks, and a sequence without a structure taken out of the pack before the
+// layout: status RAFFT_ERR_INFEASIBLE, no tables, not in pk.fold.  pf_front_inside and pf_outside_probs then launch the pf_con_*
+// kernels.
+int pf_front(const SeqCall &sc, DevScratch &mem, SeqPack &pk, const ConstraintPack &cp, double temp, double scale_factor, long long workspace_bytes,
+             int n_tabs, const size_t *cost2, PfFront &f)
+{
+    const int n_seq = (int)pk.L.size();
+    hipStream_t st = sc.st;
+    f.d_codes = sc.d_codes;
+    f.mfe.resize(n_seq);
+    for (int s = 0; s < n_seq; s++) f.mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+    std::vector<int> soft(n_seq, 0);
+    if (int rc = mfe_con_held(st, pk, f.d_codes, cp, RAFFT_MFE_LDS_LEN, workspace_bytes, f.mfe.data(), soft.data(), nullptr)) return rc;
+    int first = 0;
+    while (first < n_seq && !pk.status[first]) first++;
+    for (int s = 0; s < n_seq; s++) {
+        if (pk.status[s] || f.mfe[s].dcal < MFE_INFH) continue;
+        pk.status[s] = RAFFT_ERR_INFEASIBLE; pk.L[s] = 0;
+        f.mfe[s].dcal = 0;
+        if (s < first) { first = s; pk.first_err = "sequence " + std::to_string(s) + ": no structure satisfies its constraints"; }
+    }
+    pk.fold.erase(std::remove_if(pk.fold.begin(), pk.fold.end(), [&](int s) { return pk.status[s] != 0; }), pk.fold.end());
+    int *d_packs; unsigned long long *d_off;
+    if (int rc = mem.alloc(d_packs, cp.data.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_off, cp.off.size() * 8)) return rc;
+    HIPCHK(hipMemcpyAsync(d_packs, cp.data.data(), cp.data.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_off, cp.off.data(), cp.off.size() * 8, hipMemcpyHostToDevice, st));
+    f.d_packs = d_packs; f.d_con_off = d_off;
+    return pf_front_tables(sc, mem, pk, temp, scale_factor, workspace_bytes, n_tabs, cost2, f);
+}
+
 // launches per anti-diagonal of a chunk whose longest sequence has Lmax positions: four cells per workgroup
 unsigned pf_diag_blocks(int Lmax, int d) { return (unsigned)std::min((Lmax - d + PF_NT / 64 - 1) / (PF_NT / 64), 1024); }
 
@@ -527,9 +569,17 @@ unsigned pf_diag_blocks(int Lmax, int d) { return (unsigned)std::min((Lmax - d +
 int pf_front_inside(hipStream_t st, const PfFront &f, const ChunkView &v)
 {
     for (int d = 0; d < v.Lmax; d++)
-        hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, d);
+        if (f.d_packs)
+            hipLaunchKernelGGL(pf_con_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_con_off, f.d_packs, f.d_ws,
+                               f.d_aux, f.t.beta, d);
+        else
+            hipLaunchKernelGGL(pf_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, d);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(pf_exterior_kernel, dim3(v.ny), dim3(64), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, f.t.kt, f.d_db, f.d_rec);
+    if (f.d_packs)
+        hipLaunchKernelGGL(pf_con_exterior_kernel, dim3(v.ny), dim3(64), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_con_off, f.d_packs, f.d_ws, f.d_aux, f.t.beta, f.t.kt,
+                           f.d_db, f.d_rec);
+    else
+        hipLaunchKernelGGL(pf_exterior_kernel, dim3(v.ny), dim3(64), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, f.t.kt, f.d_db, f.d_rec);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -540,10 +590,18 @@ int pf_front_inside(hipStream_t st, const PfFront &f, const ChunkView &v)
 int pf_outside_probs(hipStream_t st, const PfFront &f, const ChunkView &v, const ChunkPlan::Range &c, const std::vector<int> &order, double *const *prob_out)
 {
     for (int d = v.Lmax - 1; d >= 4; d--)
-        hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, d);
+        if (f.d_packs)
+            hipLaunchKernelGGL(pf_con_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_con_off, f.d_packs,
+                               f.d_ws, f.d_aux, f.t.beta, d);
+        else
+            hipLaunchKernelGGL(pf_out_diag_kernel, dim3(pf_diag_blocks(v.Lmax, d), v.ny), dim3(PF_NT), 0, st, g.T, f.d_qs, v.ord, f.d_codes, f.d_ws, f.d_aux, f.t.beta, d);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(pf_prob_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_ws, f.d_aux, f.d_db, f.d_rec);
     HIPCHK(hipGetLastError());
+    if (f.d_packs) {
+        hipLaunchKernelGGL(pf_con_clamp_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_con_off, f.d_ws);
+        HIPCHK(hipGetLastError());
+    }
     if (prob_out)
         for (size_t k = c.a; k < c.b; k++) {
             const PfSeq &q = f.qs[order[k]];
@@ -617,6 +675,66 @@ int pf_batch(int n_seq, const char *const *seqs, const int *lens, double temp, d
     return pf_results(st, pk, qs, f.d_rec, f.d_db, f.n_db, seq_out, db_out, [&](int s) {
         if (prob_out && prob_out[s]) memset(prob_out[s], 0, (size_t)qs[s].L * qs[s].L * sizeof(double));
     });
+}
+
+// ---- partition function and pair probabilities under constraints and soft terms
+
+// rafft_pf_constrained_batch (arguments validated by the entry point).  pf_batch's steps with the constrained front; an error of a
+// sequence's constraints is an error of the sequence, as in mfe_con_batch.  Per chunk, after the probabilities, the unpaired
+// probabilities of the sequences whose caller asked for them.
+int pf_con_batch(int n_seq, const char *const *seqs, const int *lens, double temp, const char *const *constraints, const int32_t *const *soft_unpaired,
+                 const int32_t *const *soft_stack, double scale_factor, long long workspace_bytes, rafft_pf_seq *seq_out, char *const *db_out,
+                 double *const *prob_out, double *const *unpaired_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    const ConstraintPack cp = constraint_pack(n_seq, pk.L.data(), pk.codes.data(), pk.code_off.data(), constraints, soft_unpaired, soft_stack);
+    if (cp.param_seq >= 0) return fail(RAFFT_ERR_PARAM, cp.first_err);
+    if (cp.first_seq >= 0) {
+        int first = 0;
+        while (first < n_seq && !pk.status[first]) first++;
+        if (cp.first_seq < first) pk.first_err = cp.first_err;
+        for (int s = 0; s < n_seq; s++)
+            if (cp.status[s]) { pk.status[s] = cp.status[s]; pk.L[s] = 0; }
+        pk.fold.erase(std::remove_if(pk.fold.begin(), pk.fold.end(), [&](int s) { return cp.status[s] != 0; }), pk.fold.end());
+    }
+    auto zero_numbers = [&](int s) {
+        const size_t len = (size_t)pk.len[s];
+        if (prob_out && prob_out[s]) memset(prob_out[s], 0, len * len * sizeof(double));
+        if (unpaired_out && unpaired_out[s]) memset(unpaired_out[s], 0, len * sizeof(double));
+    };
+    for (int s = 0; s < n_seq; s++) {
+        seq_out[s] = rafft_pf_seq{pk.status[s], pk.len[s], 0, 0, 0.0, 0.0};
+        dot_row(db_out[s], pk.len[s]);
+        zero_numbers(s);
+    }
+    g_err = pk.first_err;
+    if (pk.fold.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    hipStream_t st = sc.st;
+    PfFront f;
+    if (int rc = pf_front(sc, mem, pk, cp, temp, scale_factor, workspace_bytes, 6, nullptr, f)) return rc;
+    const std::vector<int> &order = pk.fold;        // without the infeasible sequences now
+    const std::vector<PfSeq> &qs = f.qs;
+    for (int s = 0; s < n_seq; s++) { seq_out[s].status = pk.status[s]; seq_out[s].mfe_dcal = f.mfe[s].dcal; }
+    g_err = pk.first_err;
+    if (order.empty()) return 0;
+    for (const ChunkPlan::Range &c : f.plan.chunks) {
+        const ChunkView v = chunk_view(c, f.d_order, order, pk);
+        if (int rc = pf_front_inside(st, f, v)) return rc;
+        if (int rc = pf_outside_probs(st, f, v, c, order, prob_out)) return rc;
+        if (!unpaired_out) continue;
+        hipLaunchKernelGGL(pf_unpaired_kernel, dim3(pf_diag_blocks(v.Lmax, 0), v.ny), dim3(PF_NT), 0, st, f.d_qs, v.ord, f.d_ws, f.d_aux);
+        HIPCHK(hipGetLastError());
+        for (size_t k = c.a; k < c.b; k++) {
+            const PfSeq &q = qs[order[k]];
+            if (unpaired_out[order[k]]) HIPCHK(hipMemcpyAsync(unpaired_out[order[k]], f.d_aux + q.aux_off, (size_t)q.L * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+    }
+    return pf_results(st, pk, qs, f.d_rec, f.d_db, f.n_db, seq_out, db_out, zero_numbers);
 }
 
 // ---- partition function and pair probabilities under a base-pair span

@@ -27,6 +27,10 @@
 // one wavefront per cell, candidates over the 64 lanes, summed by a butterfly of fixed order.
 // pf_cell and pf_out_cell are templates over a table view, so that rafft_pf_span.hip runs them over L x W tables (DESIGN.md
 // section 19); the kernels of this file use the full view PfTab.
+// They, and the exterior sums, also take a constraint policy of rafft_mfe.hip beside the view: MfeConNone
+// compiles away - every new factor stands under `if constexpr (Con::on)`, so the plain kernels keep the parent's code -, MfeConPack
+// removes candidates and puts the soft terms into the loop energies before pf_w.  The pf_con_* kernels are the three passes again
+// with a pack per sequence in device memory, for rafft_pf_constrained_batch.
 #pragma once
 
 #include "rafft_batch_layout.h"     // PfSeq, PfRec
@@ -79,18 +83,41 @@ __global__ __launch_bounds__(64) void pf_powers_kernel(const EnergyTables *ET, c
     for (int n = 1; n <= q.L; n++) { ps[n] = ps[n - 1] * inv; pb[n] = pb[n - 1] * binv; }
 }
 
-// one wavefront fills cell (i,j) of the three inside tables; every cell of a smaller j - i is there
-template <class TB>
-__device__ inline void pf_cell(const TB &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
+// the weight of leaving k, and of leaving a..b, unpaired, beside the factor `w` those positions have without constraints (pb[1],
+// pb[n], 1 / scale): 0 where the constraints forbid it, else w times the weight of the soft terms - w itself, to the bit, when
+// these are 0.  Only under a policy that is on; MfeConNone keeps the plain factor
+template <class Con>
+__device__ __forceinline__ double pf_up_w(const Con &cn, int k, double w, double beta)
+{
+    if constexpr (!Con::on) return w;
+    else return cn.up(k) ? w * pf_w(cn.u(k), beta) : 0.0;
+}
+template <class Con>
+__device__ __forceinline__ double pf_free_w(const Con &cn, int a, int b, double w, double beta)
+{
+    if constexpr (!Con::on) return w;
+    else return cn.free(a, b) ? w * pf_w(cn.U(a, b), beta) : 0.0;
+}
+
+// MfeConNone for a sequence without a pack in the pf_con_* kernels: a type of its own, so that the instantiations the plain kernels
+// inline keep their one caller, and with it their code to the instruction
+struct PfConAbsent : MfeConNone {};
+
+// one wavefront fills cell (i,j) of the three inside tables; every cell of a smaller j - i is there.  cn: the constraint policy of
+// rafft_mfe.hip; a candidate it removes adds 0.0 and its lane stays in the butterfly
+template <class TB, class Con>
+__device__ inline void pf_cell(const TB &tb, const Con &cn, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
                                double beta, int i, int j, int lane)
 {
     const int d = j - i;
     double c = 0.0, m1 = 0.0, m = 0.0;
     if (d >= 4) {
-        const int t = pair_type(S[i], S[j]);
+        int t = pair_type(S[i], S[j]);
+        if constexpr (Con::on) { if (!cn.ok(i, j)) t = 0; }
         if (t) {
             double acc = 0.0;
-            if (lane == 0) acc = pf_w(e_hairpin(T, B, d - 1, t, S, i, j), beta) * ps[d + 1];
+            if constexpr (Con::on) { if (lane == 0 && cn.free(i + 1, j - 1)) acc = pf_w(e_hairpin(T, B, d - 1, t, S, i, j) + cn.U(i + 1, j - 1), beta) * ps[d + 1]; }
+            else if (lane == 0) acc = pf_w(e_hairpin(T, B, d - 1, t, S, i, j), beta) * ps[d + 1];
             for (int x = lane; x < MFE_NIL; x += 64) {
                 const int n12 = mfe_il.v[x], n1 = n12 >> 8, n2 = n12 & 255, p = i + 1 + n1, q = j - 1 - n2;
                 if (q - p < 4) continue;
@@ -99,7 +126,11 @@ __device__ inline void pf_cell(const TB &tb, const SmallT *T, const BigT *B, con
                 const double cc = tb.c(p, q);
                 if (cc == 0.0) continue;
                 int g = 0;
-                acc += pf_w(e_intloop(T, B, n1, n2, t, rtype(t2), S[i + 1], S[j - 1], S[p - 1], S[q + 1], g), beta) * ps[n1 + n2 + 2] * cc;
+                if constexpr (Con::on) {
+                    if (!cn.free(i + 1, p - 1) || !cn.free(q + 1, j - 1)) continue;
+                    acc += pf_w(e_intloop(T, B, n1, n2, t, rtype(t2), S[i + 1], S[j - 1], S[p - 1], S[q + 1], g) + mfe_interior_soft(cn, i, j, p, q), beta) * ps[n1 + n2 + 2] * cc;
+                } else
+                    acc += pf_w(e_intloop(T, B, n1, n2, t, rtype(t2), S[i + 1], S[j - 1], S[p - 1], S[q + 1], g), beta) * ps[n1 + n2 + 2] * cc;
             }
             double ml = 0.0;                        // a stem takes five positions: k - 1 >= i + 5, k <= j - 5
             for (int k = i + 6 + lane; k <= j - 5; k += 64) ml += tb.m(i + 1, k - 1) * tb.m1(k, j - 1);
@@ -107,10 +138,10 @@ __device__ inline void pf_cell(const TB &tb, const SmallT *T, const BigT *B, con
             c = pf_wave_sum(acc);
             m1 = c * pf_w(mfe_stem_ml(T, S, L, i, j), beta);
         }
-        m1 += tb.m1(i, j - 1) * pb[1];
+        m1 += tb.m1(i, j - 1) * pf_up_w(cn, j, pb[1], beta);
         double sp = 0.0;                            // the last stem starts at k > i (k = i is m1 itself)
         for (int k = i + 1 + lane; k <= j - 4; k += 64) {
-            double left = pb[k - i];
+            double left = pf_free_w(cn, i, k - 1, pb[k - i], beta);
             if (k - 1 - i >= 4) left += tb.m(i, k - 1);
             sp += left * tb.m1(k, j);
         }
@@ -129,17 +160,36 @@ __global__ __launch_bounds__(PF_NT) void pf_diag_kernel(const EnergyTables *ET, 
     const PfTab tb = pf_tab(tabs + q.tab_off, L);
     const uint8_t *S = codes + q.code_off;
     const double *ps = aux + q.aux_off, *pb = ps + L + 1;
-    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_cell(tb, &ET->s, &ET->b, S, L, ps, pb, beta, i, i + d, lane);
+    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_cell(tb, MfeConNone(), &ET->s, &ET->b, S, L, ps, pb, beta, i, i + d, lane);
+}
+// the same under constraints: con_off[s] is where the sequence's pack lies in `packs`; MFE_CON_NONE: it has
+// none and takes the code of pf_diag_kernel - a branch that is uniform for the workgroup
+__global__ __launch_bounds__(PF_NT) void pf_con_diag_kernel(const EnergyTables *ET, const PfSeq *seqs, const int *order, const uint8_t *codes,
+                                                            const unsigned long long *con_off, const int *packs, double *tabs, const double *aux, double beta, int d)
+{
+    const int s = order[blockIdx.y];
+    const PfSeq q = seqs[s];
+    const int L = q.L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (d >= L) return;
+    const PfTab tb = pf_tab(tabs + q.tab_off, L);
+    const uint8_t *S = codes + q.code_off;
+    const double *ps = aux + q.aux_off, *pb = ps + L + 1;
+    const unsigned long long co = con_off[s];
+    if (co != MFE_CON_NONE) {
+        const MfeConPack cn(packs + co, L);
+        for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_cell(tb, cn, &ET->s, &ET->b, S, L, ps, pb, beta, i, i + d, lane);
+    } else {
+        for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_cell(tb, PfConAbsent(), &ET->s, &ET->b, S, L, ps, pb, beta, i, i + d, lane);
+    }
 }
 
 // One wavefront per sequence: the exterior sums from both ends (F[j + 1]: positions 0..j; Fr[i]: positions i..L-1), the ensemble
 // free energy, the share of the MFE structure, the range check, and the all-dot row the centroid is written into
-__global__ __launch_bounds__(64) void pf_exterior_kernel(const EnergyTables *ET, const PfSeq *seqs, const int *order, const uint8_t *codes, double *tabs,
-                                                         double *aux, double beta, double kt, char *db, PfRec *rec)
+template <class Con>
+__device__ inline void pf_exterior(const Con &cn, const EnergyTables *ET, const PfSeq &q, int s, const uint8_t *codes, double *tabs, double *aux, double beta,
+                                   double kt, char *db, PfRec *rec, double *F)
 {
-    __shared__ double F[RAFFT_MFE_MAX_LEN + 2];
-    const int s = order[blockIdx.x], lane = (int)threadIdx.x;
-    const PfSeq q = seqs[s];
+    const int lane = (int)threadIdx.x;
     const int L = q.L;
     const PfTab tb = pf_tab(tabs + q.tab_off, L);
     const SmallT *T = &ET->s;
@@ -155,7 +205,8 @@ __global__ __launch_bounds__(64) void pf_exterior_kernel(const EnergyTables *ET,
             if (c != 0.0) acc += F[i] * c * pf_w(mfe_stem_ext(T, S, L, i, j), beta);
         }
         acc = pf_wave_sum(acc);
-        if (lane == 0) F[j + 1] = F[j] * inv + acc;
+        if constexpr (Con::on) { if (lane == 0) F[j + 1] = F[j] * pf_up_w(cn, j, inv, beta) + acc; }
+        else if (lane == 0) F[j + 1] = F[j] * inv + acc;
         wave_sync();
     }
     const double z = F[L];
@@ -170,7 +221,8 @@ __global__ __launch_bounds__(64) void pf_exterior_kernel(const EnergyTables *ET,
             if (c != 0.0) acc += c * pf_w(mfe_stem_ext(T, S, L, i, j), beta) * F[j + 1];
         }
         acc = pf_wave_sum(acc);
-        if (lane == 0) F[i] = F[i + 1] * inv + acc;
+        if constexpr (Con::on) { if (lane == 0) F[i] = F[i + 1] * pf_up_w(cn, i, inv, beta) + acc; }
+        else if (lane == 0) F[i] = F[i + 1] * inv + acc;
         wave_sync();
     }
     for (int x = lane; x <= L; x += 64) gFr[x] = F[x];
@@ -187,6 +239,26 @@ __global__ __launch_bounds__(64) void pf_exterior_kernel(const EnergyTables *ET,
         }
         rec[s] = r;
     }
+}
+__global__ __launch_bounds__(64) void pf_exterior_kernel(const EnergyTables *ET, const PfSeq *seqs, const int *order, const uint8_t *codes, double *tabs,
+                                                         double *aux, double beta, double kt, char *db, PfRec *rec)
+{
+    __shared__ double F[RAFFT_MFE_MAX_LEN + 2];
+    const int s = order[blockIdx.x];
+    const PfSeq q = seqs[s];
+    pf_exterior(MfeConNone(), ET, q, s, codes, tabs, aux, beta, kt, db, rec, F);
+}
+// the same under constraints, as pf_con_diag_kernel
+__global__ __launch_bounds__(64) void pf_con_exterior_kernel(const EnergyTables *ET, const PfSeq *seqs, const int *order, const uint8_t *codes,
+                                                             const unsigned long long *con_off, const int *packs, double *tabs, double *aux, double beta, double kt,
+                                                             char *db, PfRec *rec)
+{
+    __shared__ double F[RAFFT_MFE_MAX_LEN + 2];
+    const int s = order[blockIdx.x];
+    const PfSeq q = seqs[s];
+    const unsigned long long co = con_off[s];
+    if (co != MFE_CON_NONE) pf_exterior(MfeConPack(packs + co, q.L), ET, q, s, codes, tabs, aux, beta, kt, db, rec, F);
+    else pf_exterior(PfConAbsent(), ET, q, s, codes, tabs, aux, beta, kt, db, rec, F);
 }
 
 // the exterior sums as pf_out_cell reads them: F[i] w Fr[j + 1], the weight of the exterior loop around a stem (i,j) of weight w
@@ -206,9 +278,10 @@ __device__ inline void pf_fill_wcl(double *wcl, const SmallT *T, double beta, do
 }
 
 // one wavefront fills cell (i,j) of the three outside tables; every cell of a larger j - i that the view has is there.  wcl: the
-// table of pf_fill_wcl; ex: the exterior sums
-template <class TB, class EX>
-__device__ inline void pf_out_cell(const TB &tb, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
+// table of pf_fill_wcl; ex: the exterior sums; cn: as pf_cell.  Co of a pair the constraints remove is 0: a weight there would
+// leak into the pairs inside it
+template <class TB, class EX, class Con>
+__device__ inline void pf_out_cell(const TB &tb, const Con &cn, const SmallT *T, const BigT *B, const uint8_t *S, int L, const double *ps, const double *pb,
                                    const EX &ex, const double *wcl, double beta, int i, int j, int lane)
 {
     double a = 0.0;
@@ -224,6 +297,7 @@ __device__ inline void pf_out_cell(const TB &tb, const SmallT *T, const BigT *B,
         const double x = tb.mo(h, j);
         if (x == 0.0) continue;
         double left = pb[i - h];
+        if constexpr (Con::on) left = pf_free_w(cn, h, i - 1, left, beta);
         if (i - 1 - h >= 4) left += tb.m(h, i - 1);
         a += x * left;
     }
@@ -233,9 +307,13 @@ __device__ inline void pf_out_cell(const TB &tb, const SmallT *T, const BigT *B,
             if (x != 0.0) a += x * wcl[(pair_type(S[h], S[j + 1]) * 5 + S[j]) * 5 + S[h + 1]] * tb.m(h + 1, i - 1);
         }
     double m1o = mo + pf_wave_sum(a);
-    if (j + 1 < L && tb.has(i, j + 1)) m1o += pb[1] * tb.m1o(i, j + 1);
+    if (j + 1 < L && tb.has(i, j + 1)) {
+        if constexpr (Con::on) m1o += pf_up_w(cn, j + 1, pb[1], beta) * tb.m1o(i, j + 1);
+        else m1o += pb[1] * tb.m1o(i, j + 1);
+    }
     double co = 0.0;
-    const int t = pair_type(S[i], S[j]);
+    int t = pair_type(S[i], S[j]);
+    if constexpr (Con::on) { if (!cn.ok(i, j)) t = 0; }
     if (t) {
         a = 0.0;
         if (lane == 0) a = ex(i, j, pf_w(mfe_stem_ext(T, S, L, i, j), beta)) + pf_w(mfe_stem_ml(T, S, L, i, j), beta) * m1o;
@@ -247,7 +325,11 @@ __device__ inline void pf_out_cell(const TB &tb, const SmallT *T, const BigT *B,
             const double cc = tb.co(p, q);
             if (cc == 0.0) continue;
             int g = 0;
-            a += cc * pf_w(e_intloop(T, B, n1, n2, t2, rtype(t), S[p + 1], S[q - 1], S[i - 1], S[j + 1], g), beta) * ps[n1 + n2 + 2];
+            if constexpr (Con::on) {
+                if (!cn.free(p + 1, i - 1) || !cn.free(j + 1, q - 1)) continue;
+                a += cc * pf_w(e_intloop(T, B, n1, n2, t2, rtype(t), S[p + 1], S[q - 1], S[i - 1], S[j + 1], g) + mfe_interior_soft(cn, p, q, i, j), beta) * ps[n1 + n2 + 2];
+            } else
+                a += cc * pf_w(e_intloop(T, B, n1, n2, t2, rtype(t), S[p + 1], S[q - 1], S[i - 1], S[j + 1], g), beta) * ps[n1 + n2 + 2];
         }
         co = pf_wave_sum(a);
     }
@@ -267,7 +349,30 @@ __global__ __launch_bounds__(PF_NT) void pf_out_diag_kernel(const EnergyTables *
     const PfTab tb = pf_tab(tabs + q.tab_off, L);
     const uint8_t *S = codes + q.code_off;
     const PfExtPlain ex{gF, gFr};
-    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
+    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, MfeConNone(), T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
+}
+// the same under constraints, as pf_con_diag_kernel
+__global__ __launch_bounds__(PF_NT) void pf_con_out_diag_kernel(const EnergyTables *ET, const PfSeq *seqs, const int *order, const uint8_t *codes,
+                                                                const unsigned long long *con_off, const int *packs, double *tabs, const double *aux, double beta, int d)
+{
+    __shared__ double wcl[PF_NCLOSE];
+    const int s = order[blockIdx.y];
+    const PfSeq q = seqs[s];
+    const int L = q.L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (d >= L) return;
+    const double *ps = aux + q.aux_off, *pb = ps + L + 1, *gF = pb + L + 1, *gFr = gF + L + 1;
+    const SmallT *T = &ET->s;
+    pf_fill_wcl(wcl, T, beta, ps[2]);
+    const PfTab tb = pf_tab(tabs + q.tab_off, L);
+    const uint8_t *S = codes + q.code_off;
+    const PfExtPlain ex{gF, gFr};
+    const unsigned long long co = con_off[s];
+    if (co != MFE_CON_NONE) {
+        const MfeConPack cn(packs + co, L);
+        for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, cn, T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
+    } else {
+        for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, PfConAbsent(), T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
+    }
 }
 
 // P(i,j) into the Co table, which then has the shape of the caller's buffer (0 below j - i = 4 and below the diagonal), and the
@@ -291,4 +396,34 @@ __global__ __launch_bounds__(PF_NT) void pf_prob_kernel(const PfSeq *seqs, const
             }
             tb.co(i, j) = p;
         }
+}
+
+// Under constraints a pair that every structure holds - a forced pair - has P = 1 up to rounding, and what stands on P
+// (rafft_mea_probs_batch) takes no value above 1: the P of a sequence with a pack are held to 1.0.  A sequence without one keeps
+// the bits pf_prob_kernel wrote
+__global__ __launch_bounds__(PF_NT) void pf_con_clamp_kernel(const PfSeq *seqs, const int *order, const unsigned long long *con_off, double *tabs)
+{
+    const int s = order[blockIdx.y];
+    if (con_off[s] == MFE_CON_NONE) return;
+    const PfSeq q = seqs[s];
+    const size_t LL = (size_t)q.L * q.L;
+    double *P = tabs + q.tab_off + 3 * LL;
+    for (size_t x = (size_t)blockIdx.x * PF_NT + threadIdx.x; x < LL; x += (size_t)gridDim.x * PF_NT)
+        if (P[x] > 1.0) P[x] = 1.0;
+}
+
+// unpaired[k] = 1 - sum_j P(k,j) - sum_i P(i,k) from the P table pf_prob_kernel left, into the first L doubles of the sequence's
+// aux block (ps is dead by then).  One wavefront per position and round; the sum of a position is taken in an order that L fixes
+__global__ __launch_bounds__(PF_NT) void pf_unpaired_kernel(const PfSeq *seqs, const int *order, const double *tabs, double *aux)
+{
+    const PfSeq q = seqs[order[blockIdx.y]];
+    const int L = q.L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double *P = tabs + q.tab_off + 3 * (size_t)L * L;
+    double *up = aux + q.aux_off;
+    for (int k = blockIdx.x * (PF_NT / 64) + wave; k < L; k += gridDim.x * (PF_NT / 64)) {
+        double a = 0.0;
+        for (int x = lane; x < L; x += 64) a += P[(size_t)k * L + x] + P[(size_t)x * L + k];
+        a = pf_wave_sum(a);
+        if (lane == 0) up[k] = 1.0 - a;
+    }
 }

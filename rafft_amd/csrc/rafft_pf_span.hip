@@ -79,7 +79,7 @@ __global__ __launch_bounds__(PF_NT) void pf_span_diag_kernel(const EnergyTables 
     const SmallT *T = &ET->s;
     for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) {
         const int j = i + d;
-        pf_cell(tb, T, &ET->b, S, L, ps, pb, beta, i, j, lane);
+        pf_cell(tb, MfeConNone(), T, &ET->b, S, L, ps, pb, beta, i, j, lane);
         if (lane == 0) {
             const double c = tb.c(i, j);
             const double x = c != 0.0 ? c * pf_w(mfe_stem_ext(T, S, L, i, j), beta) : 0.0;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(PF_NT) void pf_span_out_diag_kernel(const EnergyTab
     const PfTabBand tb = pf_span_view(q, tabs);
     const uint8_t *S = codes + q.code_off;
     const PfExtScaled ex{pb + q.W + 2, eF, L, eF[L]};
-    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
+    for (int i = blockIdx.x * (PF_NT / 64) + wave; i + d < L; i += gridDim.x * (PF_NT / 64)) pf_out_cell(tb, MfeConNone(), T, &ET->b, S, L, ps, pb, ex, wcl, beta, i, i + d, lane);
 }
 
 // P(i, i + d) = C Co / m_Z into the Mo table as [i][d], which then has the shape of the caller's banded buffer (0 below d = 4 and

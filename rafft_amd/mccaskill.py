@@ -3,7 +3,9 @@ user of the reference gets from ViennaRNA's RNA.fold_compound(seq, md).pf() / bp
 benchmark_results/src/vrna_mfe.py:25.  The ensemble is the one mfe_batch minimises over.  Structures drawn from that ensemble
 (rafft_sample_batch): what ViennaRNA's pbacktrack / `RNAsubopt -p` give.  Maximum-expected-accuracy structures
 and the ensemble diversity from the pair probabilities, or from pair frequencies of any rows (rafft_mea_batch /
-rafft_mea_probs_batch): what `RNAfold -p --MEA` gives."""
+rafft_mea_probs_batch): what `RNAfold -p --MEA` gives.  The ensemble under hard constraints and SHAPE
+pseudo-energies (rafft_pf_constrained_batch): what `RNAfold -p -C --enforceConstraint` and `RNAfold -p --shape`
+give."""
 import ctypes as C
 
 import numpy as np
@@ -12,13 +14,14 @@ from . import _native as N
 from . import params as _params_mod
 from .rafft import _per_sequence
 from .utils import structures_from_rows
+from .zuker import _soft_arrays
 
 
 class PfResult:
     """energy: ensemble free energy -kT ln Z in kcal/mol; centroid: the dot-bracket row of the pairs with P > 0.5; mfe_frequency:
     the share of the MFE structure in the ensemble; mfe_energy: that structure's energy in kcal/mol; probs: L x L numpy array,
     P(i pairs j) at [i][j] for i < j (None when not asked for; from pf_span_batch it is banded, shape (L, W), P(i, i+d) at [i][d]);
-    unpaired: numpy array of the L unpaired probabilities (pf_span_batch; else None).  str_struct: the centroid, so that the scorers
+    unpaired: numpy array of the L unpaired probabilities (pf_span_batch, pf_constrained_batch; else None).  str_struct: the centroid, so that the scorers
     take it as a row."""
     __slots__ = ("energy", "centroid", "mfe_frequency", "mfe_energy", "probs", "unpaired")
 
@@ -107,6 +110,63 @@ def pf_span_batch(sequences, max_span, temp=37.0, probs=True, raise_errors=True)
 
 def pf_span(sequence, max_span, temp=37.0, probs=True):
     return pf_span_batch([sequence], max_span, temp, probs)[0]
+
+
+# ---- under hard constraints and soft terms (rafft_pf_constrained_batch)
+
+def pf_constrained_batch_raw(sequences, constraints=None, soft_unpaired=None, soft_stack=None, temp=37.0, scale_factor=0.0, workspace_bytes=0,
+                             probs=True, unpaired=True):
+    """(rows, records, probs, unpaired) of rafft_pf_constrained_batch: the centroid rows, one dict per sequence with the fields of
+    rafft_pf_seq (mfe_dcal: the constrained objective), with probs=True one L x L numpy array per sequence (None beyond
+    RAFFT_PF_MAX_LEN) and with unpaired=True one array of L unpaired probabilities (None likewise).  constraints, soft_unpaired and
+    soft_stack as zuker.mfe_constrained_batch_raw takes them (shape_deigan makes soft_stack from reactivities).  Nothing is raised for
+    a sequence's own error (its row is all dots, its numbers are 0): a malformed constraint is ERR_STRUCT, constraints no structure
+    satisfies ERR_INFEASIBLE."""
+    L = N.lib()
+    _params_mod.ensure_default_params()
+    n = len(sequences)
+    enc, arr, lens, bufs, out = N.seq_arrays(sequences, rows=True)
+    con = None
+    if constraints is not None:
+        if len(constraints) != n:
+            raise ValueError(f"constraints: {len(constraints)} entries for {n} sequences")
+        con = (C.c_char_p * n)(*[None if c is None else c.encode("ascii", "replace") for c in constraints])
+    keep_u, u = _soft_arrays(soft_unpaired, sequences, "soft_unpaired")
+    keep_b, b = _soft_arrays(soft_stack, sequences, "soft_stack")
+    rec = (N.PfSeq * n)()
+    fits = [len(e) <= N.PF_MAX_LEN for e in enc]
+    pr, ptrs = _fp64_buffers([(len(e), len(e)) if ok else None for e, ok in zip(enc, fits)]) if probs else (None, None)
+    un, uptrs = _fp64_buffers([len(e) if ok else None for e, ok in zip(enc, fits)]) if unpaired else (None, None)
+    N.check(L.rafft_pf_constrained_batch(n, arr, lens, float(temp), con, u, b, float(scale_factor), int(workspace_bytes), rec, out, ptrs, uptrs))
+    del keep_u, keep_b
+    recs = [{k: getattr(r, k) for k, _ in N.PfSeq._fields_} for r in rec]
+    return [x.value.decode("ascii") for x in bufs], recs, pr, un
+
+
+def pf_constrained_batch(sequences, constraints=None, soft_unpaired=None, soft_stack=None, temp=37.0, probs=True, raise_errors=True):
+    """The ensemble of every sequence under its constraints and soft terms, as a list of PfResult that hold `unpaired` - the
+    modelled accessibility to set beside a probe; mfe_energy is the constrained objective in kcal/mol.  The centroid need not satisfy
+    a `|`.  mea_from_probs over the `probs` of these results is the MEA row under the data.  A sequence with an error raises what
+    pf_batch raises for it, a malformed constraint a ValueError, constraints no structure satisfies a RafftError (raise_errors=False:
+    its entry is None)."""
+    rows, recs, pr, un = pf_constrained_batch_raw(sequences, constraints, soft_unpaired, soft_stack, temp, probs=probs)
+    status = [r["status"] for r in recs]
+    if raise_errors:
+        for k, st in enumerate(status):
+            if st == N.ERR_STRUCT:
+                raise ValueError(f"sequence {k}: malformed constraint {constraints[k]!r} (length, characters . x | < > ( ), balance, "
+                                 "canonical forced pairs that enclose at least 3 positions)")
+            if st == N.ERR_INFEASIBLE:
+                raise N.RafftError(st, f"sequence {k}: no structure satisfies its constraints")
+
+    def make(k):
+        return PfResult(recs[k]["energy"], rows[k], recs[k]["mfe_frequency"], recs[k]["mfe_dcal"] / 100.0, pr[k] if pr is not None else None, un[k])
+    return _per_sequence(sequences, status, raise_errors, make, "pf_constrained_batch", "RAFFT_PF_MAX_LEN", _LEFT_RANGE)
+
+
+def pf_constrained(sequence, constraint=None, soft_unpaired=None, soft_stack=None, temp=37.0, probs=True):
+    one = lambda x: None if x is None else [x]
+    return pf_constrained_batch([sequence], one(constraint), one(soft_unpaired), one(soft_stack), temp, probs)[0]
 
 
 def band_to_dense(band):
