@@ -417,6 +417,39 @@ int rafft_mfe_constrained_batch(int n_seq, const char *const *seqs, const int *l
                                 long long workspace_bytes,  /* 0: 512 MiB */
                                 rafft_mfe_con_seq *seq_out, char *const *db_out /* db_out[s]: lens[s] + 1 bytes, NUL terminated */);
 
+/* Minimum-free-energy folds of two-strand dimers: what RNAcofold's MFE answers - a miRNA and its target, an
+ * antisense oligo, a probe, a primer dimer.  seqs[s] is the concatenation S = A B of the two strands, no separator, lens[s] = L =
+ * La + Lb <= RAFFT_MFE_MAX_LEN, cuts[s] = c = La: position c is the first base of B, the nick is the missing backbone bond between
+ * c-1 and c.  cuts == NULL or cuts[s] == 0: a single strand, which gets the row, dcal and n_pairs of rafft_mfe_batch byte for byte.
+ * Ensemble: canonical, non-crossing pairs; a pair (i,j) with both ends on one strand needs j - i - 1 >= 3, a pair with i < c <= j
+ * any j - i >= 1; real interior loops have at most 30 unpaired positions, as in rafft_mfe_batch.
+ * Energy of a structure: the nick lies in exactly one loop - the exterior loop if no pair spans the nick, else the loop closed by the
+ * innermost spanning pair.  Every loop that does not hold the nick has the energy rafft_eval_structure gives it.  The loop that holds
+ * the nick and the exterior loop are both scored as exterior loops: 0 for unpaired positions and e_stem(.., ext = true) for every
+ * stem in them (dangles=2), the pair that closes the nick loop read from inside - its reversed type with neighbours S[j-1], S[i+1].
+ * A neighbour across a strand end does not exist: the 5' neighbour of p exists iff p > 0 && p != c, the 3' neighbour of q iff
+ * q < L-1 && q + 1 != c.  duplex_init is added once iff at least one pair spans the nick.  There is no symmetry correction for
+ * A == B (RNAcofold's MFE has none either).
+ * duplex_init is the loaded parameter file's DuplexInit, scaled with its enthalpy to temp like every other scalar; with the built-in
+ * tables Turner 2004's 410 dcal at 37 C.  rafft_cofold_duplex_init returns the value in force (RAFFT_ERR_TEMP as for the fold).
+ * The row is traced in one fixed, documented order (section 22) and is a function of A, B, the tables and temp - not of the batch,
+ * its order, the size class or the chunks.  n_inter is the number of pairs of the row that span the nick.
+ * Size classes, max_lds_len, workspace_bytes and every error as rafft_mfe_batch; a cuts[s] outside 0 .. lens[s]-1 is
+ * RAFFT_ERR_STRUCT of that sequence only, found on the host (all-dot row, the call returns RAFFT_OK).
+ * Not here: the dimer partition function and concentrations, constraints, SHAPE or a span with a cut, more than two strands. */
+typedef struct {
+    int32_t status;
+    int32_t length;
+    int32_t dcal;        /* the minimum free energy of the dimer in dcal/mol, duplex_init included when n_inter > 0 */
+    int32_t n_pairs;     /* pairs of the row */
+    int32_t cut;         /* the cut the sequence was folded with (0: a single strand, and for a sequence with an error) */
+    int32_t n_inter;     /* pairs of the row that span the nick */
+} rafft_cofold_seq;      /* 24 bytes */
+int rafft_cofold_batch(int n_seq, const char *const *seqs /* A then B, no separator */, const int *lens, const int *cuts /* may be NULL */,
+                       double temp, int max_lds_len /* as rafft_mfe_batch */, long long workspace_bytes /* 0: 512 MiB */,
+                       rafft_cofold_seq *seq_out, char *const *db_out /* db_out[s]: lens[s] + 1 bytes, NUL terminated, no separator */);
+int rafft_cofold_duplex_init(double temp, int *dcal_out);
+
 /* Partition function, base-pair probabilities and centroid structures of a batch (McCaskill).  Replaces:
  * RNA.fold_compound(seq, md).pf() / bpp(), the calls beside the RNA.fold of benchmark_results/src/vrna_mfe.py:25.
  * The ensemble is the one rafft_mfe_batch minimises over: canonical pairs, hairpins of at least 3, interior loops of at most 30

@@ -10,6 +10,7 @@ from .params import load_params, load_params_from_viennarna, reset_params, save_
 from .rafft_kin import kinetics, kinetics_batch  # noqa: F401
 from .zuker import mfe, mfe_batch, mfe_span, mfe_span_batch, mfe_span_batch_raw  # noqa: F401
 from .zuker import mfe_constrained, mfe_constrained_batch, mfe_constrained_batch_raw, shape_deigan  # noqa: F401
+from .cofold import cofold, cofold_batch, cofold_batch_raw, cofold_duplex_init, CofoldResult  # noqa: F401
 from .mccaskill import pf, pf_batch, sample, sample_batch  # noqa: F401
 from .mccaskill import pf_span, pf_span_batch, pf_span_batch_raw, band_to_dense, band_pairs  # noqa: F401
 from .mccaskill import pf_constrained, pf_constrained_batch, pf_constrained_batch_raw  # noqa: F401

@@ -62,6 +62,12 @@ class MfeConSeq(C.Structure):
                 ("_pad", C.c_int32)]
 
 
+class CofoldSeq(C.Structure):
+    """rafft_cofold_seq: one record per sequence of rafft_cofold_batch"""
+    _fields_ = [("status", C.c_int32), ("length", C.c_int32), ("dcal", C.c_int32), ("n_pairs", C.c_int32), ("cut", C.c_int32),
+                ("n_inter", C.c_int32)]
+
+
 MFE_MAX_LEN = 4096               # RAFFT_MFE_MAX_LEN
 MFE_SOFT_MAX = 20000             # RAFFT_MFE_SOFT_MAX (dcal)
 MFE_SPAN_MAX_LEN = 32768         # RAFFT_MFE_SPAN_MAX_LEN (RAFFT_MAX_LEN)
@@ -184,7 +190,7 @@ EXPORTS = ["rafft_init", "rafft_fold_batch", "rafft_fold_submit", "rafft_fold_wa
            "rafft_findpath_counters", "rafft_descend_batch", "rafft_descend_counters", "rafft_barriers_batch",
            "rafft_barriers_free", "rafft_barriers_counters", "rafft_kinfold_batch", "rafft_kinfold_weights", "rafft_kinfold_counters",
            "rafft_mea_batch", "rafft_mea_probs_batch", "rafft_mfe_span_batch", "rafft_pf_span_batch", "rafft_mfe_constrained_batch",
-           "rafft_pf_constrained_batch"]
+           "rafft_pf_constrained_batch", "rafft_cofold_batch", "rafft_cofold_duplex_init"]
 
 _lib = None
 
@@ -278,6 +284,9 @@ def lib():
     L.rafft_mfe_constrained_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_char_p),
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(MfeConSeq),
                                               C.POINTER(C.c_void_p)]
+    L.rafft_cofold_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_longlong,
+                                     C.POINTER(CofoldSeq), C.POINTER(C.c_void_p)]
+    L.rafft_cofold_duplex_init.argtypes = [C.c_double, C.POINTER(C.c_int)]
     L.rafft_mfe_span_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_longlong, C.POINTER(MfeSeq),
                                        C.POINTER(C.c_void_p)]
     L.rafft_pf_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_longlong, C.POINTER(PfSeq),

@@ -67,6 +67,11 @@ _OPTIONS = [
                                                            "order.  Output as -C.  Not with --span")),
     (("--shape-slope",), dict(type=float, default=1.8, metavar="M", dest="shape_slope", help="with --shape: m of m ln(reactivity + 1) + b, kcal/mol (default 1.8)")),
     (("--shape-intercept",), dict(type=float, default=-0.6, metavar="B", dest="shape_intercept", help="with --shape: b, kcal/mol (default -0.6)")),
+    (("--cofold",), dict(action="store_true", help="no RAFFT fold: the minimum-free-energy structure of every two-strand dimer on the GPU (rafft_amd.cofold_batch; as\n"
+                                                   "RNAcofold's MFE).  Every sequence is written A&B, with one `&`; with -s \"A&B\" or with -sf FILE --batch.  Per\n"
+                                                   "dimer one line `A&B len rowA&rowB energy n_inter`, n_inter the pairs between the strands.  Not with any of the\n"
+                                                   "other modes, -C, --shape or --span")),
+    (("--binding",), dict(action="store_true", help="with --cofold: four more columns, the MFE of the dimer, of A and of B and the difference E(AB) - E(A) - E(B), kcal/mol")),
     (("--pf",), dict(action="store_true", help="no RAFFT fold: the partition function of every sequence on the GPU (rafft_amd.pf_batch; the ensemble of --mfe),\n"
                                                "one line per sequence: seq len centroid energy #pairs mfe_frequency - the centroid holds the pairs with\n"
                                                "probability above 0.5, energy is the ensemble free energy.  With --scores the centroid rows are scored.\n"
@@ -390,6 +395,37 @@ def write_bpp(path, names, results, cutoff, dense=False):
             banded = r.unpaired is not None and not dense   # (what pf_span_batch fills)
             for i, j, p in (band_pairs if banded else dense_pairs)(r.probs, cutoff):
                 out.write(f"{name} {i + 1} {j + 1} {p:.6g}\n")
+
+
+def format_cofold_line(dimer, res, binding=False):
+    """the line of --cofold: `A&B len rowA&rowB energy n_inter`, with --binding `E(AB) E(A) E(B) E(AB)-E(A)-E(B)` behind it"""
+    line = f"{dimer} {len(dimer) - 1} {res.row} {res.energy} {res.n_inter}"
+    return line + f" {res.energy} {res.energy_a} {res.energy_b} {res.binding}" if binding else line
+
+
+def main_cofold(args, cofold_batch=None):
+    """--cofold: the MFE structures of dimers instead of the fold"""
+    others = (args.mfe or args.pf or args.kin or args.traj or args.scores or args.findpath or args.descend or args.barriers or args.constraint
+              or args.shape is not None or args.span is not None or args.pf_span is not None or args.sample is not None or args.subopt is not None
+              or args.mea is not None or args.kinfold is not None)
+    if others:
+        raise SystemExit("--cofold gives the MFE structure of every dimer: none of the other modes, no -C, no --shape, no --span")
+    if args.sequence is None and not (args.seq_file and args.batch):
+        raise SystemExit("--cofold needs -s \"A&B\" or -sf FILE --batch")
+    seqs, _, _ = read_records(args)
+    for k, s in enumerate(seqs):
+        a, _, b = s.partition("&")
+        if s.count("&") != 1 or not a or not b:
+            raise SystemExit(f"--cofold: record {k} ({s[:40]!r}): a dimer is written A&B, with one '&' between two strands")
+    if cofold_batch is None:
+        from .cofold import cofold_batch
+    results = cofold_batch(seqs, args.temp, args.binding)
+    txt = "".join(format_cofold_line(s, r, args.binding) + "\n" for s, r in zip(seqs, results))
+    if args.output:
+        with open(args.output, "w") as out:
+            out.write(txt)
+    else:
+        sys.stdout.write(txt)
 
 
 def main_pf(args, seqs, known, names, pf_batch=None, scorer=None, constraints=None, pf_constrained_batch=None):
@@ -755,8 +791,8 @@ def _table_note():
 
 
 def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None, pf_batch=None, sample_batch=None, subopt_batch=None, mea_batch=None,
-         mfe_constrained_batch=None, pf_constrained_batch=None):
-    """`fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch` / `subopt_batch`: injection points for tests (the fold, the
+         mfe_constrained_batch=None, pf_constrained_batch=None, cofold_batch=None):
+    """`cofold_batch`: the callable (dimers, temp, monomers) that stands in for cofold.cofold_batch.  `fold_batch` / `scorer` / `kinetics` / `mfe_batch` / `pf_batch` / `sample_batch` / `subopt_batch`: injection points for tests (the fold, the
     callable (results, known) -> score table that stands in for scoring.score_batch_gpu - with --mfe, --pf and --sample for
     scoring.score_rows_gpu -, the callable (results, max_time, n_steps) that stands in for rafft_kin.kinetics_batch, the callable
     (sequences, temp) that stands in for zuker.mfe_batch, the callable (sequences, temp) that stands in for mccaskill.pf_batch,
@@ -780,6 +816,10 @@ def main(argv=None, fold_batch=None, scorer=None, kinetics=None, mfe_batch=None,
         raise SystemExit("--pf-span W and --bpp FILE belong to --pf: they need --pf")
     if args.pf_span is not None and not 1 <= args.pf_span <= 4096:
         raise SystemExit("--pf-span is 1 to 4096")
+    if args.binding and not args.cofold:
+        raise SystemExit("--binding adds the strands' energies to the lines of --cofold: it needs --cofold")
+    if args.cofold:
+        return main_cofold(args, cofold_batch)
     if args.findpath:
         if args.descend:
             raise SystemExit("--findpath and --descend are two modes")

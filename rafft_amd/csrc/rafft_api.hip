@@ -40,6 +40,7 @@
 #include "rafft_score.hip"
 #include "rafft_mfe.hip"
 #include "rafft_mfe_span.hip"
+#include "rafft_cofold.hip"
 #include "rafft_pf.hip"
 #include "rafft_pf_span.hip"
 #include "rafft_mea.hip"
@@ -53,7 +54,7 @@
 #include "rafft_sched.h"        // the scheduler thread
 #include "rafft_submit.h"       // rafft_fold_submit / rafft_fold_wait from the caller's side: validation, lanes, hand-over
 #include "rafft_seam.h"         // the seam calls: their shared entry and device-buffer owner, evaluation, rafft_expand_node, the features
-#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, mfe_con_batch, mfe_span_batch, pf_batch, pf_con_batch, pf_span_batch, mea_batch, mea_probs_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch, kinfold_batch
+#include "rafft_batch.h"        // the batch drivers on top of them: kin_batch, mfe_batch, mfe_con_batch, cofold_batch, mfe_span_batch, pf_batch, pf_con_batch, pf_span_batch, mea_batch, mea_probs_batch, sample_batch, subopt_batch, findpath_batch, descend_batch, barriers_batch, kinfold_batch
 
 // the arguments rafft_mfe_batch and rafft_pf_batch share
 static int check_seq_args(int n_seq, const char *const *seqs, const int *lens, const void *seq_out, char *const *db_out)
@@ -365,6 +366,24 @@ int rafft_mfe_constrained_batch(int n_seq, const char *const *seqs, const int *l
     if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
     return mfe_con_batch(n_seq, seqs, lens, temp, constraints, soft_unpaired, soft_stack, max_lds_len ? max_lds_len : RAFFT_MFE_LDS_LEN, workspace_bytes,
                          seq_out, db_out);
+}
+
+int rafft_cofold_batch(int n_seq, const char *const *seqs, const int *lens, const int *cuts, double temp, int max_lds_len, long long workspace_bytes,
+                       rafft_cofold_seq *seq_out, char *const *db_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (n_seq < 0 || max_lds_len < 0 || max_lds_len > RAFFT_MFE_LDS_LEN || workspace_bytes < 0) return fail(RAFFT_ERR_PARAM, "bad argument");
+    if (int rc = check_seq_args(n_seq, seqs, lens, seq_out, db_out)) return rc;
+    return cofold_batch(n_seq, seqs, lens, cuts, temp, max_lds_len ? max_lds_len : RAFFT_MFE_LDS_LEN, workspace_bytes, seq_out, db_out);
+}
+
+int rafft_cofold_duplex_init(double temp, int *dcal_out)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!dcal_out) return fail(RAFFT_ERR_PARAM, "null argument");
+    if (int rc = check_temp(temp)) return rc;
+    *dcal_out = cofold_duplex_init(temp);
+    return 0;
 }
 
 int rafft_mfe_span_batch(int n_seq, const char *const *seqs, const int *lens, double temp, int max_span, long long workspace_bytes,

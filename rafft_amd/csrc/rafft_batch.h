@@ -1,8 +1,9 @@
 // rafft_batch.h - the batch drivers: seam calls that take many items in one call and cut them into chunks whose tables fit a
-// workspace budget (workspace_budget).  Fourteen of them:
+// workspace budget (workspace_budget).  Fifteen of them:
 //   kin_batch                    folding kinetics of many graphs
 //   mfe_batch, mfe_span_batch    minimum-free-energy folds; the same under a base-pair span, to 32768 nt
 //   mfe_con_batch                the folds of mfe_batch under hard constraints and soft terms
+//   cofold_batch                 the folds of mfe_batch for two-strand dimers
 //   pf_batch, pf_span_batch      partition function and pair probabilities; the same under a span, to 32768 nt
 //   pf_con_batch                 the same under hard constraints and soft terms
 //   mea_batch, mea_probs_batch   maximum-expected-accuracy structures, of sequences and of given probabilities
@@ -410,6 +411,108 @@ int mfe_con_batch(int n_seq, const char *const *seqs, const int *lens, double te
         seq_out[s].dcal = mfe[s].dcal; seq_out[s].n_pairs = mfe[s].n_pairs; seq_out[s].pseudo_dcal = soft[s];
     }
     g_err = err;
+    return 0;
+}
+
+// ---- minimum-free-energy folds of two-strand dimers
+
+// duplex_init of the parameter set in force at `temp` (check_temp passed): the file's DuplexInit scaled with its enthalpy like
+// every other scalar; the built-in tables store none and take Turner 2004's 4.1 kcal/mol at 37 C.  A constant of the cofold
+// code, handed to its kernels as an argument: no table set holds it.
+#define COFOLD_DUPLEX_INIT_T04 410
+int cofold_duplex_init(double temp)
+{
+    const rafft_par::ParamSet &P = param_set();
+    if (P.builtin_set) return COFOLD_DUPLEX_INIT_T04;
+    if (temp == 37.0 || !P.has_dH) return P.duplex_init[0];
+    return rafft_par::rescale(P.duplex_init[0], P.duplex_init[1], (temp + rafft_par::K0) / rafft_par::TMEASURE);
+}
+
+// The dimer folds of a pack, under the caller's guard, as mfe_held: the same layout, classes and chunks, the cofold_* kernels in
+// place of the mfe_* ones, cut[s] (cut_pack; 0: a single strand) in device memory.  The HBM class per chunk: one launch per
+// anti-diagonal over the intra cells, cofold_ends_kernel, one launch per anti-diagonal over the cross cells - the last two only
+// if a sequence of the chunk has a cut - then the traceback.  inter[s]: the pairs of the row that span the nick.
+int cofold_held(hipStream_t st, const SeqPack &pk, const uint8_t *d_codes, const std::vector<int> &cut, int dinit, int lds_len, long long workspace_bytes,
+                rafft_mfe_seq *mfe, int *inter, char *const *db_out)
+{
+    const MfeLayout y = mfe_layout(pk, lds_len, workspace_budget(workspace_bytes));
+    const std::vector<MfeSeq> &qs = y.qs;
+    DevScratch mem;
+    MfeSeq *d_qs; uint32_t *d_stack; char *d_db; int4 *d_rec; int *d_order, *d_ws = nullptr, *d_cut, *d_ends;
+    if (int rc = mem.alloc(d_qs, qs.size() * sizeof(MfeSeq))) return rc;
+    if (int rc = mem.alloc(d_stack, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_ends, y.n_stack * 4 + 16)) return rc;
+    if (int rc = mem.alloc(d_db, y.n_db + 16)) return rc;
+    if (int rc = mem.alloc(d_rec, qs.size() * sizeof(int4))) return rc;
+    if (int rc = mem.alloc(d_order, y.order.size() * 4)) return rc;
+    if (int rc = mem.alloc(d_cut, cut.size() * 4)) return rc;
+    if (y.plan.max_cost) if (int rc = mem.alloc(d_ws, y.plan.max_cost + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(d_qs, qs.data(), qs.size() * sizeof(MfeSeq), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, y.order.data(), y.order.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_cut, cut.data(), cut.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_rec, 0, qs.size() * sizeof(int4), st));
+    if (!y.lds_order.empty()) {
+        HIPCHK(hipFuncSetAttribute((const void *)cofold_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, COFOLD_LDS_BYTES));
+        hipLaunchKernelGGL(cofold_lds_kernel, dim3((unsigned)y.lds_order.size()), dim3(MFE_LDS_NT), (size_t)cofold_lds_bytes(qs[y.lds_order[0]].L), st, g.T, d_qs,
+                           d_order, d_codes, d_cut, dinit, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    for (const ChunkPlan::Range &c : y.plan.chunks) {
+        const ChunkView v = chunk_view(c, d_order + y.lds_order.size(), y.hbm_order, pk);
+        bool dimers = false;
+        for (size_t k = c.a; k < c.b; k++) dimers |= cut[y.hbm_order[k]] != 0;
+        for (int cross = 0; cross <= (dimers ? 1 : 0); cross++) {
+            for (int d = cross; d < v.Lmax; d++) {
+                const unsigned nx = (unsigned)std::min((v.Lmax - d + MFE_HBM_NT / 64 - 1) / (MFE_HBM_NT / 64), 1024);
+                hipLaunchKernelGGL(cofold_diag_kernel, dim3(nx, v.ny), dim3(MFE_HBM_NT), 0, st, g.T, d_qs, v.ord, d_codes, d_cut, dinit, d_ends, d_ws, d, cross);
+            }
+            HIPCHK(hipGetLastError());
+            if (!cross && dimers) {
+                hipLaunchKernelGGL(cofold_ends_kernel, dim3(v.ny), dim3(64), 0, st, g.T, d_qs, v.ord, d_codes, d_cut, d_ends, d_ws);
+                HIPCHK(hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(cofold_traceback_kernel, dim3(v.ny), dim3(64), 0, st, g.T, d_qs, v.ord, d_codes, d_cut, dinit, d_ends, d_ws, d_stack, d_db, d_rec);
+        HIPCHK(hipGetLastError());
+    }
+    return mfe_results(st, qs, d_rec, d_db, y.n_db, mfe, db_out, inter);
+}
+
+// rafft_cofold_batch (arguments validated by the entry point)
+int cofold_batch(int n_seq, const char *const *seqs, const int *lens, const int *cuts, double temp, int lds_len, long long workspace_bytes, rafft_cofold_seq *seq_out,
+                 char *const *db_out)
+{
+    if (int rc = check_temp(temp)) return rc;
+    if (n_seq == 0) return 0;
+    SeqPack pk = pack_sequences(n_seq, seqs, lens, RAFFT_MFE_MAX_LEN);
+    const CutPack cp = cut_pack(n_seq, pk.L.data(), cuts);
+    // a bad cut is an error of the sequence: it is not folded, and the first error in input order is named
+    if (cp.first_seq >= 0) {
+        int first = 0;
+        while (first < n_seq && !pk.status[first]) first++;
+        if (cp.first_seq < first) pk.first_err = cp.first_err;
+        for (int s = 0; s < n_seq; s++)
+            if (cp.status[s]) { pk.status[s] = cp.status[s]; pk.L[s] = 0; }
+        pk.fold.erase(std::remove_if(pk.fold.begin(), pk.fold.end(), [&](int s) { return cp.status[s] != 0; }), pk.fold.end());
+    }
+    for (int s = 0; s < n_seq; s++) {
+        seq_out[s] = rafft_cofold_seq{pk.status[s], pk.len[s], 0, 0, pk.status[s] ? 0 : cp.cut[s], 0};
+        dot_row(db_out[s], pk.len[s]);
+    }
+    g_err = pk.first_err;
+    if (pk.fold.empty()) return 0;
+    SeqCall sc;
+    DevScratch mem;
+    if (int rc = sc.open(mem, pk, temp)) return rc;
+    std::vector<rafft_mfe_seq> mfe(n_seq);
+    std::vector<int> inter(n_seq, 0);
+    for (int s = 0; s < n_seq; s++) mfe[s] = rafft_mfe_seq{pk.status[s], pk.len[s], 0, 0};
+    if (int rc = cofold_held(sc.st, pk, sc.d_codes, cp.cut, cofold_duplex_init(temp), lds_len, workspace_bytes, mfe.data(), inter.data(), db_out)) return rc;
+    for (int s = 0; s < n_seq; s++) {
+        if (pk.status[s]) continue;
+        seq_out[s].dcal = mfe[s].dcal; seq_out[s].n_pairs = mfe[s].n_pairs; seq_out[s].n_inter = cp.cut[s] ? inter[s] : 0;
+    }
+    g_err = pk.first_err;
     return 0;
 }
 

@@ -48,6 +48,17 @@ RAFFT_HD constexpr int mfe_con_pack_ints(int L) { return 4 * L + 2; }
 RAFFT_HD constexpr int mfe_con_lds_bytes(int L) { return mfe_lds_bytes(L) + ((4 * mfe_con_pack_ints(L) + 15) & ~15); }
 static_assert(mfe_con_lds_bytes(RAFFT_MFE_LDS_LEN) <= MFE_CON_LDS_BYTES, "the constraint pack of RAFFT_MFE_LDS_LEN positions fits the LDS of a workgroup");
 
+// ---- minimum-free-energy folds of two-strand dimers (rafft_cofold.hip)
+
+// LDS class: G, the exterior energies of the two strand ends (L + 1 ints: FA[i] at i for i < c, FB[j] at j + 1 for j >= c, 0 at c
+// for both), behind the bases.  The kernel takes a dynamic size of its own (130112 bytes at RAFFT_MFE_LDS_LEN), so the LDS bound
+// stays rafft_mfe_lds_len() for both entry points whatever the two layouts grow by
+#define COFOLD_LDS_BYTES (160 << 10)
+RAFFT_HD constexpr int cofold_lds_bytes(int L) { return mfe_lds_bytes(L) + ((4 * (L + 1) + 15) & ~15); }
+static_assert(cofold_lds_bytes(RAFFT_MFE_LDS_LEN) <= COFOLD_LDS_BYTES, "G of RAFFT_MFE_LDS_LEN positions fits the LDS of a workgroup");
+// HBM class: G of a sequence lies in a buffer of its own, as long as the stacks, at the sequence's stack_off (MfeSeq): its L + 1
+// ints fit the L + 8 words a stack has
+
 // ---- minimum-free-energy folds under a base-pair span (rafft_mfe_span.hip)
 
 // What a sequence of L positions folded with pairs of at most max_span positions has on the device.  W = min(max_span, L) cells

@@ -3,7 +3,8 @@
 // rafft_batch.h: chunks within a budget, the sequence pack, the graph pack, the solve order, the scale of a partition function,
 // and the layouts - every offset the drivers' kernels dereference, as records of rafft_batch_layout.h - with, for the drivers
 // that need them, the moves and conflict masks of findpath, the row intake of descend, barriers and kinfold, the tree of
-// barriers, the weight table and argument checks of kinfold, the constraint packs of the constrained MFE folds.
+// barriers, the weight table and argument checks of kinfold, the constraint packs of the constrained MFE folds, the cuts of the
+// dimer folds.
 // Plain C++ (g++ compiles it alone: the programs of tests/hostcheck).  Part of the single translation unit of rafft_api.hip
 // (included there, before the kernels).
 #pragma once
@@ -308,6 +309,31 @@ static MfeLayout mfe_layout(const SeqPack &pk, int lds_len, size_t budget)
     y.order = y.lds_order;
     y.order.insert(y.order.end(), y.hbm_order.begin(), y.hbm_order.end());
     return y;
+}
+
+// rafft_cofold_batch: the cuts of a call as the kernels read them.  cut[s] = cuts[s] for a sequence without
+// an error, 0 (a single strand) for one with an error and for all of them when cuts is null.  A cut outside 0 .. L[s] - 1 is
+// RAFFT_ERR_STRUCT of that sequence (status[s]; first_seq, first_err: the first of them); L[s] = 0: the sequence has an error already.
+struct CutPack {
+    std::vector<int> status, cut;
+    int first_seq = -1;
+    std::string first_err;
+};
+static CutPack cut_pack(int n_seq, const int *L, const int *cuts)
+{
+    CutPack p;
+    p.status.assign(n_seq, 0);
+    p.cut.assign(n_seq, 0);
+    for (int s = 0; s < n_seq; s++) {
+        if (!L[s] || !cuts) continue;
+        if (cuts[s] < 0 || cuts[s] >= L[s]) {
+            p.status[s] = RAFFT_ERR_STRUCT;
+            if (p.first_seq < 0) { p.first_seq = s; p.first_err = "sequence " + std::to_string(s) + ": cut outside 0 .. length - 1"; }
+            continue;
+        }
+        p.cut[s] = cuts[s];
+    }
+    return p;
 }
 
 // rafft_mfe_constrained_batch: the constraint packs of a call, as the kernels read them (the layout is

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(MFE_SPAN_NT) void mfe_span_diag_kernel(const Energy
     const SmallT *T = &ET->s;
     for (int i = blockIdx.x * (MFE_SPAN_NT / 64) + wave; i + d < L; i += gridDim.x * (MFE_SPAN_NT / 64)) {
         const int j = i + d;
-        mfe_cell(tb, MfeConNone(), T, &ET->b, S, L, i, j, lane);
+        mfe_cell(tb, MfeConNone(), MfeCutNone(), T, &ET->b, S, L, i, j, lane);
         if (lane == 0) {
             const int c = tb.c(i, j);
             tb.x(i, j) = c < MFE_INFH ? c + mfe_stem_ext(T, S, L, i, j) : MFE_INF;
@@ -144,5 +144,5 @@ __global__ __launch_bounds__(64) void mfe_span_traceback_kernel(const EnergyTabl
     const int *in = fs + q.f_off;
     for (int x = lane; x <= L; x += 64) F[x] = in[x];
     wave_sync();
-    mfe_traceback(mfe_span_view(q, tabs), MfeWalkBand{q.W}, MfeConNone(), &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, lane);
+    mfe_traceback(mfe_span_view(q, tabs), MfeWalkBand{q.W}, MfeConNone(), MfeCutNone(), &ET->s, &ET->b, codes + q.code_off, L, F, stacks + q.stack_off, L + 8, db + q.db_off, rec + s, lane);
 }
