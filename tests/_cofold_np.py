@@ -13,7 +13,12 @@ between c-1 and c.  DESIGN.md section 22 states the model.
   or with the last reproducing candidate of every cell ("last").  `defect` gives a mirror with a defect, there to show what the
   enumeration check catches: "split_k" - the splits of M and of the multiloop term forget that the bond before k must exist,
   which changes nothing, because M1[c][j] holds no structure anyway (its stem needs i != c): the test of the splits is implied;
-  "branch_start" - the splits and M1's stem all forget it, so a multiloop takes a branch that begins at c across the nick.
+  "branch_start" - the splits and M1's stem all forget it, so a multiloop takes a branch that begins at c across the nick;
+  "fa_two_rounds" / "fb_two_rounds" - FA keeps the stems (i,j) with j < i + 4 + 128 only, FB the stems (i,j) with i < c + 128:
+  what a 64-lane loop over the candidates of a strand end computes when it stops after two rounds (values only: `mfe_cut`).
+  After `fold_cut`, `ties` counts per kind of decision - F, FA, FB, M, M1, C_intra, C_cross - the decision points of that
+  traceback with more than one reproducing candidate, and for the cross cells how many of them set the nick loop against an
+  interior loop (C_cross_nick_interior) and against a split (C_cross_nick_split).
 """
 from functools import lru_cache
 
@@ -114,12 +119,17 @@ def multiloop_with_cross_branch(row, c):
     return False
 
 
+TIE_KINDS = ("F", "FA", "FB", "M", "M1", "C_intra", "C_cross")
+TIE_NICK = ("C_cross_nick_interior", "C_cross_nick_split")
+
+
 class CutMirror(Mirror):
     def __init__(self, tables, duplex_init, defect=None):
         super().__init__(tables)
-        assert defect in (None, "split_k", "branch_start")
+        assert defect in (None, "split_k", "branch_start", "fa_two_rounds", "fb_two_rounds")
         self.dinit = int(duplex_init)
         self.defect = defect
+        self.ties = dict.fromkeys(TIE_KINDS + TIE_NICK, 0)
         self._cut_filled = {}
 
     def _stem_ext(self, S, c, i, j):
@@ -146,7 +156,7 @@ class CutMirror(Mirror):
 
     def _bonds(self, k, c):
         """which of the positions k have the bond before them"""
-        return np.ones(len(k), dtype=bool) if self.defect else k != c
+        return np.ones(len(k), dtype=bool) if self.defect in ("split_k", "branch_start") else k != c
 
     def _cell(self, seq, S, c, C, M, M1, G, a, b):
         L, sc = len(S), self.sc
@@ -190,10 +200,13 @@ class CutMirror(Mirror):
             for a in range(0, L - d):
                 if not a < c <= a + d:
                     self._cell(seq, S, c, C, M, M1, G, a, a + d)
+        fb_end = c + 2 * 64 if self.defect == "fb_two_rounds" else L           # the candidates a loop of two rounds of 64 reaches
+        fa_len = 2 * 64 if self.defect == "fa_two_rounds" else L
         for j in range(c, L):
-            G[j + 1] = min([G[j]] + [G[i] + int(C[i, j]) + self._stem_ext(S, c, i, j) for i in range(c, j - MIN_HP) if C[i, j] < BIG])
+            G[j + 1] = min([G[j]] + [G[i] + int(C[i, j]) + self._stem_ext(S, c, i, j) for i in range(c, min(j - MIN_HP, fb_end)) if C[i, j] < BIG])
         for i in range(c - 1, -1, -1):
-            G[i] = min([G[i + 1]] + [int(C[i, j]) + self._stem_ext(S, c, i, j) + G[j + 1] for j in range(i + MIN_HP + 1, c) if C[i, j] < BIG])
+            G[i] = min([G[i + 1]] + [int(C[i, j]) + self._stem_ext(S, c, i, j) + G[j + 1] for j in range(i + MIN_HP + 1, min(c, i + MIN_HP + 1 + fa_len))
+                                     if C[i, j] < BIG])
         for d in range(1, L):
             for a in range(max(0, c - d), min(c, L - d)):
                 self._cell(seq, S, c, C, M, M1, G, a, a + d)
@@ -214,7 +227,12 @@ class CutMirror(Mirror):
         if not c:
             dcal, row = self.fold(seq, order)
             return dcal, row, 0
-        pick = (lambda hits: hits[0]) if order == "first" else (lambda hits: hits[-1])
+        ties = self.ties = dict.fromkeys(TIE_KINDS + TIE_NICK, 0)
+        take = (lambda hits: hits[0]) if order == "first" else (lambda hits: hits[-1])
+
+        def pick(hits, kind):
+            ties[kind] += len(hits) > 1
+            return take(hits)
         L, sc = len(seq), self.sc
         if (seq, c) not in self._cut_filled:
             self._cut_filled[seq, c] = self.fill_cut(seq, c)
@@ -227,7 +245,7 @@ class CutMirror(Mirror):
         while j >= 1:
             v = F[j + 1]
             hits = ([-1] if v == F[j] else []) + [i for i in range(0, j) if C[i, j] < BIG and F[i] + ext(i, j) == v]
-            i = pick(hits)
+            i = pick(hits, "F")
             if i < 0:
                 j -= 1
                 continue
@@ -238,7 +256,7 @@ class CutMirror(Mirror):
             if kind == "FA":
                 while i <= j:
                     hits = ([-1] if G[i] == G[i + 1] else []) + [y for y in range(i + MIN_HP + 1, j + 1) if C[i, y] < BIG and ext(i, y) + G[y + 1] == G[i]]
-                    y = pick(hits)
+                    y = pick(hits, "FA")
                     if y < 0:
                         i += 1
                         continue
@@ -248,7 +266,7 @@ class CutMirror(Mirror):
             if kind == "FB":
                 while j >= i:
                     hits = ([-1] if G[j + 1] == G[j] else []) + [y for y in range(i, j - MIN_HP) if C[y, j] < BIG and G[y] + ext(y, j) == G[j + 1]]
-                    y = pick(hits)
+                    y = pick(hits, "FB")
                     if y < 0:
                         j -= 1
                         continue
@@ -265,7 +283,7 @@ class CutMirror(Mirror):
                     k = np.arange(i + 1, j + 1)
                     a, b = M[i, k - 1], M1[k, j]
                     hits += [("split", int(x)) for x in k[(a < BIG) & (b < BIG) & (k != c) & (a + b == v)]]
-                    what, k = pick(hits)
+                    what, k = pick(hits, "M")
                     if what == "skip":
                         i += 1
                         continue
@@ -283,7 +301,7 @@ class CutMirror(Mirror):
                         hits.append("C")
                     if j > i and M1[i, j - 1] < BIG and j != c and int(M1[i, j - 1]) + mlb == v:
                         hits.append("skip")
-                    if pick(hits) == "C":
+                    if pick(hits, "M1") == "C":
                         break
                     j -= 1
             pt[i], pt[j] = j, i
@@ -300,7 +318,10 @@ class CutMirror(Mirror):
                 close = sc["ml_closing"] + self.stem(int(RT[t]), int(S[j - 1]), int(S[i + 1]), False)
                 a, b = M[i + 1, k - 1], M1[k, j - 1]
                 hits += [("split", int(x)) for x in k[(a < BIG) & (b < BIG) & (k != c) & (a + b + close == v)]]
-            what, x = pick(hits)
+            what, x = pick(hits, "C_cross" if cross else "C_intra")
+            if cross and len(hits) > 1 and hits[0][0] == "nick":
+                ties["C_cross_nick_interior"] += any(h[0] == "interior" for h in hits)
+                ties["C_cross_nick_split"] += any(h[0] == "split" for h in hits)
             if what == "nick":
                 if i + 1 < c:
                     stack.append((i + 1, c - 1, "FA"))

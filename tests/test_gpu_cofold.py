@@ -1,7 +1,8 @@
 """rafft_cofold_batch on a real MI355X (`-m gpu`): the minimum of the definition over every structure of
 the host test's dimers, several times each in one batch mixed with single strands, under two table sets; the tests' mirror of the
 recurrences - energy, row and n_inter - at 60-105 nt and on the 133- and 197-nt sequences of _lane_rounds cut near the middle,
-where every 64-lane loop is past its second round; strands of one nt, the adjacent pair across the nick, a perfect duplex, strands
+where the 64-lane loops over the splits and the exterior loop, which span the dimer, are past their second round (the loops over
+one strand end, FA and FB, are not: tests/test_gpu_cofold_edges.py); strands of one nt, the adjacent pair across the nick, a perfect duplex, strands
 that cannot meet; swap symmetry; the same bytes in both size classes, per chunk, in another order and alone; the bytes of
 rafft_mfe_batch without a cut; another DuplexInit and other temperatures; the limits of length; a bad cut; the command line.
 Integers and bytes: no tolerance."""
