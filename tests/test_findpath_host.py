@@ -1,7 +1,7 @@
 """rafft_findpath_batch before any kernel runs: the tests' own restatement of the search
 (`_findpath_np.search`, whole-structure oracle energies) finds the exact lowest saddle of the short problems at width 256 - nothing is
 dropped there - under the built-in tables and an index-sensitive set, and loses against it at width 1 on some; the host-pure part of
-the library (moves, conflict masks, sizes, chunk plans) in a stand-alone C++ program under AddressSanitizer + UBSan; the records and
+the library (moves, conflict masks of one, two and three words, sizes, chunk plans) in a stand-alone C++ program under AddressSanitizer + UBSan; the records and
 limits against the header; bad arguments and erroneous problems without a device; barrier_rates on a constructed graph.  No GPU."""
 import ctypes
 import os
@@ -15,6 +15,7 @@ import oracle
 from rafft_amd import _native, params, rafft_kin
 from rafft_amd import findpath as FPm
 from conftest import ROOT
+import _findpath_cases as FC
 import _findpath_np as FP
 import _loops as LP
 import _par_reader as PR
@@ -94,7 +95,13 @@ def test_host_pure_part_against_the_tests_values_under_sanitizers(tmp_path):
         mv, n_rem = FP.move_list(a, b)
         n_cross += any(FP.conflict_masks(mv, n_rem))
     assert n_cross >= 50
-    crossing = describe("(((......))).........", "......(((......)))...")
+    # ... and the problems of two and three mask words (_findpath_cases): removals and conflict words past bit 63
+    wide = [prob for _, prob, *_ in FC.removal_cases() + FC.addition_cases() + FC.dedup_cases()]
+    assert sorted({FC.mask_words(FC.dist(p)[0]) for p in wide}) == [1, 2, 3]
+    for seq, a, b in wide:
+        argv += [seq, a, b, OKAY, describe(a, b)]
+    assert describe(*wide[7][1:]).split(";")[2].split(",")[:2] == ["8000000000000000:1:0", "0:3:0"]
+    crossing =describe("(((......))).........", "......(((......)))...")
     assert crossing == "3;0-11,1-10,2-9,6-17,7-16,8-15;7,7,7"
     src = os.path.join(ROOT, "tests", "hostcheck", "findpath_check.cpp")
     for tag, flags in (("plain", ["-O1"]), ("san", ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):

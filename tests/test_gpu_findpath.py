@@ -68,8 +68,9 @@ def bits(recs, moves, dcal, k):
     return (tuple(recs[k].items()), moves[k].tobytes(), dcal[k].tobytes())
 
 
-def same_as_mirror(prob, width, rec, moves, dcal):
-    want = FP.search(*prob, width)
+def same_as_mirror(prob, width, rec, moves, dcal, want=None):
+    """`want`: what FP.search(*prob, width) returned, where the caller holds it already"""
+    want = want or FP.search(*prob, width)
     assert rec["status"] == 0 and rec["length"] == rec["dist"] == want["dist"], (prob, width, rec)
     got = {k: rec[k] for k in ("start_dcal", "end_dcal", "saddle_dcal", "saddle_step")}
     assert got == {k: want[k] for k in got}, (prob, width, rec, want)
